@@ -7,6 +7,13 @@ other BASELINE configs (5-term OR top-100, 3-word phrase, mixed AND/OR stream) a
 
     python bench.py --gpus N --steps K --warmup W        # N > 1: spawns the N ranks itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # also fine
+    python bench.py --full ...                           # everything below, not just the headline
+    python bench.py --dump-outputs DIR ...               # + the last timed step's results as DIR/*.npy
+
+A plain run builds the workload, warms up, times the K steps and prints the headline line (metric, value,
+ms_per_step, the kernel / host times of the timed steps).  Everything else is --full: the exhaustive mode
+beside the timed one, the oracle spot checks, latency, roofline (rocprofv3 passes), CPU baselines, the other
+workloads, strong scaling and the stream block.
 
 One step = one pass of the hot path over one batch of queries (posting lists resident in HBM;
 query weights prepared outside the timed region, like `query.weight()` in tantivy's benches).
@@ -88,6 +95,13 @@ def parse_args(argv=None):
                          "batch while this one is planned and enqueued; profiles/r05_stream_prepare_thread.txt has both)")
     ap.add_argument("--check-queries", type=int, default=512,
                     help="queries of every workload checked against the oracle, spread over the kernel families that ran")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: pruned == exhaustive, oracle spot checks, latency, roofline "
+                         "(rocprofv3 passes), CPU baselines, other workloads, strong scaling, stream block (off: set up, "
+                         "warm up, time the steps, print the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the main workload's last step (scores, segment_ords, docs, counts "
+                         "of every query) as DIR/<name>.npy in float32 / float64")
     return ap.parse_args(argv)
 
 
@@ -383,9 +397,10 @@ class Cluster:
                                   "C ABI (%s)" % self.comm.library)
 
 
-def measure(cl, runner, torch, queries, k, steps, warmup, time_exhaustive=False):
+def measure(cl, runner, torch, queries, k, steps, warmup, time_exhaustive=False, both_modes=True):
     """Both modes once (parity + algorithmic bytes), then W warm-up and K timed steps of the
-    chosen mode, pipelined, bracketed by barrier + synchronize; max over ranks."""
+    chosen mode, pipelined, bracketed by barrier + synchronize; max over ranks.  both_modes=False
+    (a plain run): the chosen mode's synchronous steps only, no parity, no algorithmic bytes."""
     runner.prepare(queries, k)
 
     def one(exhaustive, n):
@@ -397,11 +412,14 @@ def measure(cl, runner, torch, queries, k, steps, warmup, time_exhaustive=False)
             st = runner.batch_stats()
         return runner.results(), st
 
-    exh_out, exh_st = one(True, 1)
-    _, exh_st2 = one(True, 2)
-    prn_out, prn_st = one(False, 1)
-    _, prn_st2 = one(False, 2)
-    same = all(np.array_equal(a, b) for a, b in zip(exh_out, prn_out))
+    if both_modes:
+        exh_out, exh_st = one(True, 1)
+        _, exh_st2 = one(True, 2)
+        prn_out, prn_st = one(False, 1)
+        _, prn_st2 = one(False, 2)
+        same = all(np.array_equal(a, b) for a, b in zip(exh_out, prn_out))
+    else:
+        one(time_exhaustive, 3)  # (first-use tables of the batch's terms: built here, as in a --full run)
     runner.set_option("exhaustive", 1 if time_exhaustive else 0)
     import gc
     gc.collect()  # (before the warm-up, not between it and the timed steps: a collection evicts the planner's tables
@@ -430,10 +448,38 @@ def measure(cl, runner, torch, queries, k, steps, warmup, time_exhaustive=False)
     if gc_was:
         gc.enable()
     st = runner.batch_stats()  # HIP-event kernel time, mean over the timed steps (<= last 16)
+    if not both_modes:
+        return {"elapsed": elapsed, "stats": st, "final": runner.results()}
     return {"elapsed": elapsed, "stats": st, "final": runner.results(), "mode_parity": same,
             "n_diff": int(np.sum(np.any(exh_out[2] != prn_out[2], axis=1))),
             "exh_stats": exh_st2, "prn_stats": prn_st2,
             "algo_bytes_full": exh_st["algorithmic_bytes"], "full_matches": exh_st["matches"]}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, final):
+    """The last timed step's results as a caller receives them, one .npy per array: scores (float32),
+    segment_ords / docs / counts (float64: exact for 32-bit integers).  Slots beyond a query's count hold
+    no result: 0 / -1 there, so that two runs compare slot for slot.  Above DUMP_BYTES_MAX a fixed, seeded
+    sample of the queries (rows.npy: which ones)."""
+    scores, ords, docs, counts = (np.asarray(a) for a in final)
+    n, k = scores.shape
+    empty = np.arange(k)[None, :] >= counts[:, None]
+    arrays = {"scores": np.where(empty, 0, scores).astype(np.float32),
+              "segment_ords": np.where(empty, -1, ords).astype(np.float64),
+              "docs": np.where(empty, -1, docs).astype(np.float64),
+              "counts": counts.astype(np.float64)}
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    if n * row_bytes > DUMP_BYTES_MAX:
+        keep = (DUMP_BYTES_MAX - 4096) // (row_bytes + 8)  # (+ rows.npy; 4 KB for the .npy headers)
+        rows = np.sort(np.random.default_rng(20261016).choice(n, keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def latency_curve(dev, queries, k):
@@ -923,9 +969,66 @@ def main():
     queries, k = build_queries(O, args.workload, n_main, args.k, args.terms)
     n_q = len(queries)
     n_distinct = len({(q[0], tuple(sorted(q[1]))) for q in queries})
-    m = measure(cl, runner, torch, queries, k, args.steps, args.warmup, args.exhaustive)
-    if not m["mode_parity"]:
+    m = measure(cl, runner, torch, queries, k, args.steps, args.warmup, args.exhaustive, both_modes=args.full)
+    if args.full and not m["mode_parity"]:
         raise SystemExit("pruned and exhaustive results differ on %d queries" % m["n_diff"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["final"])
+    st = m["stats"]
+    k_ms = st["kernel_ms"]
+    head = {
+        "metric": "queries_per_sec_2term_AND_bm25_top10" if args.workload == "and2"
+        else "queries_per_sec_" + args.workload,
+        "value": round(n_q * args.steps * world / m["elapsed"], 1),  # one unit = one query evaluated on one segment
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(m["elapsed"] / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32+f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "%s: %d queries/batch, k=%d, one %dM-doc Zipf segment per GPU (%d terms, "
+                        "df_r=0.5N/r, WithFreqs%s); term ranks ~ Zipf(1)" %
+                        (args.workload, n_q, k, args.docs // 1_000_000, args.terms,
+                         "AndPositions" if with_pos else ""),
+            "distinct_queries": n_distinct,
+            "unit_note": "weak scaling: one unit = one query evaluated on one segment; at N GPUs every "
+                         "query runs on N segments (N x %dM docs), the per-segment top-k are "
+                         "all-gathered over RCCL and merged.  The same 8-segment index at every N "
+                         "(strong scaling, config 5) is reported under strong_scaling" %
+                         (args.docs // 1_000_000),
+            "timed_region": "K x [collect_segment (plan + H2D of query descriptors + scan + merge "
+                            "kernels) -> all-gather -> merge_top_k -> D2H], enqueued back to back "
+                            "(host planning of step i+1 overlaps the GPU work of step i), one "
+                            "synchronisation at each end",
+            "mode": "block-max pruned (block_wand_intersection semantics)" if pruned_mode
+                    else "exhaustive (every match scored)",
+            "exchange": cl.exchange_note,
+            "segments_per_gpu": S_main,
+            "index_bytes": int(sum(x.idx_len for x in main_segs)),
+            "index_build_s": round(t_gen, 2),
+        },
+    }
+    if not args.full:
+        # a plain run: the headline and what the timed steps measured on the way (HIP events, host planner)
+        head["timed_steps"] = {"kernel": " + ".join(st.get("kernels") or []), "kernel_ms_avg": round(k_ms, 4),
+                               "host_plan_ms": round(st["host_plan_ms"], 3), "gpu_batch_ms": round(st["total_ms"], 4),
+                               "exchange_ms": round(runner.exchange_ms(), 4)}
+        runner.close()
+        if cl.comm is not None:
+            cl.comm.close()
+            cl.comm = None
+        if rank == 0:
+            print(json.dumps(head))
+            sys.stdout.flush()
+        cl.barrier()
+        if cl.dist is not None:
+            cl.dist.destroy_process_group()
+        return
 
     # ---- single-query latency (p50), outside the timed region
     lat = []
@@ -1179,45 +1282,10 @@ def main():
         tkey += "_s%d" % S_main
     tf = traffic_fields(load_traffic(tkey), S_main, k_ms)  # per step: one scan launch per local segment
     phys = physical_roofline(k_ms, pm_main, tf)
-    total_units = n_q * args.steps * world  # one unit = one query evaluated on one segment
-    value = total_units / m["elapsed"]
-    out = {
-        "metric": "queries_per_sec_2term_AND_bm25_top10" if args.workload == "and2"
-        else "queries_per_sec_" + args.workload,
-        "value": round(value, 1),
+    head["config"]["exchange"] = cl.exchange_note  # (config 5 set up its own exchange since)
+    out = dict(head)
+    out.update({
         "value_distinct": (side.get("and2_distinct") or {}).get("qps"),  # the same stream without repeated queries (other_workloads.and2_distinct)
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(m["elapsed"] / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32+f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "%s: %d queries/batch, k=%d, one %dM-doc Zipf segment per GPU (%d terms, "
-                        "df_r=0.5N/r, WithFreqs%s); term ranks ~ Zipf(1)" %
-                        (args.workload, n_q, k, args.docs // 1_000_000, args.terms,
-                         "AndPositions" if with_pos else ""),
-            "distinct_queries": n_distinct,
-            "unit_note": "weak scaling: one unit = one query evaluated on one segment; at N GPUs every "
-                         "query runs on N segments (N x %dM docs), the per-segment top-k are "
-                         "all-gathered over RCCL and merged.  The same 8-segment index at every N "
-                         "(strong scaling, config 5) is reported under strong_scaling" %
-                         (args.docs // 1_000_000),
-            "timed_region": "K x [collect_segment (plan + H2D of query descriptors + scan + merge "
-                            "kernels) -> all-gather -> merge_top_k -> D2H], enqueued back to back "
-                            "(host planning of step i+1 overlaps the GPU work of step i), one "
-                            "synchronisation at each end",
-            "mode": "block-max pruned (block_wand_intersection semantics)" if pruned_mode
-                    else "exhaustive (every match scored)",
-            "exchange": cl.exchange_note,
-            "segments_per_gpu": S_main,
-            "index_bytes": int(sum(x.idx_len for x in main_segs)),
-            "index_build_s": round(t_gen, 2),
-        },
         "roofline": {
             "bound": "hbm",
             "achieved": phys["achieved"],
@@ -1282,7 +1350,7 @@ def main():
         "stream": stream,
         "other_workloads": side or None,
         "strong_scaling": strong,
-    }
+    })
     print(json.dumps(out))
     sys.stdout.flush()
     cl.barrier()

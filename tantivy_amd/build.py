@@ -127,7 +127,8 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as pool:
+    jobs = int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 1  # (MAX_JOBS: the CPUs this build may use)
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), jobs)) as pool:
         list(pool.map(compile_one, zip(SOURCES, objs)))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
     if verbose:

@@ -167,14 +167,14 @@ def test_planners_under_thread_sanitizer(tmp_path_factory):
         src = u if os.path.isabs(u) else os.path.join(csrc, u)
         obj = str(d / (os.path.basename(src) + ".o"))
         r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fPIC",
-                            "-Wno-unused-function", "-fsanitize=thread", "-c", src, "-o", obj], capture_output=True, text=True)
+                            "-Wno-unused-function", "-fsanitize=thread", "-fno-gpu-sanitize", "-c", src, "-o", obj], capture_output=True, text=True)
         if r.returncode != 0:
             pytest.skip("no ThreadSanitizer build here: " + r.stderr[-300:])
         tsan_objs.append(obj)
     others = [os.path.join(B.OBJ_DIR, os.path.basename(s) + ".o") for s in B.SOURCES
               if os.sep + "csrc" + os.sep in s and os.path.basename(s) not in units]
     exe = str(d / "plan_check_tsan")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-fsanitize=thread", "-o", exe] + tsan_objs + others +
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-fsanitize=thread", "-fno-gpu-sanitize", "-o", exe] + tsan_objs + others +
                        ["-ldl", "-lpthread"], capture_output=True, text=True)
     if r.returncode != 0:
         pytest.skip("ThreadSanitizer runtime not linkable here: " + r.stderr[-300:])

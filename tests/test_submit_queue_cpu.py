@@ -148,7 +148,7 @@ def test_submit_queue_stress(tmp_path_factory, sanitize):
     src = d / "submit_stress.cpp"
     src.write_text(SRC)
     csrc = os.path.join(ROOT, "tantivy_amd", "csrc")
-    flags = ["-fsanitize=thread"] if sanitize == "thread" else []
+    flags = ["-fsanitize=thread", "-fno-gpu-sanitize"] if sanitize == "thread" else []
     obj = str(d / "submit_stress.o")
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-Wno-unused-function",
                         "-I", csrc, "-I", os.path.join(ROOT, "include")] + flags + ["-c", str(src), "-o", obj],

@@ -1,11 +1,11 @@
 #!/bin/bash
-# the default bench line (what the driver runs) + its wall time
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out
-{ time python bench.py > gpurun_out/r6_bench_line.json 2> gpurun_out/r6_bench_err.txt ; } 2> gpurun_out/r6_bench_time.txt
-tail -c 600 gpurun_out/r6_bench_err.txt; cat gpurun_out/r6_bench_time.txt
-python - <<'PY'
-import json
-j=json.loads(open("gpurun_out/r6_bench_line.json").read().strip().splitlines()[-1])
+# the full bench line (bench.py --full) + its wall time, in $OUT (default results/)
+cd "$(dirname "$0")/.."; OUT=${OUT:-results}; mkdir -p "$OUT"
+{ time python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_err.txt" ; } 2> "$OUT/bench_time.txt"
+tail -c 600 "$OUT/bench_err.txt"; cat "$OUT/bench_time.txt"
+OUT="$OUT" python - <<'PY'
+import json, os
+j=json.loads(open(os.path.join(os.environ["OUT"], "bench_line.json")).read().strip().splitlines()[-1])
 r=j["roofline"]
 print("HEADLINE", j["value"], "q/s  distinct", j.get("value_distinct"), " ms/step", j["ms_per_step"], "kernel", r["kernel_ms_avg"], "host", r["host_plan_ms"], "frac", r["frac"], "traffic", r["traffic"], "p50", j["p50_latency_ms"])
 print("cpu", j["cpu_baseline"]["value"] if j["cpu_baseline"] else None)

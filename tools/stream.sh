@@ -1,7 +1,7 @@
 #!/bin/bash
 # the stream block alone (fresh batches, Query::weight timed): serial against a preparing thread one batch ahead
 for flag in "--stream-serial" ""; do
-  python bench.py --workload and2 --no-side --no-cpu-baseline --latency-queries 0 --no-pmc-inline --steps 5 --warmup 2 --stream-vocabs ${VOCABS:-256,4096} $flag 2>/dev/null | tail -1 | python -c '
+  python bench.py --full --workload and2 --no-side --no-cpu-baseline --latency-queries 0 --no-pmc-inline --steps 5 --warmup 2 --stream-vocabs ${VOCABS:-256,4096} $flag 2>/dev/null | tail -1 | python -c '
 import json,sys
 j=json.loads(sys.stdin.readline())
 for k,v in j["stream"]["by_terms"].items():

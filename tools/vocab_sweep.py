@@ -13,12 +13,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04_vocab_sweep"
 workloads = (sys.argv[2] if len(sys.argv) > 2 else "and2,or5,mixed,phrase3,bool").split(",")
 terms = [int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "256,4096,65536").split(",")]
-out = {"note": "bench.py --workload W --terms T --no-side --no-cpu-baseline --steps 10 (one 10M-doc segment; pruned "
+out = {"note": "bench.py --full --workload W --terms T --no-side --no-cpu-baseline --steps 10 (one 10M-doc segment; pruned "
                "mode timed, pruned == exhaustive and 64 oracle-checked queries per cell); ns_per_posting = kernel "
                "time / postings of the batch's lists (algorithmic bytes ~ 1.3 B per posting)", "cells": {}}
 for w in workloads:
     for t in terms:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", w, "--terms", str(t), "--no-side",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", w, "--terms", str(t), "--no-side",
                "--no-cpu-baseline", "--latency-queries", "0", "--steps", "10", "--warmup", "2"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
