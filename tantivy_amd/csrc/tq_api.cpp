@@ -205,9 +205,6 @@ void tq_segment_free(tq_segment *s) {
   if (s->d_local_cache) (void)hipFree(s->d_local_cache);
   if (s->d_match_counter) (void)hipFree(s->d_match_counter);
   s->d_stage.release();
-  s->d_out_scores.release();
-  s->d_out_docs.release();
-  s->d_out_counts.release();
   s->d_misc.release();
   for (int i = 0; i < 2; ++i) {
     s->h_prep_stage[i].release();
@@ -375,8 +372,7 @@ int tq_segment_get_stats(tq_segment *s, tq_segment_stats *out) {
   r.bitmap_bytes = s->bytes_bitmaps;
   r.docmat_bytes = s->bytes_docmat;
   r.posdir_bytes = s->bytes_posdir;
-  r.scratch_bytes = s->d_stage.cap + s->d_stage_alt.cap + s->d_out_scores.cap + s->d_out_docs.cap +
-                    s->d_out_counts.cap + s->d_misc.cap + s->d_thr.cap + s->d_qmatches.cap + s->d_share_words.cap +
+  r.scratch_bytes = s->d_stage.cap + s->d_stage_alt.cap + s->d_misc.cap + s->d_thr.cap + s->d_qmatches.cap + s->d_share_words.cap +
                     s->d_ashare_words.cap + s->d_bshare_words.cap + s->d_count_queries.cap + s->d_count_out.cap +
                     s->d_count_bits.cap + s->d_count_wgs.cap;
   {

@@ -295,7 +295,7 @@ struct tq_segment {
   std::unordered_map<uint64_t, bool> reserved_cols;
   bool cols_reserved = false;
   // batch scratch
-  DevBuf d_stage, d_out_scores, d_out_docs, d_out_counts, d_misc, d_thr, d_qmatches;
+  DevBuf d_stage, d_misc, d_thr, d_qmatches;
   DevBuf d_share_words;   // shared-union launch: per-query words
   DevBuf d_count_queries, d_count_out, d_count_bits, d_count_wgs;  // Count collector over bitmaps (tq_count.hip)
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
@@ -320,7 +320,7 @@ struct tq_segment {
   bool batch_in_flight = false;
   hipStream_t side_stream = nullptr;  // the launch groups of one batch run concurrently
   // The batch's staging blob goes up on a stream of its own, into one of two device buffers, while
-  // the previous batch's kernels still run (TQ_COPY_STREAM=0: on the batch's stream, one buffer).
+  // the previous batch's kernels still run.
   // Measured with SDMA copies: step 5.19 -> 5.12 ms on 60-step runs and a steadier step time;
   // round 1's attempt (one buffer, blit copies) had lost 8 %
   hipStream_t copy_stream = nullptr;
@@ -332,7 +332,6 @@ struct tq_segment {
              ev_k1[kTimingRing] = {};
   uint64_t batches_timed = 0, batches_reported = 0;
   bool stage_in_flight = false;
-  bool thr_seeded = false;  // (TQ_KEEP_THR experiments: the slots were zeroed once)
   double host_ms_sum = 0;   // host time inside tq_search_batch_device since the last stats call
   uint32_t host_ms_n = 0;
   unsigned long long *d_match_counter = nullptr;
@@ -465,13 +464,13 @@ struct Group {
   std::vector<uint32_t> tile_starts;
   std::vector<uint4> chunk_recs;      // launch order: {first tile, end tile, first query, chunk}
   std::vector<uint32_t> tile_cost;  // per query, cost units per tile
-  std::vector<TqdTreeQuery> tree;   // group 10: the nested boolean queries' descriptors (tq_tree.hip), one per query
+  std::vector<TqdTreeQuery> tree;   // kGTree: the nested boolean queries' descriptors (tq_tree.hip), one per query
   uint32_t total_tiles = 0, n_chunks = 0, max_k = 1;
   uint64_t list_entries = 0;  // term-major / doc-major groups: 8-byte entries of the group's result lists
   int kpl = 1;
   // offsets inside the staging blob
-  size_t o_queries = 0, o_tiles = 0, o_outidx = 0, o_chunks = 0, o_perm = 0, o_sinks = 0;
-  size_t o_leads = 0, o_tasks = 0, o_lists = 0;  // shared-union group
+  size_t o_queries = 0, o_tiles = 0, o_outidx = 0, o_chunks = 0, o_sinks = 0;
+  size_t o_leads = 0, o_tasks = 0, o_lists = 0;  // the extra tables of the shared, doc-major and tree groups
   void reset() {  // keeps the vectors' capacity
     queries.clear();
     out_index.clear();
@@ -484,7 +483,7 @@ struct Group {
     list_entries = 0;
     max_k = 1;
     kpl = 1;
-    o_queries = o_tiles = o_outidx = o_chunks = o_perm = o_sinks = 0;
+    o_queries = o_tiles = o_outidx = o_chunks = o_sinks = 0;
     o_leads = o_tasks = o_lists = 0;
   }
 };
@@ -510,15 +509,41 @@ struct ShareKey {  // one (query, list) pair of the shared-union group
   uint64_t key;    // list position i << 56 | blocks of the term (rare terms first) << 32 | cache
   uint32_t term, q;
 };
-// launch groups of a batch: 0 AND over bitmap lists, 1 unions, 2 phrases, 3 AND over any lists, 4 boolean
-// queries, 5 shared unions, 6 phrase sweep, 7 doc-major unions, 8 shared intersections, 9 boolean queries
-// through the shared-intersection launch
-constexpr int kNGroups = 11;  // (10: nested boolean queries over bitmaps, tq_tree.hip)
-struct QuerySlab {  // one slab of a batch's queries, planned by one thread into groups of its own
-  Group groups[kNGroups];
+// The launch groups of a batch.  The values are also the order of the groups' partial lists in the batch's buffer,
+// so they stay as they are.
+enum GroupId : int {
+  kGAndDense = 0,  // AND queries whose non-leader lists all have a bitmap (and_kernel's lean instantiation)
+  kGUnion = 1,     // unions (candidate-driven per query, or 4096-doc windows)
+  kGPhrase = 2,    // phrases
+  kGAnd = 3,       // AND queries over any lists
+  kGBool = 4,      // boolean queries (clauses with roles: the union kernel's BOOL instantiation)
+  kGUShare = 5,    // shared unions (term-major for the batch, tq_ushare.hip)
+  kGPhSweep = 6,   // phrases through the bitmap-AND sweep
+  kGXUnion = 7,    // unpruned unions, doc-major for the batch (tq_xunion.hip)
+  kGAShare = 8,    // shared intersections (leader-major for the batch, tq_ashare.hip)
+  kGBShare = 9,    // boolean queries through the shared-intersection launch
+  kGTree = 10,     // nested boolean queries over bitmaps (tq_tree.hip)
+  kNGroups = 11
+};
+// per group: the TQ_MODE_* of its descriptors; whether it writes result lists (part_start / n_parts count 8-byte
+// entries) rather than per-tile partials; its TQ_KERNEL_* bit (the union group's: group_kernel_bit)
+struct GroupTraits { int mode; bool result_lists; uint32_t kernel; };
+constexpr GroupTraits kGroupTraits[kNGroups] = {
+    {TQ_MODE_AND, false, TQ_KERNEL_AND_DENSE}, {TQ_MODE_OR, false, TQ_KERNEL_UNION}, {TQ_MODE_PHRASE, false, TQ_KERNEL_PHRASE},
+    {TQ_MODE_AND, false, TQ_KERNEL_AND},       {TQ_MODE_OR, false, TQ_KERNEL_BOOL},  {TQ_MODE_OR, true, TQ_KERNEL_USHARE},
+    {TQ_MODE_PHRASE, false, TQ_KERNEL_PHRASE_SWEEP}, {TQ_MODE_OR, true, TQ_KERNEL_XUNION}, {TQ_MODE_AND, true, TQ_KERNEL_ASHARE},
+    {TQ_MODE_OR, true, TQ_KERNEL_BSHARE},      {TQ_MODE_OR, false, TQ_KERNEL_TREE}};
+inline uint32_t group_kernel_bit(int gi, bool or_windows) {
+  return gi == kGUnion && or_windows ? TQ_KERNEL_OR_WINDOWS : kGroupTraits[gi].kernel;
+}
+struct RouteTotals {  // what routing a run of queries adds up besides the groups' descriptors
   uint32_t n_thr_rows = 0;
   uint64_t algo_bytes = 0;
-  bool phrase_all_dense = true;
+  bool phrase_all_dense = true;  // (the phrase group may run the lean instantiation)
+};
+struct QuerySlab {  // one slab of a batch's queries, planned by one thread into groups of its own
+  Group groups[kNGroups];
+  RouteTotals t;
   int rc = 0;
   std::string err;
 };
@@ -531,6 +556,7 @@ struct PlanScratch {
   std::vector<TqkDenseQuery> xqueries;
   std::vector<uint64_t> xrow_term;           // row -> term handle << 32 | weight bits, in order of first use
   std::unordered_map<uint64_t, uint32_t> xrow_of;  // ... -> row
+  uint32_t xcache = 0xFFFFFFFFu;  // the group's one Bm25Weight cache
   uint32_t xgrid = 0, x_bitmap_rows = 0, x_tiles_per_task = 1, x_list_stride = 0, x_max_terms = 1;
   // shared-union group (tq_ushare.hip): leads grouped by term, tasks in launch order
   std::vector<ShareKey> share_keys, share_keys2;

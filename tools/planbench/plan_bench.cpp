@@ -38,7 +38,7 @@ static int bench_share(int n_queries, int reps) {
   PlanScratch ps;
   double best = 1e9;
   for (int rep = 0; rep < reps; ++rep) {
-    Group &g = ps.groups[5];
+    Group &g = ps.groups[kGUShare];
     g.reset();
     g.mode = TQ_MODE_OR;
     rng.seed(7);
@@ -86,7 +86,7 @@ static int bench_and(int n_queries, int reps) {
   PlanScratch ps;
   double best = 1e9;
   for (int rep = 0; rep < reps; ++rep) {
-    Group &g = ps.groups[0];
+    Group &g = ps.groups[kGAndDense];
     g.reset();
     g.mode = TQ_MODE_AND;
     rng.seed(7);
@@ -116,7 +116,7 @@ static int bench_and(int n_queries, int reps) {
     best = std::min(best, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   }
   printf("and: queries %d chunks %u tiles %u: build_group_chunks %.2f ms (best of %d)\n", n_queries,
-         ps.groups[0].n_chunks, ps.groups[0].total_tiles, best, reps);
+         ps.groups[kGAndDense].n_chunks, ps.groups[kGAndDense].total_tiles, best, reps);
   return 0;
 }
 
@@ -151,7 +151,7 @@ static int bench_ashare(int n_queries, int reps) {
   double best = 1e9;
   std::vector<double> all_ms;
   for (int rep = 0; rep < reps; ++rep) {
-    Group &g = ps.groups[8];
+    Group &g = ps.groups[kGAShare];
     g.reset();
     g.mode = TQ_MODE_AND;
     rng.seed(7);
@@ -204,7 +204,7 @@ int main(int argc, char **argv) {
   double best = 1e9;
   uint32_t chunks = 0;
   for (int rep = 0; rep < reps; ++rep) {
-    Group &g = ps.groups[1];
+    Group &g = ps.groups[kGUnion];
     g.reset();
     g.mode = TQ_MODE_OR;
     rng.seed(7);
@@ -251,6 +251,6 @@ int main(int argc, char **argv) {
     chunks = g.n_chunks;
   }
   printf("queries %d chunks %u tiles %u: build_group_chunks %.2f ms (best of %d)\n", n_queries, chunks,
-         ps.groups[1].total_tiles, best, reps);
+         ps.groups[kGUnion].total_tiles, best, reps);
   return 0;
 }

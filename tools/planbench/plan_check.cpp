@@ -79,7 +79,7 @@ static int check_share(int seed) {
   }
   seg.max_doc = 10000000u;
   PlanScratch ps;
-  Group &g = ps.groups[5];
+  Group &g = ps.groups[kGUShare];
   g.reset();
   g.mode = TQ_MODE_OR;
   const uint32_t nq = 700;
@@ -214,7 +214,7 @@ static int check_ashare(int seed) {
   }
   seg.max_doc = 10000000u;
   PlanScratch ps;
-  Group &g = ps.groups[8];
+  Group &g = ps.groups[kGAShare];
   g.reset();
   g.mode = TQ_MODE_AND;
   const uint32_t nq = uni(1, 4) == 1 ? uni(1, 40) : uni(500, 3000);
@@ -422,7 +422,7 @@ static int check_bshare(int seed) {
   seg.max_doc = 10000000u;
   seg.share_table_lo = (uint64_t)arena;
   PlanScratch ps;
-  Group &g = ps.groups[9];
+  Group &g = ps.groups[kGBShare];
   g.reset();
   g.mode = TQ_MODE_OR;
   const uint32_t nq = uni(1, 3) == 1 ? uni(1, 30) : uni(300, 1500);
@@ -641,7 +641,7 @@ static int check_dense(int seed) {
   }
   seg.max_doc = uni(1, 3) == 1 ? uni(1, 5000) : uni(100000, 12000000);
   PlanScratch ps;
-  Group &g = ps.groups[7];
+  Group &g = ps.groups[kGXUnion];
   g.reset();
   g.mode = TQ_MODE_OR;
   const uint32_t nq = uni(1, 900);
@@ -885,7 +885,7 @@ int main(int argc, char **argv) {
   auto uni = [&](uint32_t lo, uint32_t hi) { return std::uniform_int_distribution<uint32_t>(lo, hi)(rng); };
   PlanScratch ps;
   for (int shape = 0; shape < 3; ++shape) {  // 0 candidate unions, 1 AND-style, 2 OR windows
-    Group &g = ps.groups[1];
+    Group &g = ps.groups[kGUnion];
     g.reset();
     g.mode = shape == 1 ? TQ_MODE_AND : TQ_MODE_OR;
     const uint32_t nq = shape == 0 ? 3000 : 400;
