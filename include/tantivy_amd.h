@@ -378,6 +378,36 @@ int tq_count_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
  * "exhaustive" = 1 that is the number of matches, which makes (Count, TopDocs) one pass). */
 int tq_last_batch_match_counts(tq_segment *seg, uint32_t *out, uint32_t n_queries);
 
+/* ---- doc sets ----
+ * replaces: Weight::for_each_no_score -> SegmentCollector::collect_block with the alive filter of
+ * default_collect_segment_impl (src/query/weight.rs:23-35,101-121, src/query/boolean_query/boolean_weight.rs:536-560,
+ * src/query/term_query/term_weight.rs:88-116, src/collector/mod.rs:186-221) — what DocSetCollector
+ * (src/collector/docset_collector.rs:26-57), FilterCollector, facets and aggregations ask a Weight for: for every
+ * query the ALIVE matching docs of this segment, ascending, back to back (CSR): query q owns
+ * out_docs[out_starts[q] .. out_starts[q+1]).  out_starts has n_queries + 1 entries and is always filled when the
+ * queries are valid; out_starts[n_queries] = total docs.  If that exceeds out_cap the call returns TQ_ERR_INVALID, has
+ * written no doc at or past out_cap (the host variant: no doc at all), and the caller retries with a buffer of
+ * out_starts[n_queries] entries (the protocol of tq_encode_postings' *out_len).  The top-k fields, weights and tf_cache
+ * of the queries are ignored (weights / tf_cache may be NULL).
+ * Query shapes: TQ_MODE_AND, TQ_MODE_OR and flat TQ_MODE_BOOL — occurs, clause_of unions, MustNot,
+ * min_should_match "at least m of n Should clauses" for any m (a clause = the OR of the lists that share a clause_of
+ * value and counts once; a clause without a list does not count toward n; m > n is the empty set) — with
+ * TQ_TERM_ABSENT terms.  Every list is read as bitmap words (8 bytes per list per 32 docs; a list without a bitmap is
+ * scattered into batch scratch first, see "docset_temp_lists"), twice: a count pass, a device prefix sum, a write pass.
+ * Not taken: TQ_MODE_PHRASE and nested queries (tq_query.nested_occurs / atom_of trees) — a batch that holds one fails
+ * as a whole with TQ_ERR_UNSUPPORTED, tq_last_error() names the index of the first such query, nothing is launched and
+ * the segment stays usable; malformed queries (mixed occurs in one clause, occur > 2, handle out of range, n_terms 0
+ * or > TQ_MAX_TERMS) return TQ_ERR_INVALID the same way.  Scores (Weight::for_each) are not produced.
+ * Afterwards tq_last_batch_match_counts gives the per-query sizes, tq_batch_stats.matches the total docs,
+ * kernel_mask = TQ_KERNEL_DOCSET and algorithmic_bytes = lists x bitmap words x 4 + 4 x docs. */
+int tq_docset_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                    uint32_t *out_docs, uint64_t out_cap, uint64_t *out_starts);
+/* Same with DEVICE outputs on the segment's device, enqueued on hip_stream (NULL = the segment's stream), no
+ * host synchronisation: docs whose position is >= out_cap are not written; d_out_starts[n_queries] tells the
+ * consumer the total.  Returns TQ_OK even when the total exceeds out_cap (only the device knows). */
+int tq_docset_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                           uint32_t *d_out_docs, uint64_t out_cap, uint64_t *d_out_starts, void *hip_stream);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -409,6 +439,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_BSHARE 0x400u       /* ashare_kernel, boolean leads (TQ_MODE_BOOL, leader-major) */
 #define TQ_KERNEL_COUNT_BITMAPS 0x800u /* count_bitmap_kernel (tq_count_batch over bitmap words) */
 #define TQ_KERNEL_TREE 0x1000u         /* tree_kernel (nested boolean queries over bitmap words) */
+#define TQ_KERNEL_DOCSET 0x2000u       /* docset_count / docset_write kernels (tq_docset_batch* over bitmap words) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -481,6 +512,10 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        expression over bitmap words (4-8 bytes per list per 32 docs, no postings decoded; a list
  *        without a bitmap is scattered into a scratch bitmap once per batch) when the clause a scan
  *        would walk holds at least max_doc / ratio postings per list of the query,
+ *        "docset_temp_lists" (default 0 = as many max_doc / 8-byte bitmaps as 1 GB — TQ_COUNT_TEMP_MB — holds, at most
+ *        4096; never below TQ_MAX_TERMS, so a single query always fits): tq_docset_batch* — how many lists without a
+ *        bitmap one launch scatters into batch scratch; a batch that names more of them runs as consecutive
+ *        sub-batches of whole queries (out_starts continues across them; the caller sees one call),
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

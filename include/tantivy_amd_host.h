@@ -92,6 +92,14 @@ int tqh_search_concurrent(tqh_searcher *s, const tqh_query *queries, uint32_t n,
 /* Searcher::search(&query, &Count) of the prepared batch (src/collector/count_collector.rs:39-80):
  * counts[q] = alive matching docs summed over the segments. */
 int tqh_count_prepared(tqh_searcher *s, uint64_t *counts);
+/* Searcher::search(&query, &DocSetCollector) of the prepared batch (src/collector/docset_collector.rs:26-57): query q
+ * owns the pairs (out_segment_ords[i], out_docs[i]), i in out_starts[q] .. out_starts[q+1], the alive matching docs of
+ * every segment (tq_docset_batch) ordered by (segment_ord, doc) — the DocAddresses merge_fruits unions.  out_starts has
+ * n + 1 entries and is filled whenever the queries are valid; if out_starts[n] exceeds out_cap the call fails, has
+ * written no pair, and the caller retries with buffers of out_starts[n] entries.  Flat queries only (tantivy_amd.h,
+ * "doc sets"): a phrase or a nested query fails the batch as unsupported. */
+int tqh_docset_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, uint64_t out_cap,
+                        uint64_t *out_starts);
 /* Collector::collect_segment of the prepared batch on one segment: [n][k] sorted. */
 int tqh_collect_segment_prepared(tqh_searcher *s, uint32_t segment_ord, uint32_t k, float *scores,
                                  uint32_t *docs, uint32_t *counts);

@@ -52,10 +52,11 @@ KERNEL_PHRASE_SWEEP, KERNEL_BOOL, KERNEL_USHARE, KERNEL_XUNION, KERNEL_ASHARE = 
 KERNEL_BSHARE = 0x400
 KERNEL_COUNT_BITMAPS = 0x800
 KERNEL_TREE = 0x1000
+KERNEL_DOCSET = 0x2000
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
-                0x1000: "tree"}
+                0x1000: "tree", 0x2000: "docset"}
 
 
 def kernel_names(mask):
@@ -108,6 +109,7 @@ EXPORTS = [
     "tqh_term_info_store_open", "tqh_term_info_store_free", "tqh_term_info_store_num_terms",
     "tqh_term_info_store_get", "tqh_term_info_store_write", "tqh_searcher_add_segment_with_store",
     "tqh_count_prepared", "tqh_searcher_add_segment_device_with_store",
+    "tq_docset_batch", "tq_docset_batch_device", "tqh_docset_prepared",
 ]
 
 
@@ -154,6 +156,9 @@ def lib():
     L.tq_segment_set_alive_bitset.argtypes = [vp, vp, C.c_size_t]
     L.tq_count_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p]
     L.tq_last_batch_match_counts.argtypes = [vp, u32p, C.c_uint32]
+    L.tq_docset_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.tq_docset_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.tqh_docset_prepared.argtypes = [vp, u32p, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_last_batch_query_kernels.argtypes = [vp, u32p, C.c_uint32]
     u64p = C.POINTER(C.c_uint64)
     L.tq_encoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
@@ -645,6 +650,24 @@ class DeviceIndex:
         _check(lib().tqh_count_prepared(self._s, out.ctypes.data_as(C.POINTER(C.c_uint64))), host=True)
         return out[: len(queries)]
 
+    def docset(self, queries):
+        """Searcher::search(&query, &DocSetCollector) for a batch: per query an (n, 2) uint32 array of
+        (segment_ord, doc) rows — the alive matching docs of every segment, ordered by (segment_ord, doc)."""
+        self.prepare(queries)
+        n = len(queries)
+        starts = np.zeros(n + 1, np.uint64)
+        ords = np.zeros(1, np.uint32)
+        docs = np.zeros(1, np.uint32)
+        u64p = C.POINTER(C.c_uint64)
+        rc = lib().tqh_docset_prepared(self._s, _u32(ords), _u32(docs), 0, starts.ctypes.data_as(u64p))
+        if rc != 0 and int(starts[n]) > 0:  # too small: the call reported the size
+            ords = np.zeros(int(starts[n]), np.uint32)
+            docs = np.zeros(int(starts[n]), np.uint32)
+            rc = lib().tqh_docset_prepared(self._s, _u32(ords), _u32(docs), docs.size, starts.ctypes.data_as(u64p))
+        _check(rc, host=True)
+        pairs = np.stack([ords, docs], axis=1)
+        return [pairs[int(starts[q]): int(starts[q + 1])] for q in range(n)]
+
     # ---- raw C ABI access (parity tests)
     def segment_raw(self, segment_ord=0):
         return C.c_void_p(lib().tqh_segment_raw(self._s, segment_ord))
@@ -713,6 +736,62 @@ class DeviceIndex:
         out["tantivy_bytes"] = (out["index_bytes"] + out["positions_bytes"] + out["fieldnorm_bytes"]
                                 + out["alive_bytes"])
         return out
+
+    def _raw_flat_queries(self, queries, segment_ord):
+        """tq_query structs without scoring fields from the tuples _host_queries takes: (mode, [term ids]),
+        (MODE_PHRASE, [term ids], [offsets]) or (MODE_BOOL, [term ids], [occurs][, clause_of | None[, min_should_match]])
+        with an optional trailing dict {"nested_occurs": [...]}.  -> (array, keep-alive list)"""
+        n = len(queries)
+        qs = (TqQuery * max(1, n))()
+        keep = []
+        for i, q in enumerate(queries):
+            extra = q[-1] if isinstance(q[-1], dict) else None
+            if extra is not None:
+                q = q[:-1]
+            mode, terms = q[0], q[1]
+            hs = (C.c_uint32 * max(1, len(terms)))(*[self.term_handle(t, segment_ord) for t in terms])
+            keep.append(hs)
+            qs[i].n_terms = len(terms)
+            qs[i].terms = C.cast(hs, C.POINTER(C.c_uint32))
+            qs[i].mode = mode
+            qs[i].k = 1
+            if mode == MODE_BOOL:
+                oc = (C.c_uint8 * len(terms))(*[int(o) for o in q[2]])
+                keep.append(oc)
+                qs[i].occurs = C.cast(oc, C.POINTER(C.c_uint8))
+                if len(q) > 3 and q[3] is not None:
+                    co = (C.c_uint8 * len(terms))(*[int(o) for o in q[3]])
+                    keep.append(co)
+                    qs[i].clause_of = C.cast(co, C.POINTER(C.c_uint8))
+                if len(q) > 4:
+                    qs[i].min_should_match = int(q[4])
+                if extra and extra.get("nested_occurs") is not None:
+                    na = (C.c_uint8 * len(terms))(*[int(o) for o in extra["nested_occurs"]])
+                    keep.append(na)
+                    qs[i].nested_occurs = C.cast(na, C.POINTER(C.c_uint8))
+            elif mode == MODE_PHRASE:
+                oa = (C.c_uint32 * len(terms))(*(q[2] if len(q) > 2 and q[2] is not None else range(len(terms))))
+                keep.append(oa)
+                qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
+        return qs, keep
+
+    def raw_docset(self, queries, cap, segment_ord=0, guard=0, fill=0xDEADBEEF):
+        """Direct tq_docset_batch on one segment with a buffer of `cap` docs -> (rc, docs, starts).  docs has cap + guard
+        entries preset to `fill` (the call may write the first cap only); starts has len(queries) + 1 entries."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        docs = np.full(max(1, cap + guard), fill, np.uint32)
+        starts = np.zeros(n + 1, np.uint64)
+        rc = lib().tq_docset_batch(self.segment_raw(segment_ord), qs, n, _u32(docs), int(cap),
+                                   starts.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return rc, docs[: cap + guard], starts
+
+    def raw_docset_device(self, queries, d_docs, cap, d_starts, segment_ord=0, stream=None):
+        """Direct tq_docset_batch_device: d_docs (int32 / uint32, at least cap entries) and d_starts (int64 / uint64,
+        len(queries) + 1 entries) are torch tensors on the segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        return lib().tq_docset_batch_device(self.segment_raw(segment_ord), qs, len(queries), d_docs.data_ptr(), int(cap),
+                                            d_starts.data_ptr(), C.c_void_p(stream) if stream else None)
 
     def raw_count(self, queries, weights, cache, segment_ord=0):
         """Direct tq_count_batch (Count collector): alive matches per query."""

@@ -224,6 +224,13 @@ void tq_segment_free(tq_segment *s) {
   s->d_count_out.release();
   s->d_count_bits.release();
   s->d_count_wgs.release();
+  s->d_docset_queries.release();
+  s->d_docset_counts.release();
+  s->d_docset_offs.release();
+  s->d_docset_partials.release();
+  s->d_docset_starts.release();
+  s->d_docset_docs.release();
+  s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
   if (s->side_stream) (void)hipStreamSynchronize(s->side_stream);
@@ -304,6 +311,22 @@ int tq_count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries,
   return count_batch(s, queries, n_queries, out_counts);
 }
 
+int tq_docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
+                    uint64_t *out_starts) {
+  if (!s || (!queries && n_queries) || (!out_docs && out_cap) || !out_starts)
+    return fail(TQ_ERR_INVALID, "tq_docset_batch: null argument");
+  TQ_SEGMENT_LOCK(s);
+  return docset_batch(s, queries, n_queries, out_docs, out_cap, out_starts, false, nullptr);
+}
+
+int tq_docset_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *d_out_docs,
+                           uint64_t out_cap, uint64_t *d_out_starts, void *hip_stream) {
+  if (!s || (!queries && n_queries) || (!d_out_docs && out_cap) || !d_out_starts)
+    return fail(TQ_ERR_INVALID, "tq_docset_batch_device: null argument");
+  TQ_SEGMENT_LOCK(s);
+  return docset_batch(s, queries, n_queries, d_out_docs, out_cap, d_out_starts, true, hip_stream);
+}
+
 int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
   if (!s || !out) return fail(TQ_ERR_INVALID, "tq_last_batch_stats: null argument");
   TQ_SEGMENT_LOCK(s);
@@ -316,7 +339,7 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
     unsigned long long m = 0;
     HIP_TRY(hipMemcpy(&m, s->d_match_counter, sizeof m, hipMemcpyDeviceToHost));
     s->stats.matches = m;
-    s->stats.algorithmic_bytes += m;  // 1 fieldnorm byte per scored doc
+    s->stats.algorithmic_bytes += m * s->stats_match_bytes;  // 1 fieldnorm byte per scored doc; 4 per doc of a doc set
     if (s->opt.timing) {
       uint64_t first = s->batches_reported;
       if (s->batches_timed - first > (uint64_t)tq_segment::kTimingRing)
@@ -374,7 +397,7 @@ int tq_segment_get_stats(tq_segment *s, tq_segment_stats *out) {
   r.posdir_bytes = s->bytes_posdir;
   r.scratch_bytes = s->d_stage.cap + s->d_stage_alt.cap + s->d_misc.cap + s->d_thr.cap + s->d_qmatches.cap + s->d_share_words.cap +
                     s->d_ashare_words.cap + s->d_bshare_words.cap + s->d_count_queries.cap + s->d_count_out.cap +
-                    s->d_count_bits.cap + s->d_count_wgs.cap;
+                    s->d_count_bits.cap + s->d_count_wgs.cap + s->docset_scratch_bytes();
   {
     std::lock_guard<std::mutex> lk(s->dscratch->m);
     r.device_scratch_bytes = s->dscratch->partials.cap + s->dscratch->share_stage.cap + s->dscratch->ashare_stage.cap +
@@ -424,6 +447,8 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.xunion_ratio = (int)value;
   else if (!strcmp(name, "count_bitmap_ratio") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.count_bitmap_ratio = (int)value;
+  else if (!strcmp(name, "docset_temp_lists") && value >= 0 && value <= 0x7FFFFFFF)
+    s->opt.docset_temp_lists = (int)value;
   else if (!strcmp(name, "ashare_min_batch") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.ashare_min_batch = (int)value;
   else if (!strcmp(name, "xunion_min_queries") && value >= 1 && value <= 0x7FFFFFFF)

@@ -7,6 +7,57 @@
 
 namespace tqi {
 
+// The clauses of a flat query (AND, OR, or TQ_MODE_BOOL over terms and unions of terms): what count_expression and
+// docset_expression (tq_docset.cpp) both start from.  FLAT_UNSUPPORTED: a phrase or a nested query; FLAT_INVALID:
+// malformed input (*why says what).
+int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why) {
+  fc.n_cl = fc.n_must = fc.n_should = 0;
+  fc.empty = false;
+  *why = "";
+  if (!q.terms || q.n_terms == 0 || q.n_terms > TQ_MAX_TERMS) return *why = "n_terms out of range (1..TQ_MAX_TERMS) or no terms", FLAT_INVALID;
+  if (q.mode == TQ_MODE_PHRASE) return *why = "a phrase query", FLAT_UNSUPPORTED;
+  if (q.mode > TQ_MODE_BOOL) return *why = "unknown mode", FLAT_INVALID;
+  if (q.mode == TQ_MODE_BOOL && !q.occurs) return *why = "TQ_MODE_BOOL without occurs", FLAT_INVALID;
+  if (bool_query_is_tree(q)) return *why = "a nested boolean query", FLAT_UNSUPPORTED;
+  FlatClauses::Clause *cl = fc.cl;
+  uint32_t n_cl = 0;
+  for (uint32_t i = 0; i < q.n_terms; ++i) {
+    uint32_t occur = q.mode == TQ_MODE_AND ? TQ_MUST : TQ_SHOULD;
+    uint32_t id = i;
+    if (q.mode == TQ_MODE_BOOL) {
+      occur = q.occurs[i];
+      if (occur > TQ_MUST_NOT) return *why = "occur out of range", FLAT_INVALID;
+      if (q.clause_of) id = q.clause_of[i];
+    }
+    uint32_t c = 0;
+    while (c < n_cl && cl[c].id != id) ++c;
+    if (c == n_cl) {
+      cl[n_cl] = FlatClauses::Clause{};
+      cl[n_cl].id = id;
+      cl[n_cl].occur = occur;
+      ++n_cl;
+    } else if (cl[c].occur != occur) {
+      return *why = "mixed occurs in one clause", FLAT_INVALID;
+    }
+    const uint32_t h = q.terms[i];
+    if (h == TQ_TERM_ABSENT) continue;
+    if (h >= s->terms.size()) return *why = "term handle out of range", FLAT_INVALID;
+    cl[c].terms[cl[c].n++] = h;
+    cl[c].cost += s->terms[h].doc_freq;
+  }
+  fc.n_cl = n_cl;
+  // BooleanWeight::complex_scorer (boolean_weight.rs:236-431), as plan_bool_query restates it
+  for (uint32_t c = 0; c < n_cl; ++c) {
+    if (cl[c].occur == TQ_MUST) {
+      if (cl[c].n == 0) fc.empty = true;
+      ++fc.n_must;
+    } else if (cl[c].n) {
+      if (cl[c].occur == TQ_SHOULD) ++fc.n_should;
+    }
+  }
+  return FLAT_OK;
+}
+
 // The query as a bitwise expression, or false if it has to be scanned (a phrase, a list without a bitmap,
 // minimum_number_should_match >= 2 over fewer Should clauses than that, malformed input — the scan reports it).
 // `known` = the count is known without looking (an absent Must term, MustNot clauses only, ...): 0 matches.
@@ -15,54 +66,20 @@ bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool 
   known = false;
   driver_postings = 0;
   cq = TqkCountQuery{};
-  if (!q.terms || q.n_terms == 0 || q.n_terms > TQ_MAX_TERMS || q.mode == TQ_MODE_PHRASE || q.mode > TQ_MODE_BOOL) return false;
-  if (q.mode == TQ_MODE_BOOL && !q.occurs) return false;
-  if (bool_query_is_tree(q)) return false;  // (nested queries: the scan — tq_tree.hip — counts them from bitmap words itself)
-  struct Clause {
-    uint32_t id, occur, n = 0, terms[TQ_MAX_TERMS];
-    uint64_t cost = 0;
-  };
-  Clause cl[TQ_MAX_TERMS];
-  uint32_t n_cl = 0;
-  for (uint32_t i = 0; i < q.n_terms; ++i) {
-    uint32_t occur = q.mode == TQ_MODE_AND ? TQ_MUST : TQ_SHOULD;
-    uint32_t id = i;
-    if (q.mode == TQ_MODE_BOOL) {
-      occur = q.occurs[i];
-      if (occur > TQ_MUST_NOT) return false;
-      if (q.clause_of) id = q.clause_of[i];
+  FlatClauses fc;
+  const char *why;
+  if (parse_flat_clauses(s, q, fc, &why) != FLAT_OK) return false;
+  using Clause = FlatClauses::Clause;
+  const Clause *cl = fc.cl;
+  const uint32_t n_cl = fc.n_cl, n_must = fc.n_must, n_should = fc.n_should;
+  bool empty = fc.empty;
+  // a list without a bitmap gets one for the duration of the batch (count_scatter_kernel), while the
+  // batch's scratch has room for another
+  for (uint32_t c = 0; c < n_cl; ++c)
+    for (uint32_t i = 0; i < cl[c].n; ++i) {
+      const uint32_t h = cl[c].terms[i];
+      if (!(s->terms[h].dense_blob && s->opt.use_dense) && !temp_slot.count(h) && temp_slot.size() >= max_temp) return false;
     }
-    uint32_t c = 0;
-    while (c < n_cl && cl[c].id != id) ++c;
-    if (c == n_cl) {
-      cl[n_cl].id = id;
-      cl[n_cl].occur = occur;
-      ++n_cl;
-    } else if (cl[c].occur != occur) {
-      return false;  // (mixed occurs in one clause: the scan reports it)
-    }
-    const uint32_t h = q.terms[i];
-    if (h == TQ_TERM_ABSENT) continue;
-    if (h >= s->terms.size()) return false;
-    if (!(s->terms[h].dense_blob && s->opt.use_dense)) {
-      // a list without a bitmap gets one for the duration of the batch (count_scatter_kernel), while the
-      // batch's scratch has room for another
-      if (!temp_slot.count(h) && temp_slot.size() >= max_temp) return false;
-    }
-    cl[c].terms[cl[c].n++] = h;
-    cl[c].cost += s->terms[h].doc_freq;
-  }
-  // BooleanWeight::complex_scorer (boolean_weight.rs:236-431), as plan_bool_query restates it
-  uint32_t n_must = 0, n_should = 0;
-  bool empty = false;
-  for (uint32_t c = 0; c < n_cl; ++c) {
-    if (cl[c].occur == TQ_MUST) {
-      if (cl[c].n == 0) empty = true;
-      ++n_must;
-    } else if (cl[c].n) {
-      if (cl[c].occur == TQ_SHOULD) ++n_should;
-    }
-  }
   uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
   if (msm > n_should) empty = true;
   bool should_is_must = false;

@@ -1,0 +1,265 @@
+// tq_docset_batch / tq_docset_batch_device: the full doc set of every query of a batch (Weight::for_each_no_score ->
+// SegmentCollector::collect_block with the alive filter, src/query/weight.rs:23-35,101-121, src/collector/mod.rs:186-221)
+// as CSR rows of ascending doc ids.  Every list is reached through bitmap words: its own bitmap, or — a list without
+// one — bits scattered into the batch's scratch (count_scatter_kernel); tq_docset.hip counts, scans and writes.
+#include "tq_internal.hpp"
+
+#include <unordered_map>
+
+namespace tqi {
+
+int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why) {
+  dq = TqkDocsetQuery{};
+  FlatClauses fc;
+  const int prc = parse_flat_clauses(s, q, fc, why);
+  if (prc != FLAT_OK) return prc;
+  using Clause = FlatClauses::Clause;
+  // BooleanWeight::complex_scorer (boolean_weight.rs:236-431), as count_expression restates it
+  uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
+  if (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0)) {
+    dq.min_should = 1;  // no lists, one Should clause wanted: the empty set
+    return FLAT_OK;
+  }
+  const bool should_is_must = msm >= 2 && msm == fc.n_should;  // all of them: Must clauses
+  if (should_is_must) msm = 0;
+  const bool has_must = fc.n_must > 0 || should_is_must;
+  uint32_t n = 0;
+  auto put = [&](const Clause &c, uint32_t kind) {
+    for (uint32_t i = 0; i < c.n; ++i) {
+      const TermHost &th = s->terms[c.terms[i]];
+      if (th.dense_blob && s->opt.use_dense) {
+        dq.dense[n] = (const uint2 *)th.dense_blob;
+      } else {  // (the handle for now; the pointer once the sub-batch's scratch slot is known)
+        dq.dense[n] = (const uint2 *)(uintptr_t)c.terms[i];
+        dq.narrow |= 1u << n;
+      }
+      dq.kinds |= kind << (2u * n);
+      if (i + 1 == c.n) {
+        if (kind == TQK_COUNT_MUST) dq.clause_end |= 1u << n;
+        if (kind == TQK_COUNT_SHOULD) dq.should_end |= 1u << n;
+      }
+      ++n;
+    }
+  };
+  for (uint32_t c = 0; c < fc.n_cl; ++c)
+    if (fc.cl[c].occur == TQ_MUST || (should_is_must && fc.cl[c].occur == TQ_SHOULD && fc.cl[c].n)) put(fc.cl[c], TQK_COUNT_MUST);
+  for (uint32_t c = 0; c < fc.n_cl; ++c)
+    if (fc.cl[c].occur == TQ_MUST_NOT && fc.cl[c].n) put(fc.cl[c], TQK_COUNT_NOT);
+  // with Must clauses and no minimum the Should lists do not change the doc set
+  if (!should_is_must && !(has_must && msm == 0))
+    for (uint32_t c = 0; c < fc.n_cl; ++c)
+      if (fc.cl[c].occur == TQ_SHOULD && fc.cl[c].n) put(fc.cl[c], TQK_COUNT_SHOULD);
+  dq.n_terms = n;
+  dq.min_should = has_must ? msm : std::max(msm, 1u);  // (msm >= 2 here: fewer than the n_should <= 16 clauses, so <= 15)
+  return FLAT_OK;
+}
+
+namespace {
+
+struct SubBatch {  // consecutive whole queries whose lists without a bitmap fit the scratch together
+  uint32_t q0 = 0, q1 = 0;
+  size_t wg0 = 0, wg1 = 0;  // its part of the scatter work list
+  uint32_t n_temp = 0;
+};
+enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
+
+}  // namespace
+
+int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
+                 uint64_t *out_starts, bool device_out, void *hip_stream) {
+  const char *const fn = device_out ? "tq_docset_batch_device" : "tq_docset_batch";
+  // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
+  static const uint32_t kStageMin = tune_u32("TQ_DOCSET_STAGE_MIN", 2048);
+  static const uint64_t kTempBudget = (uint64_t)std::max<uint32_t>(1u, tune_u32("TQ_COUNT_TEMP_MB", 1024)) << 20;
+  const uint32_t n_words = (uint32_t)(((uint64_t)s->max_doc + 31u) / 32u);
+  const uint32_t words_per_list = (n_words + 63u) & ~63u;
+  const uint32_t n_tiles = (n_words + tqk_docset_tile_words() - 1u) / tqk_docset_tile_words();
+  uint32_t max_temp = s->opt.docset_temp_lists > 0
+                          ? (uint32_t)s->opt.docset_temp_lists
+                          : (uint32_t)std::min<uint64_t>(4096u, kTempBudget / std::max<uint64_t>(1u, (uint64_t)words_per_list * 4u));
+  max_temp = std::max<uint32_t>(max_temp, TQ_MAX_TERMS);  // a single query always fits
+  const uint32_t max_sub_queries = std::max<uint32_t>(1u, (1u << 26) / std::max(1u, n_tiles));  // (query, tile) entries per launch
+
+  // every query is checked before anything is launched: a batch fails as a whole
+  std::vector<TqkDocsetQuery> dqs(n_queries);
+  uint64_t algo_bytes = 0;
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    const char *why = "";
+    const int rc = docset_expression(s, queries[qi], dqs[qi], &why);
+    if (rc == FLAT_UNSUPPORTED)
+      return fail(TQ_ERR_UNSUPPORTED, "%s: query %u is %s: doc sets of phrases and nested queries stay on the CPU", fn, qi, why);
+    if (rc != FLAT_OK) return fail(TQ_ERR_INVALID, "%s: query %u: %s", fn, qi, why);
+    algo_bytes += (uint64_t)dqs[qi].n_terms * n_words * 4u;
+  }
+  // sub-batches; a list without a bitmap gets a slot of the scratch for the duration of its sub-batch
+  std::vector<SubBatch> subs;
+  std::vector<uint4> wgs;
+  std::unordered_map<uint32_t, uint32_t> slot;
+  SubBatch cur;
+  uint32_t max_sub_temp = 0, max_sub_n = 0;
+  auto close_sub = [&](uint32_t q1) {
+    cur.q1 = q1;
+    cur.wg1 = wgs.size();
+    cur.n_temp = (uint32_t)slot.size();
+    max_sub_temp = std::max(max_sub_temp, cur.n_temp);
+    max_sub_n = std::max(max_sub_n, cur.q1 - cur.q0);
+    subs.push_back(cur);
+    cur = SubBatch{};
+    cur.q0 = q1;
+    cur.wg0 = wgs.size();
+    slot.clear();
+  };
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    TqkDocsetQuery &dq = dqs[qi];
+    uint32_t fresh[TQ_MAX_TERMS], n_fresh = 0;
+    for (uint32_t m = 0; m < dq.n_terms; ++m) {
+      if (!((dq.narrow >> m) & 1u)) continue;
+      const uint32_t h = (uint32_t)(uintptr_t)dq.dense[m];
+      if (slot.count(h) || std::find(fresh, fresh + n_fresh, h) != fresh + n_fresh) continue;
+      fresh[n_fresh++] = h;
+    }
+    if (qi > cur.q0 && (slot.size() + n_fresh > max_temp || qi - cur.q0 >= max_sub_queries)) close_sub(qi);
+    for (uint32_t m = 0; m < dq.n_terms; ++m) {
+      if (!((dq.narrow >> m) & 1u)) continue;
+      const uint32_t h = (uint32_t)(uintptr_t)dq.dense[m];
+      auto it = slot.find(h);
+      if (it == slot.end()) {
+        it = slot.emplace(h, (uint32_t)slot.size()).first;
+        for (uint32_t j = 0; j < s->terms[h].n_blocks; j += 4u) wgs.push_back(make_uint4(h, j, it->second, 0u));
+      }
+      dq.dense[m] = (const uint2 *)(uintptr_t)it->second;  // (the slot; the pointer below)
+    }
+  }
+  if (n_queries) close_sub(n_queries);
+
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = device_out && hip_stream ? (hipStream_t)hip_stream : s->stream;
+  {
+    const int wrc = wait_segment_idle(s);  // the scratch below is shared with the batches before
+    if (wrc != TQ_OK) return wrc;
+  }
+  s->stats = tq_batch_stats{};
+  s->stats.kernel_mask = TQ_KERNEL_DOCSET;
+  s->stats.algorithmic_bytes = algo_bytes;
+  s->stats_pending = false;
+  s->last_batch_queries = 0;
+  if (n_queries == 0 || n_tiles == 0) {  // no query, or a segment without docs: empty rows
+    if (device_out) {
+      HIP_TRY(hipMemsetAsync(out_starts, 0, ((size_t)n_queries + 1u) * sizeof(uint64_t), st));
+    } else {
+      memset(out_starts, 0, ((size_t)n_queries + 1u) * sizeof(uint64_t));
+    }
+    return TQ_OK;
+  }
+  if (!wgs.empty()) {
+    const int src = sync_terms(s, s->stream);
+    if (src != TQ_OK) return src;
+  }
+  const size_t q_bytes = (size_t)n_queries * sizeof(TqkDocsetQuery), wg_bytes = wgs.size() * sizeof(uint4);
+  const size_t max_entries = (size_t)max_sub_n * n_tiles;
+  int rc = s->h_docset.ensure(q_bytes + wg_bytes);
+  if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
+  if (rc == TQ_OK) rc = s->d_count_wgs.ensure(wg_bytes);
+  if (rc == TQ_OK) rc = s->d_count_bits.ensure((size_t)max_sub_temp * words_per_list * sizeof(uint32_t));
+  if (rc == TQ_OK) rc = s->d_docset_counts.ensure(max_entries * sizeof(uint32_t));
+  if (rc == TQ_OK) rc = s->d_docset_offs.ensure(max_entries * sizeof(uint64_t));
+  if (rc == TQ_OK) rc = s->d_docset_partials.ensure(((max_entries + tqk_docset_scan_tile() - 1) / tqk_docset_scan_tile()) * sizeof(uint64_t));
+  if (rc == TQ_OK) rc = s->d_qmatches.ensure((size_t)n_queries * sizeof(uint32_t));
+  if (rc == TQ_OK && !device_out) rc = s->d_docset_starts.ensure(((size_t)n_queries + 1u) * sizeof(uint64_t));
+  if (rc != TQ_OK) return rc;
+  for (TqkDocsetQuery &dq : dqs)
+    for (uint32_t m = 0; m < dq.n_terms; ++m)
+      if ((dq.narrow >> m) & 1u)
+        dq.dense[m] = (const uint2 *)((const uint32_t *)s->d_count_bits.p + (size_t)(uintptr_t)dq.dense[m] * words_per_list);
+  // option "timing" (device variant): the batch takes a slot of the event ring like a search batch
+  const bool timed = device_out && s->opt.timing;
+  const int ring = (int)(s->batches_timed % tq_segment::kTimingRing);
+  if (timed) HIP_TRY(hipEventRecord(s->ev_t0[ring], st));
+  memcpy(s->h_docset.p, dqs.data(), q_bytes);
+  if (wg_bytes) memcpy((uint8_t *)s->h_docset.p + q_bytes, wgs.data(), wg_bytes);
+  HIP_TRY(hipMemcpyAsync(s->d_docset_queries.p, s->h_docset.p, q_bytes, hipMemcpyHostToDevice, st));
+  if (wg_bytes)
+    HIP_TRY(hipMemcpyAsync(s->d_count_wgs.p, (const uint8_t *)s->h_docset.p + q_bytes, wg_bytes, hipMemcpyHostToDevice, st));
+
+  uint64_t *const d_starts = device_out ? out_starts : (uint64_t *)s->d_docset_starts.p;
+  auto enqueue = [&](const SubBatch &sb, uint32_t stages, uint32_t *d_docs, uint64_t cap) -> int {
+    if ((stages & DS_SCATTER) && sb.n_temp) {  // the sub-batch's lists without a bitmap, as bits
+      HIP_TRY(hipMemsetAsync(s->d_count_bits.p, 0, (size_t)sb.n_temp * words_per_list * sizeof(uint32_t), st));
+      const hipError_t se = tqk_launch_count_scatter(s->dseg, s->d_terms, (const uint4 *)s->d_count_wgs.p + sb.wg0,
+                                                     (uint32_t)(sb.wg1 - sb.wg0), (uint32_t *)s->d_count_bits.p, words_per_list, st);
+      if (se != hipSuccess) return fail(TQ_ERR_HIP, "doc-set scatter launch: %s", hipGetErrorString(se));
+    }
+    TqkDocsetParams p{};
+    p.queries = (const TqkDocsetQuery *)s->d_docset_queries.p + sb.q0;
+    p.alive = s->d_alive;
+    p.tile_counts = (uint32_t *)s->d_docset_counts.p;
+    p.tile_offs = (uint64_t *)s->d_docset_offs.p;
+    p.partials = (uint64_t *)s->d_docset_partials.p;
+    p.base_in = sb.q0 ? d_starts + sb.q0 : nullptr;  // (the total the sub-batch before left there)
+    p.out_starts = d_starts + sb.q0;
+    p.query_sizes = (uint32_t *)s->d_qmatches.p + sb.q0;
+    p.total_out = s->d_match_counter;
+    p.out_docs = d_docs;
+    p.out_cap = cap;
+    p.n_queries = sb.q1 - sb.q0;
+    p.n_tiles = n_tiles;
+    p.n_words = n_words;
+    p.max_doc = s->max_doc;
+    p.stage_min_docs = kStageMin;
+    hipError_t e = hipSuccess;
+    if (stages & DS_COUNT) {
+      e = tqk_launch_docset_count(p, st);
+      if (e == hipSuccess) e = tqk_launch_docset_scan(p, st);
+    }
+    if (e == hipSuccess && (stages & DS_WRITE)) e = tqk_launch_docset_write(p, st);
+    if (e != hipSuccess) return fail(TQ_ERR_HIP, "doc-set kernel launch: %s", hipGetErrorString(e));
+    return TQ_OK;
+  };
+
+  s->last_batch_queries = n_queries;
+  if (device_out) {
+    if (timed) HIP_TRY(hipEventRecord(s->ev_k0[ring], st));
+    for (const SubBatch &sb : subs) {
+      rc = enqueue(sb, DS_SCATTER | DS_COUNT | DS_WRITE, out_docs, out_cap);
+      if (rc != TQ_OK) return rc;
+    }
+    if (timed) {
+      HIP_TRY(hipEventRecord(s->ev_k1[ring], st));
+      HIP_TRY(hipEventRecord(s->ev_t1[ring], st));
+      ++s->batches_timed;
+    }
+    s->stats_pending = true;  // the total is on the device: tq_last_batch_stats reads it
+    s->stats_match_bytes = 4;
+    HIP_TRY(hipEventRecord(s->ev_batch_done, st));
+    s->last_stream = st;
+    s->batch_in_flight = true;
+    return TQ_OK;
+  }
+  // host outputs: the row starts first — they say whether the docs fit
+  for (const SubBatch &sb : subs) {
+    rc = enqueue(sb, DS_SCATTER | DS_COUNT, nullptr, 0);
+    if (rc != TQ_OK) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out_starts, d_starts, ((size_t)n_queries + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t total = out_starts[n_queries];
+  s->stats.matches = total;
+  s->stats.algorithmic_bytes += 4u * total;
+  if (total > out_cap)
+    return fail(TQ_ERR_INVALID, "%s: the batch has %llu docs, out_cap is %llu (out_starts is filled: retry with that many)", fn,
+                (unsigned long long)total, (unsigned long long)out_cap);
+  if (!total) return TQ_OK;
+  rc = s->d_docset_docs.ensure((size_t)total * sizeof(uint32_t));
+  if (rc != TQ_OK) return rc;
+  for (const SubBatch &sb : subs) {
+    // one sub-batch: its tables and bits are still there; several: each is evaluated again (the scratch held the last one's)
+    rc = enqueue(sb, subs.size() == 1 ? DS_WRITE : (DS_SCATTER | DS_COUNT | DS_WRITE), (uint32_t *)s->d_docset_docs.p, total);
+    if (rc != TQ_OK) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(out_docs, s->d_docset_docs.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (s->d_docset_docs.cap > ((size_t)256 << 20)) s->d_docset_docs.release();  // (a large result is not kept as scratch)
+  return TQ_OK;
+}
+
+}  // namespace tqi

@@ -186,6 +186,7 @@ struct Options {
   int rdir_budget_x = 4;    // range directories of the lists below "dense_ratio" (6-8 B per posting): at most this multiple of the segment
   int probe_budget_x = 16;  // bitmaps + tf bytes built on demand for the lists boolean queries probe: at most this multiple of the segment
   int count_bitmap_ratio = 128;  // Count: bitmap words instead of a scan if the driving clause holds >= max_doc / ratio postings per list
+  int docset_temp_lists = 0;     // doc sets: lists without a bitmap scattered per launch (0 = what TQ_COUNT_TEMP_MB holds, at most 4096)
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
   // tq_submit / tq_search_one: how long the leader of a batch waits for the callers of the previous
   // batch to come back with their next query (0 = launch with whatever is pending)
@@ -298,6 +299,13 @@ struct tq_segment {
   DevBuf d_stage, d_misc, d_thr, d_qmatches;
   DevBuf d_share_words;   // shared-union launch: per-query words
   DevBuf d_count_queries, d_count_out, d_count_bits, d_count_wgs;  // Count collector over bitmaps (tq_count.hip)
+  // full doc sets (tq_docset.hip): descriptors, the (query, tile) tables of the scan, and the host variant's outputs
+  DevBuf d_docset_queries, d_docset_counts, d_docset_offs, d_docset_partials, d_docset_starts, d_docset_docs;
+  PinnedBuf h_docset;  // descriptors + scatter work list on their way up
+  size_t docset_scratch_bytes() const {
+    return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
+           d_docset_docs.cap;
+  }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
   // the shared-union launch addresses bitmaps / byte-wide tfs as 32-bit offsets (8-byte units) from
@@ -376,6 +384,8 @@ struct tq_segment {
   bool device_prepare() const { return h_idx.empty() || opt.device_prepare != 0; }
   tq_batch_stats stats{};
   bool stats_pending = false;
+  uint32_t stats_match_bytes = 1;  // what a match adds to algorithmic_bytes once d_match_counter is read: a fieldnorm
+                                   // byte per scored doc, 4 bytes per doc of a doc-set batch on the device
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -762,6 +772,24 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
 // a query as a bitwise expression over bitmap words (tq_count.cpp; checked on the CPU by tools/planbench/plan_check.cpp)
 bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool &known, uint64_t &driver_postings,
                       std::unordered_map<uint32_t, uint32_t> &temp_slot, uint32_t max_temp);
+// the clauses of a flat query: what count_expression and docset_expression start from
+struct FlatClauses {
+  struct Clause {
+    uint32_t id, occur, n = 0, terms[TQ_MAX_TERMS];
+    uint64_t cost = 0;
+  };
+  Clause cl[TQ_MAX_TERMS];
+  uint32_t n_cl = 0, n_must = 0, n_should = 0;  // (n_should: the Should clauses that hold a list)
+  bool empty = false;                           // a Must clause without a list: no doc matches
+};
+enum { FLAT_OK = 0, FLAT_UNSUPPORTED, FLAT_INVALID };
+int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why);
+// ---- tq_docset.cpp: full doc sets (tq_docset_batch / tq_docset_batch_device)
+// the query as a TqkDocsetQuery: FLAT_*; lists without a bitmap are left as their term HANDLE in dq.dense (narrow bit set)
+int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why);
+// out_docs / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on hip_stream
+int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
+                 uint64_t *out_starts, bool device_out, void *hip_stream);
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);

@@ -271,6 +271,38 @@ hipError_t tqk_launch_count_bitmaps(const TqkCountParams &p, hipStream_t st);
 hipError_t tqk_launch_count_scatter(const TqdSegment &seg, const TqdTerm *terms, const uint4 *wgs, uint32_t n_wgs,
                                     uint32_t *bits, uint32_t words_per_list, hipStream_t st);
 uint32_t tqk_count_tile_words();
+// ---- full doc sets over bitmaps (tq_docset.hip): the expression of TqkCountQuery with the result bits kept
+struct TqkDocsetQuery {           // 152 bytes
+  uint32_t n_terms;               // lists: Must clauses first (a clause = a union of lists), then MustNot, then Should
+  uint32_t kinds;                 // 2 bits per list: TQK_COUNT_*
+  uint32_t clause_end;            // bit m: list m is the last of its Must clause
+  uint32_t should_end;            // bit m: list m is the last of its Should clause (a clause counts once)
+  uint32_t narrow;                // bit m: list m's bitmap is a plain array of 32-bit words (the batch's scratch)
+  uint32_t min_should;            // 0: the Must clauses alone; m >= 1: ... and at least m of the Should clauses (m <= 15);
+                                  // a query without Must clauses is the union of its Should clauses: 1.
+                                  // The empty doc set: no lists and min_should = 1
+  const uint2 *dense[TQD_MAX_TERMS];  // the lists' bitmaps: {32 doc bits, postings before the word}
+};
+struct TqkDocsetParams {
+  const TqkDocsetQuery *queries;  // [n_queries] (one sub-batch)
+  const uint8_t *alive;           // AliveBitSet bits or null
+  uint32_t *tile_counts;          // [n_queries][n_tiles] docs per (query, tile): written by the count pass
+  uint64_t *tile_offs;            // ... their exclusive prefix sum, from *base_in: written by the scan
+  uint64_t *partials;             // [ceil(n_queries * n_tiles / tqk_docset_scan_tile())] scan scratch
+  const uint64_t *base_in;        // docs of the sub-batches before this one (null: 0)
+  uint64_t *out_starts;           // [n_queries + 1] the sub-batch's part of the CSR row starts
+  uint32_t *query_sizes;          // [n_queries] docs per query
+  unsigned long long *total_out;  // docs so far, this sub-batch included
+  uint32_t *out_docs;             // the write pass stores no doc at or past out_cap
+  uint64_t out_cap;
+  uint32_t n_queries, n_tiles, n_words, max_doc;
+  uint32_t stage_min_docs;        // write pass: a tile with at least this many docs goes through an LDS slab
+};
+hipError_t tqk_launch_docset_count(const TqkDocsetParams &p, hipStream_t st);
+hipError_t tqk_launch_docset_scan(const TqkDocsetParams &p, hipStream_t st);
+hipError_t tqk_launch_docset_write(const TqkDocsetParams &p, hipStream_t st);
+uint32_t tqk_docset_tile_words();
+uint32_t tqk_docset_scan_tile();
 hipError_t tqk_launch_ashare(const TqkAShareParams &p, int kpl, hipStream_t st);
 uint32_t tqk_ashare_waves_per_cu();  // resident wavefronts per CU the kernel is built for
 uint32_t tqk_bshare_waves_per_cu();  // ... its boolean instantiation

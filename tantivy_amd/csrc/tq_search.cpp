@@ -1257,6 +1257,7 @@ int finish_batch(const Batch &b) {
   b.s->stats.kernel_mask = kernel_mask;
   b.s->stats.unique_bytes = b.unique_bytes;
   b.s->stats_pending = true;
+  b.s->stats_match_bytes = 1;
   return TQ_OK;
 }
 

@@ -515,6 +515,29 @@ int tqh_count_prepared(tqh_searcher *s, uint64_t *counts) {
   });
 }
 
+// Searcher::search(&query, &DocSetCollector) of the prepared batch as CSR rows of (segment_ord, doc) pairs; *out_len =
+// pairs needed (valid also when the buffer is too small).
+int tqh_docset_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, uint64_t out_cap,
+                        uint64_t *out_starts) {
+  return guard([&] {
+    if (!s || !s->searcher || !out_starts || (out_cap && (!out_segment_ords || !out_docs)))
+      throw TantivyError(TantivyError::InvalidArgument, "null argument");
+    const std::vector<std::vector<DocAddress>> rows = s->searcher->docset_batch(s->prepared);
+    uint64_t at = 0;
+    for (size_t q = 0; q < rows.size(); ++q) {
+      out_starts[q] = at;
+      at += rows[q].size();
+    }
+    out_starts[rows.size()] = at;
+    if (at > out_cap) throw TantivyError(TantivyError::InvalidArgument, "output buffer too small");
+    for (size_t q = 0; q < rows.size(); ++q)
+      for (size_t i = 0; i < rows[q].size(); ++i) {
+        out_segment_ords[out_starts[q] + i] = rows[q][i].segment_ord;
+        out_docs[out_starts[q] + i] = rows[q][i].doc_id;
+      }
+  });
+}
+
 // ---- TermInfoStore (src/termdict/fst_termdict/term_info_store.rs)
 struct tqh_term_info_store {
   TermInfoStore store;

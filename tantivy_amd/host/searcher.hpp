@@ -319,6 +319,10 @@ class Searcher {
   // Searcher::search(&query, &Count) for a batch (count_collector.rs:39-80: per-segment counts of
   // alive matching docs, summed by merge_fruits)
   std::vector<uint64_t> count_batch(const std::vector<Weight> &weights);
+  // Searcher::search(&query, &DocSetCollector) for a batch (docset_collector.rs:26-57: every segment's alive matching
+  // docs — Weight::for_each_no_score — which merge_fruits unions into DocAddresses): per query the addresses over all
+  // segments, ordered by (segment_ord, doc_id).  Flat queries only: a phrase or a nested query throws Unsupported.
+  std::vector<std::vector<DocAddress>> docset_batch(const std::vector<Weight> &weights);
   // collect_segment for a batch on one segment: per-segment top-(offset+limit), sorted
   void collect_segment_batch(size_t segment_ord, const std::vector<Weight> &weights, uint32_t k,
                              std::vector<float> &scores, std::vector<uint32_t> &docs,

@@ -1,0 +1,162 @@
+#!/usr/bin/env python
+"""Full doc sets on the device (tq_docset_batch_device) against the Count collector over the same bitmap words
+(tq_count_batch with "count_bitmap_ratio" forced to always): a 10 M-doc Zipf segment from the oracle's generator,
+batches of and2, or5 and flat boolean queries from O.zipf_queries, each sized so that its output stays under 4 GB.
+
+Count reads every list's words once and writes nothing; the doc-set call reads them twice (count pass, write pass)
+and writes 4 bytes per doc: the yardstick is 2 x the count time + docs x 4 B at the fill bandwidth of the same run.
+
+The parent starts one fresh child process per workload, each under its own time limit, and stops at the first that
+fails.  Per workload one JSON line; all of them go to profiles/docset_bench.json.
+
+  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_PEAK_GBS = 8000.0
+OUT_BYTES_MAX = 4 << 30
+WORKLOADS = ("and2", "or5", "bool")
+
+
+def _queries(O, T, workload, n, terms):
+    if workload == "and2":
+        return [(O.MODE_AND, q.tolist()) for q in O.zipf_queries(n, 2, terms, seed=20260921)]
+    if workload == "or5":
+        return [(O.MODE_OR, q.tolist()) for q in O.zipf_queries(n, 5, terms, seed=20260922)]
+    # the shapes of bench.py's "bool" workload (an m-of-n shape would be scanned by Count: no yardstick for it)
+    M, S, N = T.MUST, T.SHOULD, T.MUST_NOT
+    shapes = [(3, [M, M, M], [0, 1, 1]), (4, [M, M, M, M], [0, 0, 1, 1]), (3, [M, S, N], None), (3, [M, M, M], [0, 0, 1])]
+    ids = O.zipf_queries(n, 4, terms, seed=20260924)
+    return [(T.MODE_BOOL, q.tolist()[:shapes[i % 4][0]], shapes[i % 4][1], shapes[i % 4][2], 0) for i, q in enumerate(ids)]
+
+
+def child(args):
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a GPU")
+    from oracle import oracle as O
+    import tantivy_amd as T
+
+    seg = O.synth_segment(args.docs, n_terms=args.terms, with_positions=False)
+    dev = T.DeviceIndex([seg], devices=[0])
+    dev.set_option("timing", 1)
+    dev.set_option("count_bitmap_ratio", 1 << 30)  # Count: always from bitmap words
+    n = args.queries
+    queries = _queries(O, T, args.child, n, args.terms)
+    counts = dev.count(queries)
+    while int(counts.sum()) * 4 > OUT_BYTES_MAX and n > 1:  # size the batch by its output
+        n = max(1, int(n * OUT_BYTES_MAX / (int(counts.sum()) * 4) * 0.95))
+        queries, counts = queries[:n], counts[:n]
+    total = int(counts.sum())
+    d_docs = torch.empty(max(1, total), dtype=torch.int32, device="cuda")
+    d_starts = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    stream = torch.cuda.Stream()
+
+    def docset_step():
+        rc = dev.raw_docset_device(queries, d_docs, total, d_starts, stream=stream.cuda_stream)
+        assert rc == 0, T.binding.lib().tq_last_error()
+
+    ds_ms, ds_wall, ct_wall = [], [], []
+    for i in range(args.warmup + args.reps):
+        t0 = time.perf_counter()
+        docset_step()
+        st = dev.last_batch_stats()  # waits for the batch; kernel_ms = HIP events around scatter + count + scan + write
+        wall = (time.perf_counter() - t0) * 1e3
+        if i >= args.warmup:
+            ds_ms.append(st["kernel_ms"])
+            ds_wall.append(wall)
+    assert st["kernels"] == ["docset"] and st["matches"] == total, st
+    starts = d_starts.cpu().numpy()
+    assert int(starts[-1]) == total and np.array_equal(np.diff(starts), counts.astype(np.int64))
+    # a sample of rows against the oracle
+    docs = None
+    for q in range(0, n, max(1, n // 8)):
+        if counts[q] > 2_000_000:
+            continue
+        if queries[q][0] == T.MODE_BOOL:
+            w, _ = O.bool_match_all(seg, queries[q][1], queries[q][2], queries[q][3], queries[q][4])
+        else:
+            w, _ = O.match_all(seg, queries[q][1], queries[q][0])
+        got = d_docs[int(starts[q]): int(starts[q + 1])].cpu().numpy().view(np.uint32)
+        assert np.array_equal(got, np.asarray(w, np.uint32)), queries[q]
+    dev.prepare(queries)
+    out = np.zeros(max(1, n), np.uint64)
+    import ctypes as C
+    for i in range(args.warmup + args.reps):
+        t0 = time.perf_counter()
+        T.binding._check(T.binding.lib().tqh_count_prepared(dev._s, out.ctypes.data_as(C.POINTER(C.c_uint64))), host=True)
+        if i >= args.warmup:
+            ct_wall.append((time.perf_counter() - t0) * 1e3)
+    assert dev.last_batch_stats()["kernels"] == ["count_bitmaps"]
+    assert np.array_equal(out[:n], counts)
+    # the fill bandwidth of this run: a device memset of the output buffer
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fill = []
+    for i in range(args.warmup + args.reps):
+        ev0.record()
+        d_docs.fill_(i)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            fill.append(ev0.elapsed_time(ev1))
+    lists = st["algorithmic_bytes"] - 4 * total  # lists x bitmap words x 4
+    k = float(np.median(ds_ms))
+    res = {"workload": args.child, "docs": args.docs, "terms": args.terms, "queries": n, "out_docs": total,
+           "docset_kernel_ms": round(k, 4), "docset_kernel_ms_min": round(float(np.min(ds_ms)), 4),
+           "docset_wall_ms": round(float(np.median(ds_wall)), 4),
+           "count_wall_ms": round(float(np.median(ct_wall)), 4),
+           "fill_ms": round(float(np.median(fill)), 4),
+           "fill_GBs": round(4 * total / (float(np.median(fill)) * 1e-3) / 1e9, 1) if total else None,
+           "yardstick_ms": round(2 * float(np.median(ct_wall)) + float(np.median(fill)), 4),
+           "algorithmic_bytes": int(st["algorithmic_bytes"]), "list_word_bytes": int(lists),
+           "model_GBs": round(st["algorithmic_bytes"] / (k * 1e-3) / 1e9, 1),
+           "model_frac_of_peak": round(st["algorithmic_bytes"] / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+           "stage_min_docs": int(os.environ.get("TQ_DOCSET_STAGE_MIN", "2048")), "reps": args.reps, "warmup": args.warmup, "rows_checked_against_oracle": True}
+    print("RESULT " + json.dumps(res))
+    dev.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--docs", type=int, default=10_000_000)
+    ap.add_argument("--terms", type=int, default=256)
+    ap.add_argument("--queries", type=int, default=1000)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--step-timeout", type=int, default=240)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "docset_bench.json"))
+    ap.add_argument("--child", choices=WORKLOADS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    results = []
+    for wl in WORKLOADS:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", wl, "--docs", str(args.docs), "--terms", str(args.terms),
+               "--queries", str(args.queries), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+        try:
+            r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            raise SystemExit("%s: no result after %d s: stopping" % (wl, args.step_timeout))
+        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+        if r.returncode != 0 or not line:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            raise SystemExit("%s failed (exit %d): stopping" % (wl, r.returncode))
+        results.append(json.loads(line[-1][7:]))
+        print(json.dumps(results[-1]), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump({"bench": "tools/bench_docset.py", "device": "MI355X", "results": results}, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
