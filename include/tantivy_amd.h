@@ -397,7 +397,7 @@ int tq_last_batch_match_counts(tq_segment *seg, uint32_t *out, uint32_t n_querie
  * Not taken: TQ_MODE_PHRASE and nested queries (tq_query.nested_occurs / atom_of trees) — a batch that holds one fails
  * as a whole with TQ_ERR_UNSUPPORTED, tq_last_error() names the index of the first such query, nothing is launched and
  * the segment stays usable; malformed queries (mixed occurs in one clause, occur > 2, handle out of range, n_terms 0
- * or > TQ_MAX_TERMS) return TQ_ERR_INVALID the same way.  Scores (Weight::for_each) are not produced.
+ * or > TQ_MAX_TERMS) return TQ_ERR_INVALID the same way.  Scores (Weight::for_each): tq_docset_scored_batch below.
  * Afterwards tq_last_batch_match_counts gives the per-query sizes, tq_batch_stats.matches the total docs,
  * kernel_mask = TQ_KERNEL_DOCSET and algorithmic_bytes = lists x bitmap words x 4 + 4 x docs. */
 int tq_docset_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
@@ -407,6 +407,39 @@ int tq_docset_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries
  * consumer the total.  Returns TQ_OK even when the total exceeds out_cap (only the device knows). */
 int tq_docset_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
                            uint32_t *d_out_docs, uint64_t out_cap, uint64_t *d_out_starts, void *hip_stream);
+
+/* ---- doc sets with scores ----
+ * replaces: Weight::for_each -> for_each_scorer (src/query/weight.rs:9-18,89-97) under default_collect_segment_impl
+ * (src/collector/mod.rs:186-221) — what every collector whose requires_scoring() is true asks a Weight for
+ * (TopDocs::tweak_score / custom_score, a MultiCollector with a scoring child, a user collector that reads the score):
+ * every ALIVE matching doc with its BM25 score, however many there are (top-k stops at TQ_MAX_K).
+ * out_docs / out_starts are exactly what tq_docset_batch returns for the same queries — same query shapes, same
+ * refusals (TQ_MODE_PHRASE and nested queries: TQ_ERR_UNSUPPORTED naming the first such query, nothing launched), same
+ * capacity protocol — and out_scores[i] is the score of out_docs[i]; one out_cap covers both arrays (host variant, total
+ * > out_cap: TQ_ERR_INVALID, out_starts complete, no doc and no score written).  Unlike tq_docset_batch, weights and
+ * tf_cache are REQUIRED for every query that has a scoring (non-MustNot, present) list — TQ_ERR_INVALID naming the
+ * query otherwise — and are used as in tq_search_batch; k is still ignored.
+ * Scores are the unpruned scorers': per list bm25(weights[i], tf_cache[fieldnorm id], tf) with an IEEE divide (a
+ * TQ_BASIC list scores tf = 1; no fieldnorms: the constant id); TQ_MODE_OR: 0 + the lists that hold the doc in query
+ * order (SumCombiner); TQ_MODE_AND and the Must part of TQ_MODE_BOOL: clauses sorted by cost (stable), first + second
+ * + (0 + the others) (Intersection::score, src/query/intersection.rs:325-329) — Should clauses that
+ * min_should_match == n_should >= 2 turned into Must clauses join the sort; a clause of several lists scores the sum
+ * of its present lists in clause order; Should clauses beside a Must part add req + opt with opt = the sum of the present
+ * Should clauses (src/query/reqopt_scorer.rs:85-98).  One lane computes one doc's score in that order: the result does
+ * not depend on the batch, the sub-batching or the run.
+ * A scoring pass (tq_docset_score.hip) follows every write pass: it reads the rows back and asks each scoring list
+ * for the doc's tf — through its bitmap + rank directory and byte-wide tfs, its range directory, or a block search.
+ * Afterwards tq_last_batch_match_counts / tq_batch_stats.matches as for doc sets, kernel_mask = TQ_KERNEL_DOCSET |
+ * TQ_KERNEL_DOCSET_SCORE, and algorithmic_bytes = the doc-set figure (lists x bitmap words x 4 + 4 x docs) + per doc
+ * 4 (score) + 1 (fieldnorm byte) + per scoring list of every query 8 bytes per 32 docs of the segment (a bitmap word
+ * with its rank: the most a list's presence and posting index cost; tf bytes are not counted). */
+int tq_docset_scored_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                           uint32_t *out_docs, float *out_scores, uint64_t out_cap, uint64_t *out_starts);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream): nothing is written at or past
+ * out_cap in either array, the call returns TQ_OK and d_out_starts[n_queries] holds the total. */
+int tq_docset_scored_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                                  uint32_t *d_out_docs, float *d_out_scores, uint64_t out_cap,
+                                  uint64_t *d_out_starts, void *hip_stream);
 
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
@@ -440,6 +473,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_COUNT_BITMAPS 0x800u /* count_bitmap_kernel (tq_count_batch over bitmap words) */
 #define TQ_KERNEL_TREE 0x1000u         /* tree_kernel (nested boolean queries over bitmap words) */
 #define TQ_KERNEL_DOCSET 0x2000u       /* docset_count / docset_write kernels (tq_docset_batch* over bitmap words) */
+#define TQ_KERNEL_DOCSET_SCORE 0x4000u /* docset_score kernel (tq_docset_scored_batch*: the scoring pass behind the write pass) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py

@@ -100,6 +100,11 @@ int tqh_count_prepared(tqh_searcher *s, uint64_t *counts);
  * "doc sets"): a phrase or a nested query fails the batch as unsupported. */
 int tqh_docset_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, uint64_t out_cap,
                         uint64_t *out_starts);
+/* The same for a collector that needs scores (Weight::for_each: TopDocs::tweak_score / custom_score, a MultiCollector
+ * with a scoring child): out_scores[i] = the BM25 score of pair i under the searcher's index-wide statistics
+ * (tq_docset_scored_batch on every segment).  Same rows, same capacity protocol; one out_cap covers the three arrays. */
+int tqh_docset_scored_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, float *out_scores,
+                               uint64_t out_cap, uint64_t *out_starts);
 /* Collector::collect_segment of the prepared batch on one segment: [n][k] sorted. */
 int tqh_collect_segment_prepared(tqh_searcher *s, uint32_t segment_ord, uint32_t k, float *scores,
                                  uint32_t *docs, uint32_t *counts);

@@ -53,10 +53,11 @@ KERNEL_BSHARE = 0x400
 KERNEL_COUNT_BITMAPS = 0x800
 KERNEL_TREE = 0x1000
 KERNEL_DOCSET = 0x2000
+KERNEL_DOCSET_SCORE = 0x4000
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
-                0x1000: "tree", 0x2000: "docset"}
+                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score"}
 
 
 def kernel_names(mask):
@@ -110,6 +111,7 @@ EXPORTS = [
     "tqh_term_info_store_get", "tqh_term_info_store_write", "tqh_searcher_add_segment_with_store",
     "tqh_count_prepared", "tqh_searcher_add_segment_device_with_store",
     "tq_docset_batch", "tq_docset_batch_device", "tqh_docset_prepared",
+    "tq_docset_scored_batch", "tq_docset_scored_batch_device", "tqh_docset_scored_prepared",
 ]
 
 
@@ -159,6 +161,9 @@ def lib():
     L.tq_docset_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_docset_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, vp, C.c_uint64, vp, vp]
     L.tqh_docset_prepared.argtypes = [vp, u32p, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.tq_docset_scored_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p, f32p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.tq_docset_scored_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, vp, vp, C.c_uint64, vp, vp]
+    L.tqh_docset_scored_prepared.argtypes = [vp, u32p, u32p, f32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_last_batch_query_kernels.argtypes = [vp, u32p, C.c_uint32]
     u64p = C.POINTER(C.c_uint64)
     L.tq_encoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
@@ -668,6 +673,28 @@ class DeviceIndex:
         pairs = np.stack([ords, docs], axis=1)
         return [pairs[int(starts[q]): int(starts[q + 1])] for q in range(n)]
 
+    def docset_scored(self, queries):
+        """Searcher::search with a collector that needs scores (Weight::for_each) for a batch: per query the (n, 2)
+        uint32 array of (segment_ord, doc) rows docset() returns and a float32 array of their BM25 scores under the
+        index-wide statistics."""
+        self.prepare(queries)
+        n = len(queries)
+        starts = np.zeros(n + 1, np.uint64)
+        ords = np.zeros(1, np.uint32)
+        docs = np.zeros(1, np.uint32)
+        scores = np.zeros(1, np.float32)
+        u64p = C.POINTER(C.c_uint64)
+        rc = lib().tqh_docset_scored_prepared(self._s, _u32(ords), _u32(docs), _f32(scores), 0, starts.ctypes.data_as(u64p))
+        if rc != 0 and int(starts[n]) > 0:  # too small: the call reported the size
+            ords = np.zeros(int(starts[n]), np.uint32)
+            docs = np.zeros(int(starts[n]), np.uint32)
+            scores = np.zeros(int(starts[n]), np.float32)
+            rc = lib().tqh_docset_scored_prepared(self._s, _u32(ords), _u32(docs), _f32(scores), docs.size,
+                                                  starts.ctypes.data_as(u64p))
+        _check(rc, host=True)
+        pairs = np.stack([ords, docs], axis=1)
+        return [(pairs[int(starts[q]): int(starts[q + 1])], scores[int(starts[q]): int(starts[q + 1])]) for q in range(n)]
+
     # ---- raw C ABI access (parity tests)
     def segment_raw(self, segment_ord=0):
         return C.c_void_p(lib().tqh_segment_raw(self._s, segment_ord))
@@ -792,6 +819,44 @@ class DeviceIndex:
         qs, keep = self._raw_flat_queries(queries, segment_ord)
         return lib().tq_docset_batch_device(self.segment_raw(segment_ord), qs, len(queries), d_docs.data_ptr(), int(cap),
                                             d_starts.data_ptr(), C.c_void_p(stream) if stream else None)
+
+    def _raw_scored_queries(self, queries, weights, cache, segment_ord):
+        """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =
+        np.float32[256] (or None).  -> (array, keep-alive list)"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        if cache is not None:
+            cache = np.ascontiguousarray(cache, np.float32)
+            keep.append(cache)
+        for i in range(len(queries)):
+            if weights is not None and weights[i] is not None:
+                ws = (C.c_float * max(1, len(weights[i])))(*weights[i])
+                keep.append(ws)
+                qs[i].weights = C.cast(ws, C.POINTER(C.c_float))
+            if cache is not None:
+                qs[i].tf_cache = _f32(cache)
+        return qs, keep
+
+    def raw_docset_scored(self, queries, cap, segment_ord=0, guard=0, weights=None, cache=None):
+        """Direct tq_docset_scored_batch on one segment with buffers of `cap` entries -> (rc, docs, scores, starts).  docs
+        and scores have cap + guard entries preset to 0xDEADBEEF (the scores: that bit pattern as f32); weights / cache
+        as raw_search takes them (None: the queries' weights / tf_cache stay NULL)."""
+        n = len(queries)
+        qs, keep = self._raw_scored_queries(queries, weights, cache, segment_ord)
+        docs = np.full(max(1, cap + guard), 0xDEADBEEF, np.uint32)
+        scores = np.full(max(1, cap + guard), 0xDEADBEEF, np.uint32).view(np.float32)
+        starts = np.zeros(n + 1, np.uint64)
+        rc = lib().tq_docset_scored_batch(self.segment_raw(segment_ord), qs, n, _u32(docs), _f32(scores), int(cap),
+                                          starts.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return rc, docs[: cap + guard], scores[: cap + guard], starts
+
+    def raw_docset_scored_device(self, queries, d_docs, d_scores, cap, d_starts, segment_ord=0, stream=None, weights=None,
+                                 cache=None):
+        """Direct tq_docset_scored_batch_device: d_docs (int32 / uint32), d_scores (float32) with at least cap entries and
+        d_starts (int64 / uint64, len(queries) + 1 entries) are torch tensors on the segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_scored_queries(queries, weights, cache, segment_ord)
+        return lib().tq_docset_scored_batch_device(self.segment_raw(segment_ord), qs, len(queries), d_docs.data_ptr(),
+                                                   d_scores.data_ptr(), int(cap), d_starts.data_ptr(),
+                                                   C.c_void_p(stream) if stream else None)
 
     def raw_count(self, queries, weights, cache, segment_ord=0):
         """Direct tq_count_batch (Count collector): alive matches per query."""

@@ -230,6 +230,9 @@ void tq_segment_free(tq_segment *s) {
   s->d_docset_partials.release();
   s->d_docset_starts.release();
   s->d_docset_docs.release();
+  s->d_docset_squeries.release();
+  s->d_docset_caches.release();
+  s->d_docset_scores.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
@@ -316,7 +319,7 @@ int tq_docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, 
   if (!s || (!queries && n_queries) || (!out_docs && out_cap) || !out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_batch: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, out_docs, out_cap, out_starts, false, nullptr);
+  return docset_batch(s, queries, n_queries, out_docs, nullptr, out_cap, out_starts, false, false, nullptr);
 }
 
 int tq_docset_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *d_out_docs,
@@ -324,7 +327,23 @@ int tq_docset_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_qu
   if (!s || (!queries && n_queries) || (!d_out_docs && out_cap) || !d_out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_batch_device: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, d_out_docs, out_cap, d_out_starts, true, hip_stream);
+  return docset_batch(s, queries, n_queries, d_out_docs, nullptr, out_cap, d_out_starts, false, true, hip_stream);
+}
+
+int tq_docset_scored_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
+                           uint64_t out_cap, uint64_t *out_starts) {
+  if (!s || (!queries && n_queries) || ((!out_docs || !out_scores) && out_cap) || !out_starts)
+    return fail(TQ_ERR_INVALID, "tq_docset_scored_batch: null argument");
+  TQ_SEGMENT_LOCK(s);
+  return docset_batch(s, queries, n_queries, out_docs, out_scores, out_cap, out_starts, true, false, nullptr);
+}
+
+int tq_docset_scored_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *d_out_docs,
+                                  float *d_out_scores, uint64_t out_cap, uint64_t *d_out_starts, void *hip_stream) {
+  if (!s || (!queries && n_queries) || ((!d_out_docs || !d_out_scores) && out_cap) || !d_out_starts)
+    return fail(TQ_ERR_INVALID, "tq_docset_scored_batch_device: null argument");
+  TQ_SEGMENT_LOCK(s);
+  return docset_batch(s, queries, n_queries, d_out_docs, d_out_scores, out_cap, d_out_starts, true, true, hip_stream);
 }
 
 int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {

@@ -42,6 +42,7 @@ int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const 
     const uint32_t h = q.terms[i];
     if (h == TQ_TERM_ABSENT) continue;
     if (h >= s->terms.size()) return *why = "term handle out of range", FLAT_INVALID;
+    cl[c].pos[cl[c].n] = i;
     cl[c].terms[cl[c].n++] = h;
     cl[c].cost += s->terms[h].doc_freq;
   }

@@ -2,15 +2,18 @@
 // SegmentCollector::collect_block with the alive filter, src/query/weight.rs:23-35,101-121, src/collector/mod.rs:186-221)
 // as CSR rows of ascending doc ids.  Every list is reached through bitmap words: its own bitmap, or — a list without
 // one — bits scattered into the batch's scratch (count_scatter_kernel); tq_docset.hip counts, scans and writes.
+// tq_docset_scored_batch*: the same rows with every doc's BM25 score (Weight::for_each, src/query/weight.rs:9-18,89-97):
+// tq_docset_score.hip's pass behind every write pass, over a scoring descriptor of its own (score_expression).
 #include "tq_internal.hpp"
 
 #include <unordered_map>
 
 namespace tqi {
 
-int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why) {
+int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why, FlatClauses *fc_out) {
   dq = TqkDocsetQuery{};
-  FlatClauses fc;
+  FlatClauses fc_own;
+  FlatClauses &fc = fc_out ? *fc_out : fc_own;
   const int prc = parse_flat_clauses(s, q, fc, why);
   if (prc != FLAT_OK) return prc;
   using Clause = FlatClauses::Clause;
@@ -54,20 +57,71 @@ int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, cons
   return FLAT_OK;
 }
 
+// The scoring lists of a flat query in the order the unpruned scorers add them up (BooleanWeight::complex_scorer,
+// boolean_weight.rs:236-431, under for_each, :521-528): the Must clauses — with the Should clauses that
+// minimum_number_should_match == n_should >= 2 turned into Must clauses behind them — sorted by cost, stable
+// (intersect_scorers, intersection.rs:31); then the Should clauses in query order.  MustNot lists score nothing.
+// Every list with the access path tq_docset_score.hip takes: its bitmap, its range directory, or the block search.
+void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, TqkScoreQuery &sq) {
+  sq = TqkScoreQuery{};
+  using Clause = FlatClauses::Clause;
+  uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
+  if (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0)) return;  // the empty set
+  const bool should_is_must = msm >= 2 && msm == fc.n_should;
+  const Clause *must[TQ_MAX_TERMS];
+  uint32_t n_must = 0;
+  for (uint32_t c = 0; c < fc.n_cl; ++c)
+    if (fc.cl[c].occur == TQ_MUST) must[n_must++] = &fc.cl[c];
+  if (should_is_must)
+    for (uint32_t c = 0; c < fc.n_cl; ++c)
+      if (fc.cl[c].occur == TQ_SHOULD && fc.cl[c].n) must[n_must++] = &fc.cl[c];
+  small_stable_sort(must, must + n_must, [](const Clause *a, const Clause *b) { return a->cost < b->cost; });
+  uint32_t n = 0;
+  auto put = [&](const Clause &c) {
+    for (uint32_t i = 0; i < c.n; ++i) {
+      const TermHost &th = s->terms[c.terms[i]];
+      sq.handle[n] = c.terms[i];
+      sq.weight[n] = q.weights[c.pos[i]];
+      uint32_t kind = TQK_SCORE_BLOCKS;
+      if (th.dense_blob && s->opt.use_dense) {
+        kind = TQK_SCORE_BITMAP;
+        sq.tab[n] = th.dense_blob;
+        sq.aux[n] = th.tf8_blob;
+      } else if (th.rdir_blob && th.rdir_ent) {
+        kind = TQK_SCORE_RDIR;
+        sq.tab[n] = th.rdir_blob;
+        sq.aux[n] = th.rdir_ent;
+        sq.shift[n] = th.rdir_shift;
+      }
+      sq.access |= kind << (2u * n);
+      if (i + 1 == c.n) sq.clause_end |= 1u << n;
+      ++n;
+    }
+  };
+  for (uint32_t c = 0; c < n_must; ++c) put(*must[c]);
+  sq.n_must_lists = n;
+  if (!should_is_must)
+    for (uint32_t c = 0; c < fc.n_cl; ++c)
+      if (fc.cl[c].occur == TQ_SHOULD && fc.cl[c].n) put(fc.cl[c]);
+  sq.n_lists = n;
+}
+
 namespace {
 
 struct SubBatch {  // consecutive whole queries whose lists without a bitmap fit the scratch together
   uint32_t q0 = 0, q1 = 0;
   size_t wg0 = 0, wg1 = 0;  // its part of the scatter work list
   uint32_t n_temp = 0;
+  bool score_blocks = false;  // some scoring list of its queries is reached by the block search
 };
 enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
 
 }  // namespace
 
-int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
-                 uint64_t *out_starts, bool device_out, void *hip_stream) {
-  const char *const fn = device_out ? "tq_docset_batch_device" : "tq_docset_batch";
+int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream) {
+  const char *const fn = scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
+                                : (device_out ? "tq_docset_batch_device" : "tq_docset_batch");
   // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
   static const uint32_t kStageMin = tune_u32("TQ_DOCSET_STAGE_MIN", 2048);
   static const uint64_t kTempBudget = (uint64_t)std::max<uint32_t>(1u, tune_u32("TQ_COUNT_TEMP_MB", 1024)) << 20;
@@ -82,14 +136,36 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
 
   // every query is checked before anything is launched: a batch fails as a whole
   std::vector<TqkDocsetQuery> dqs(n_queries);
+  std::vector<TqkScoreQuery> sqs(scored ? n_queries : 0u);
+  std::vector<const float *> caches;  // the batch's Bm25Weight caches in order of first use (pointer identity, as in search)
   uint64_t algo_bytes = 0;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     const char *why = "";
-    const int rc = docset_expression(s, queries[qi], dqs[qi], &why);
+    FlatClauses fc;
+    const tq_query &q = queries[qi];
+    const int rc = docset_expression(s, q, dqs[qi], &why, scored ? &fc : nullptr);
     if (rc == FLAT_UNSUPPORTED)
       return fail(TQ_ERR_UNSUPPORTED, "%s: query %u is %s: doc sets of phrases and nested queries stay on the CPU", fn, qi, why);
     if (rc != FLAT_OK) return fail(TQ_ERR_INVALID, "%s: query %u: %s", fn, qi, why);
     algo_bytes += (uint64_t)dqs[qi].n_terms * n_words * 4u;
+    if (!scored) continue;
+    bool has_list = false;
+    for (uint32_t c = 0; c < fc.n_cl; ++c) has_list = has_list || (fc.cl[c].occur != TQ_MUST_NOT && fc.cl[c].n);
+    if (has_list && (!q.weights || !q.tf_cache)) return fail(TQ_ERR_INVALID, "%s: query %u: null weights / tf_cache", fn, qi);
+    if (has_list)
+      for (uint32_t i = 0; i < q.n_terms; ++i)
+        if (!std::isfinite(q.weights[i])) return fail(TQ_ERR_INVALID, "%s: query %u: weight %u is not finite", fn, qi, i);
+    if (has_list) score_expression(s, q, fc, sqs[qi]);
+    if (sqs[qi].n_lists) {
+      uint32_t ci = (uint32_t)caches.size();
+      while (ci > 0 && caches[ci - 1] != q.tf_cache) --ci;  // (last first: neighbours share one)
+      if (ci == 0) {
+        caches.push_back(q.tf_cache);
+        ci = (uint32_t)caches.size();
+      }
+      sqs[qi].cache_idx = ci - 1u;
+    }
+    algo_bytes += (uint64_t)sqs[qi].n_lists * n_words * 8u;
   }
   // sub-batches; a list without a bitmap gets a slot of the scratch for the duration of its sub-batch
   std::vector<SubBatch> subs;
@@ -101,6 +177,9 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     cur.q1 = q1;
     cur.wg1 = wgs.size();
     cur.n_temp = (uint32_t)slot.size();
+    for (uint32_t qi = cur.q0; scored && qi < q1; ++qi)
+      for (uint32_t m = 0; m < sqs[qi].n_lists; ++m)
+        cur.score_blocks = cur.score_blocks || ((sqs[qi].access >> (2u * m)) & 3u) == TQK_SCORE_BLOCKS;
     max_sub_temp = std::max(max_sub_temp, cur.n_temp);
     max_sub_n = std::max(max_sub_n, cur.q1 - cur.q0);
     subs.push_back(cur);
@@ -139,7 +218,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (wrc != TQ_OK) return wrc;
   }
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = TQ_KERNEL_DOCSET;
+  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u);
   s->stats.algorithmic_bytes = algo_bytes;
   s->stats_pending = false;
   s->last_batch_queries = 0;
@@ -151,13 +230,16 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     return TQ_OK;
   }
-  if (!wgs.empty()) {
+  if (!wgs.empty() || scored) {  // (the scoring pass reads term records: saturated tfs, the block search)
     const int src = sync_terms(s, s->stream);
     if (src != TQ_OK) return src;
   }
   const size_t q_bytes = (size_t)n_queries * sizeof(TqkDocsetQuery), wg_bytes = wgs.size() * sizeof(uint4);
+  const size_t sq_bytes = sqs.size() * sizeof(TqkScoreQuery), cache_bytes = caches.size() * 256u * sizeof(float);
   const size_t max_entries = (size_t)max_sub_n * n_tiles;
-  int rc = s->h_docset.ensure(q_bytes + wg_bytes);
+  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes);
+  if (rc == TQ_OK && scored) rc = s->d_docset_squeries.ensure(sq_bytes);
+  if (rc == TQ_OK && scored) rc = s->d_docset_caches.ensure(std::max<size_t>(cache_bytes, 256u * sizeof(float)));
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
   if (rc == TQ_OK) rc = s->d_count_wgs.ensure(wg_bytes);
   if (rc == TQ_OK) rc = s->d_count_bits.ensure((size_t)max_sub_temp * words_per_list * sizeof(uint32_t));
@@ -180,9 +262,16 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   HIP_TRY(hipMemcpyAsync(s->d_docset_queries.p, s->h_docset.p, q_bytes, hipMemcpyHostToDevice, st));
   if (wg_bytes)
     HIP_TRY(hipMemcpyAsync(s->d_count_wgs.p, (const uint8_t *)s->h_docset.p + q_bytes, wg_bytes, hipMemcpyHostToDevice, st));
+  if (scored) {
+    uint8_t *const h_sq = (uint8_t *)s->h_docset.p + q_bytes + wg_bytes;
+    memcpy(h_sq, sqs.data(), sq_bytes);
+    for (size_t c = 0; c < caches.size(); ++c) memcpy(h_sq + sq_bytes + c * 256u * sizeof(float), caches[c], 256u * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(s->d_docset_squeries.p, h_sq, sq_bytes, hipMemcpyHostToDevice, st));
+    if (cache_bytes) HIP_TRY(hipMemcpyAsync(s->d_docset_caches.p, h_sq + sq_bytes, cache_bytes, hipMemcpyHostToDevice, st));
+  }
 
   uint64_t *const d_starts = device_out ? out_starts : (uint64_t *)s->d_docset_starts.p;
-  auto enqueue = [&](const SubBatch &sb, uint32_t stages, uint32_t *d_docs, uint64_t cap) -> int {
+  auto enqueue = [&](const SubBatch &sb, uint32_t stages, uint32_t *d_docs, float *d_scores, uint64_t cap) -> int {
     if ((stages & DS_SCATTER) && sb.n_temp) {  // the sub-batch's lists without a bitmap, as bits
       HIP_TRY(hipMemsetAsync(s->d_count_bits.p, 0, (size_t)sb.n_temp * words_per_list * sizeof(uint32_t), st));
       const hipError_t se = tqk_launch_count_scatter(s->dseg, s->d_terms, (const uint4 *)s->d_count_wgs.p + sb.wg0,
@@ -212,6 +301,22 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       if (e == hipSuccess) e = tqk_launch_docset_scan(p, st);
     }
     if (e == hipSuccess && (stages & DS_WRITE)) e = tqk_launch_docset_write(p, st);
+    if (e == hipSuccess && (stages & DS_WRITE) && scored) {  // right behind its write pass: the tables are this sub-batch's
+      TqkScoreParams sp{};
+      sp.seg = s->dseg;
+      sp.terms = s->d_terms;
+      sp.queries = (const TqkScoreQuery *)s->d_docset_squeries.p + sb.q0;
+      sp.caches = (const float *)s->d_docset_caches.p;
+      sp.tile_counts = p.tile_counts;
+      sp.tile_offs = p.tile_offs;
+      sp.out_docs = d_docs;
+      sp.out_scores = d_scores;
+      sp.out_cap = cap;
+      sp.n_queries = p.n_queries;
+      sp.n_tiles = n_tiles;
+      sp.any_blocks = sb.score_blocks ? 1u : 0u;
+      e = tqk_launch_docset_score(sp, st);
+    }
     if (e != hipSuccess) return fail(TQ_ERR_HIP, "doc-set kernel launch: %s", hipGetErrorString(e));
     return TQ_OK;
   };
@@ -220,7 +325,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   if (device_out) {
     if (timed) HIP_TRY(hipEventRecord(s->ev_k0[ring], st));
     for (const SubBatch &sb : subs) {
-      rc = enqueue(sb, DS_SCATTER | DS_COUNT | DS_WRITE, out_docs, out_cap);
+      rc = enqueue(sb, DS_SCATTER | DS_COUNT | DS_WRITE, out_docs, out_scores, out_cap);
       if (rc != TQ_OK) return rc;
     }
     if (timed) {
@@ -229,7 +334,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       ++s->batches_timed;
     }
     s->stats_pending = true;  // the total is on the device: tq_last_batch_stats reads it
-    s->stats_match_bytes = 4;
+    s->stats_match_bytes = scored ? 9 : 4;  // doc [+ score + fieldnorm byte]
     HIP_TRY(hipEventRecord(s->ev_batch_done, st));
     s->last_stream = st;
     s->batch_in_flight = true;
@@ -237,28 +342,32 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   }
   // host outputs: the row starts first — they say whether the docs fit
   for (const SubBatch &sb : subs) {
-    rc = enqueue(sb, DS_SCATTER | DS_COUNT, nullptr, 0);
+    rc = enqueue(sb, DS_SCATTER | DS_COUNT, nullptr, nullptr, 0);
     if (rc != TQ_OK) return rc;
   }
   HIP_TRY(hipMemcpyAsync(out_starts, d_starts, ((size_t)n_queries + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const uint64_t total = out_starts[n_queries];
   s->stats.matches = total;
-  s->stats.algorithmic_bytes += 4u * total;
+  s->stats.algorithmic_bytes += (scored ? 9u : 4u) * total;
   if (total > out_cap)
     return fail(TQ_ERR_INVALID, "%s: the batch has %llu docs, out_cap is %llu (out_starts is filled: retry with that many)", fn,
                 (unsigned long long)total, (unsigned long long)out_cap);
   if (!total) return TQ_OK;
   rc = s->d_docset_docs.ensure((size_t)total * sizeof(uint32_t));
+  if (rc == TQ_OK && scored) rc = s->d_docset_scores.ensure((size_t)total * sizeof(float));
   if (rc != TQ_OK) return rc;
   for (const SubBatch &sb : subs) {
     // one sub-batch: its tables and bits are still there; several: each is evaluated again (the scratch held the last one's)
-    rc = enqueue(sb, subs.size() == 1 ? DS_WRITE : (DS_SCATTER | DS_COUNT | DS_WRITE), (uint32_t *)s->d_docset_docs.p, total);
+    rc = enqueue(sb, subs.size() == 1 ? DS_WRITE : (DS_SCATTER | DS_COUNT | DS_WRITE), (uint32_t *)s->d_docset_docs.p,
+                 (float *)s->d_docset_scores.p, total);
     if (rc != TQ_OK) return rc;
   }
   HIP_TRY(hipMemcpyAsync(out_docs, s->d_docset_docs.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (scored) HIP_TRY(hipMemcpyAsync(out_scores, s->d_docset_scores.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (s->d_docset_docs.cap > ((size_t)256 << 20)) s->d_docset_docs.release();  // (a large result is not kept as scratch)
+  if (s->d_docset_scores.cap > ((size_t)256 << 20)) s->d_docset_scores.release();
   return TQ_OK;
 }
 

@@ -301,10 +301,12 @@ struct tq_segment {
   DevBuf d_count_queries, d_count_out, d_count_bits, d_count_wgs;  // Count collector over bitmaps (tq_count.hip)
   // full doc sets (tq_docset.hip): descriptors, the (query, tile) tables of the scan, and the host variant's outputs
   DevBuf d_docset_queries, d_docset_counts, d_docset_offs, d_docset_partials, d_docset_starts, d_docset_docs;
+  // ... with scores (tq_docset_score.hip): scoring descriptors, the batch's Bm25Weight caches, the host variant's scores
+  DevBuf d_docset_squeries, d_docset_caches, d_docset_scores;
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
-           d_docset_docs.cap;
+           d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -385,7 +387,7 @@ struct tq_segment {
   tq_batch_stats stats{};
   bool stats_pending = false;
   uint32_t stats_match_bytes = 1;  // what a match adds to algorithmic_bytes once d_match_counter is read: a fieldnorm
-                                   // byte per scored doc, 4 bytes per doc of a doc-set batch on the device
+                                   // byte per scored doc, 4 bytes per doc of a doc-set batch on the device (9 with scores)
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -776,6 +778,7 @@ bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool 
 struct FlatClauses {
   struct Clause {
     uint32_t id, occur, n = 0, terms[TQ_MAX_TERMS];
+    uint32_t pos[TQ_MAX_TERMS];  // where terms[i] stands in tq_query.terms (its weight)
     uint64_t cost = 0;
   };
   Clause cl[TQ_MAX_TERMS];
@@ -784,12 +787,16 @@ struct FlatClauses {
 };
 enum { FLAT_OK = 0, FLAT_UNSUPPORTED, FLAT_INVALID };
 int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why);
-// ---- tq_docset.cpp: full doc sets (tq_docset_batch / tq_docset_batch_device)
-// the query as a TqkDocsetQuery: FLAT_*; lists without a bitmap are left as their term HANDLE in dq.dense (narrow bit set)
-int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why);
-// out_docs / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on hip_stream
-int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
-                 uint64_t *out_starts, bool device_out, void *hip_stream);
+// ---- tq_docset.cpp: full doc sets (tq_docset_batch* / tq_docset_scored_batch*)
+// the query as a TqkDocsetQuery: FLAT_*; lists without a bitmap are left as their term HANDLE in dq.dense (narrow bit set);
+// fc_out (or null): the clauses it was made from
+int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why, FlatClauses *fc_out = nullptr);
+// the scoring lists of the same query in summation order (weights and access paths; cache_idx is left to the caller)
+void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, TqkScoreQuery &sq);
+// out_docs / out_scores / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on
+// hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used
+int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream);
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);

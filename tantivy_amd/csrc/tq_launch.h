@@ -303,6 +303,39 @@ hipError_t tqk_launch_docset_scan(const TqkDocsetParams &p, hipStream_t st);
 hipError_t tqk_launch_docset_write(const TqkDocsetParams &p, hipStream_t st);
 uint32_t tqk_docset_tile_words();
 uint32_t tqk_docset_scan_tile();
+// ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
+// How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
+#define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
+#define TQK_SCORE_RDIR 1u    // tab = its range directory, aux = the directory's entries, shift = the directory's shift
+#define TQK_SCORE_BLOCKS 2u  // seek_block + lookup_in_blocks over the packed list
+struct TqkScoreQuery {             // 472 bytes: every non-MustNot list of the query, in the order its scores are summed
+  uint32_t n_lists;                // 0: the query matches nothing
+  uint32_t cache_idx;              // which 256-float Bm25Weight cache of the batch
+  uint32_t access;                 // 2 bits per list: TQK_SCORE_*
+  uint32_t clause_end;             // bit m: list m is the last of its clause (a clause = the sum of its present lists)
+  uint32_t n_must_lists;           // lists [0, n_must_lists): the Must clauses, cheapest first (Intersection::score: first +
+                                   // second + the sum of the others); behind them the Should clauses (req + opt, or the union)
+  uint32_t pad_;
+  uint32_t handle[TQD_MAX_TERMS];  // term record (exact tfs of saturated entries, the block search)
+  float weight[TQD_MAX_TERMS];
+  uint32_t shift[TQD_MAX_TERMS];
+  const void *tab[TQD_MAX_TERMS];
+  const void *aux[TQD_MAX_TERMS];
+};
+struct TqkScoreParams {
+  TqdSegment seg;
+  const TqdTerm *terms;
+  const TqkScoreQuery *queries;    // [n_queries] (one sub-batch)
+  const float *caches;             // n_caches x 256
+  const uint32_t *tile_counts;     // [n_queries][n_tiles] and their prefix sum: what the sub-batch's count pass and scan left
+  const uint64_t *tile_offs;
+  const uint32_t *out_docs;        // the rows the write pass has just stored
+  float *out_scores;               // out_scores[i] = the score of out_docs[i]; nothing at or past out_cap
+  uint64_t out_cap;
+  uint32_t n_queries, n_tiles;
+  uint32_t any_blocks;             // some list of the sub-batch is TQK_SCORE_BLOCKS (selects the instantiation with LDS)
+};
+hipError_t tqk_launch_docset_score(const TqkScoreParams &p, hipStream_t st);
 hipError_t tqk_launch_ashare(const TqkAShareParams &p, int kpl, hipStream_t st);
 uint32_t tqk_ashare_waves_per_cu();  // resident wavefronts per CU the kernel is built for
 uint32_t tqk_bshare_waves_per_cu();  // ... its boolean instantiation

@@ -538,6 +538,29 @@ int tqh_docset_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *o
   });
 }
 
+// ... with every pair's score (Searcher::docset_scored_batch)
+int tqh_docset_scored_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, float *out_scores,
+                               uint64_t out_cap, uint64_t *out_starts) {
+  return guard([&] {
+    if (!s || !s->searcher || !out_starts || (out_cap && (!out_segment_ords || !out_docs || !out_scores)))
+      throw TantivyError(TantivyError::InvalidArgument, "null argument");
+    const std::vector<std::vector<std::pair<DocAddress, Score>>> rows = s->searcher->docset_scored_batch(s->prepared);
+    uint64_t at = 0;
+    for (size_t q = 0; q < rows.size(); ++q) {
+      out_starts[q] = at;
+      at += rows[q].size();
+    }
+    out_starts[rows.size()] = at;
+    if (at > out_cap) throw TantivyError(TantivyError::InvalidArgument, "output buffer too small");
+    for (size_t q = 0; q < rows.size(); ++q)
+      for (size_t i = 0; i < rows[q].size(); ++i) {
+        out_segment_ords[out_starts[q] + i] = rows[q][i].first.segment_ord;
+        out_docs[out_starts[q] + i] = rows[q][i].first.doc_id;
+        out_scores[out_starts[q] + i] = rows[q][i].second;
+      }
+  });
+}
+
 // ---- TermInfoStore (src/termdict/fst_termdict/term_info_store.rs)
 struct tqh_term_info_store {
   TermInfoStore store;

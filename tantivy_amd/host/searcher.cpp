@@ -565,6 +565,30 @@ std::vector<std::vector<DocAddress>> Searcher::docset_batch(const std::vector<We
   return out;
 }
 
+std::vector<std::vector<std::pair<DocAddress, Score>>> Searcher::docset_scored_batch(const std::vector<Weight> &weights) {
+  const size_t n = weights.size();
+  std::vector<std::vector<std::pair<DocAddress, Score>>> out(n);
+  std::vector<uint64_t> starts(n + 1);
+  std::vector<uint32_t> docs;
+  std::vector<float> scores;
+  for (auto &seg : segments_) {  // (segments_ is in segment_ord order: the rows stay sorted)
+    SegmentBatch b(*seg, weights, 1);
+    int rc = tq_docset_scored_batch(seg->raw(), b.qs.data(), (uint32_t)n, docs.data(), scores.data(), docs.size(), starts.data());
+    if (rc == TQ_ERR_INVALID && starts[n] > docs.size()) {  // too small: the call reported the size
+      docs.resize(starts[n]);
+      scores.resize(starts[n]);
+      rc = tq_docset_scored_batch(seg->raw(), b.qs.data(), (uint32_t)n, docs.data(), scores.data(), docs.size(), starts.data());
+    }
+    if (rc != TQ_OK) throw_tq(rc);
+    for (size_t q = 0; q < n; ++q) {
+      out[q].reserve(out[q].size() + (size_t)(starts[q + 1] - starts[q]));
+      for (uint64_t i = starts[q]; i < starts[q + 1]; ++i)
+        out[q].push_back({DocAddress{seg->segment_ord(), docs[i]}, scores[i]});
+    }
+  }
+  return out;
+}
+
 void Searcher::collect_segment_batch_device(size_t segment_ord, const std::vector<Weight> &weights,
                                             uint32_t k, float *d_scores, uint32_t *d_docs,
                                             uint32_t *d_counts, void *hip_stream) {

@@ -323,6 +323,10 @@ class Searcher {
   // docs — Weight::for_each_no_score — which merge_fruits unions into DocAddresses): per query the addresses over all
   // segments, ordered by (segment_ord, doc_id).  Flat queries only: a phrase or a nested query throws Unsupported.
   std::vector<std::vector<DocAddress>> docset_batch(const std::vector<Weight> &weights);
+  // the same for a collector whose requires_scoring() is true (Weight::for_each, weight.rs:9-18,89-97: TopDocs::tweak_score
+  // / custom_score, a MultiCollector with a scoring child): every address with its BM25 score under the searcher's
+  // index-wide statistics (tq_docset_scored_batch)
+  std::vector<std::vector<std::pair<DocAddress, Score>>> docset_scored_batch(const std::vector<Weight> &weights);
   // collect_segment for a batch on one segment: per-segment top-(offset+limit), sorted
   void collect_segment_batch(size_t segment_ord, const std::vector<Weight> &weights, uint32_t k,
                              std::vector<float> &scores, std::vector<uint32_t> &docs,

@@ -9,7 +9,12 @@ and writes 4 bytes per doc: the yardstick is 2 x the count time + docs x 4 B at 
 The parent starts one fresh child process per workload, each under its own time limit, and stops at the first that
 fails.  Per workload one JSON line; all of them go to profiles/docset_bench.json.
 
-  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3]"""
+--scores: the same batches through tq_docset_scored_batch_device as well, alternating with the unscored call in one
+process: the scored call's kernel time, the scoring pass as the difference of the two, what the byte model predicts
+for the bytes the pass adds at the fill bandwidth of the same run, and — for context — the exhaustive top-10 search of the
+same queries, the only route that scored every match before.  Written to profiles/docset_scored_bench.json.
+
+  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3] [--scores]"""
 import argparse
 import json
 import os
@@ -109,6 +114,7 @@ def child(args):
         if i >= args.warmup:
             fill.append(ev0.elapsed_time(ev1))
     lists = st["algorithmic_bytes"] - 4 * total  # lists x bitmap words x 4
+    scored = scored_run(args, O, T, seg, dev, queries, total, d_docs, d_starts, stream, float(np.median(fill))) if args.scores else {}
     k = float(np.median(ds_ms))
     res = {"workload": args.child, "docs": args.docs, "terms": args.terms, "queries": n, "out_docs": total,
            "docset_kernel_ms": round(k, 4), "docset_kernel_ms_min": round(float(np.min(ds_ms)), 4),
@@ -121,8 +127,76 @@ def child(args):
            "model_GBs": round(st["algorithmic_bytes"] / (k * 1e-3) / 1e9, 1),
            "model_frac_of_peak": round(st["algorithmic_bytes"] / (k * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
            "stage_min_docs": int(os.environ.get("TQ_DOCSET_STAGE_MIN", "2048")), "reps": args.reps, "warmup": args.warmup, "rows_checked_against_oracle": True}
+    res.update(scored)
     print("RESULT " + json.dumps(res))
     dev.close()
+
+
+def scored_run(args, O, T, seg, dev, queries, total, d_docs, d_starts, stream, fill_ms):
+    """The batch through tq_docset_scored_batch_device, alternating with the unscored call; -> the extra result fields."""
+    import torch
+
+    n = len(queries)
+    avg = seg.avg_fieldnorm
+    w_of = {}
+    for q in queries:
+        for t in q[1]:
+            if t not in w_of:
+                w_of[t] = O.bm25_for_one_term(seg.terms[t].doc_freq, seg.max_doc, avg)
+    weights = [[float(w_of[t].weight) for t in q[1]] for q in queries]
+    cache = np.array(list(w_of[queries[0][1][0]].cache), np.float32)
+    d_scores = torch.empty(max(1, total), dtype=torch.float32, device="cuda")
+    d_docs2 = torch.empty(max(1, total), dtype=torch.int32, device="cuda")
+    plain_ms, scored_ms = [], []
+    for i in range(args.warmup + args.reps):
+        rc = dev.raw_docset_device(queries, d_docs2, total, d_starts, stream=stream.cuda_stream)
+        assert rc == 0, T.binding.lib().tq_last_error()
+        a = dev.last_batch_stats()
+        rc = dev.raw_docset_scored_device(queries, d_docs, d_scores, total, d_starts, stream=stream.cuda_stream,
+                                          weights=weights, cache=cache)
+        assert rc == 0, T.binding.lib().tq_last_error()
+        b = dev.last_batch_stats()
+        if i >= args.warmup:
+            plain_ms.append(a["kernel_ms"])
+            scored_ms.append(b["kernel_ms"])
+    assert b["kernels"] == ["docset", "docset_score"] and b["matches"] == total, b
+    assert torch.equal(d_docs, d_docs2)  # the rows are the unscored call's
+    starts = d_starts.cpu().numpy()
+    n_lists = []
+    for q in range(0, n, max(1, n // 8)):  # a sample of rows against the oracle: bit-equal up to two lists, 1e-5 beyond
+        if starts[q + 1] - starts[q] > 2_000_000:
+            continue
+        if queries[q][0] == T.MODE_BOOL:
+            _, w = O.bool_match_all_c(seg, queries[q][1], queries[q][2], queries[q][3], queries[q][4])
+            n_sc = sum(1 for o in queries[q][2] if o != T.MUST_NOT)
+        else:
+            _, w = O.match_all(seg, queries[q][1], queries[q][0])
+            n_sc = len(queries[q][1])
+        got = d_scores[int(starts[q]): int(starts[q + 1])].cpu().numpy()
+        w = np.asarray(w, np.float32)
+        assert got.shape == w.shape, queries[q]
+        assert np.array_equal(got, w) if n_sc <= 2 else np.allclose(got, w, rtol=1e-5, atol=0), queries[q]
+        n_lists.append(n_sc)
+    # the exhaustive top-10 search of the same queries (tq_search_batch, option exhaustive for the call)
+    sq = [(q[0], q[1], None) + ((q[2], q[3], q[4]) if q[0] == T.MODE_BOOL else ()) for q in queries]
+    ex_ms = []
+    for i in range(1 + 3):
+        dev.raw_search(sq, weights, cache, 10, opts=(1, 0))
+        e = dev.last_batch_stats()
+        if i >= 1:
+            ex_ms.append(e["kernel_ms"])
+    p_ms, s_ms = float(np.median(plain_ms)), float(np.median(scored_ms))
+    added = int(b["algorithmic_bytes"]) - int(a["algorithmic_bytes"])  # 5 B per doc + 8 B per scoring list per 32 docs
+    fill_gbs = 4 * total / (fill_ms * 1e-3) / 1e9 if total else float("nan")
+    return {"unscored_kernel_ms": round(p_ms, 4), "scored_kernel_ms": round(s_ms, 4),
+            "scored_kernel_ms_min": round(float(np.min(scored_ms)), 4),
+            "score_pass_ms": round(s_ms - p_ms, 4),
+            "scored_algorithmic_bytes": int(b["algorithmic_bytes"]), "score_pass_added_bytes": added,
+            "score_pass_model_ms_at_fill_bw": round(added / (fill_gbs * 1e9) * 1e3, 4),
+            "scored_model_GBs": round(b["algorithmic_bytes"] / (s_ms * 1e-3) / 1e9, 1),
+            "scored_model_frac_of_peak": round(b["algorithmic_bytes"] / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            "exhaustive_top10_kernel_ms": round(float(np.median(ex_ms)), 4), "exhaustive_kernels": e["kernels"],
+            "scores_checked_against_oracle": True}
 
 
 def main():
@@ -133,15 +207,20 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=240)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "docset_bench.json"))
+    ap.add_argument("--scores", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", choices=WORKLOADS)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "docset_scored_bench.json" if args.scores else "docset_bench.json")
     if args.child:
         return child(args)
     results = []
     for wl in WORKLOADS:
         cmd = [sys.executable, os.path.abspath(__file__), "--child", wl, "--docs", str(args.docs), "--terms", str(args.terms),
                "--queries", str(args.queries), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+        if args.scores:
+            cmd.append("--scores")
         try:
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=args.step_timeout)
         except subprocess.TimeoutExpired:
