@@ -58,7 +58,13 @@
 #define TQ_AS_TIMERS 0  // region timers (tools/probe_ashare_regions.sh builds a variant with them)
 #endif
 #ifndef TQ_AS_PREFETCH
-#define TQ_AS_PREFETCH 0  // 1: the next wanted block's payload is fetched into LDS (global_load_lds) under the current block's work — measured: no gain (the chain is the doc-matrix gather), 1 KB of LDS
+// 1 (intersections only): the next wanted block's payload is fetched into LDS (global_load_lds) and its line of norm
+// bytes into a register under the current block's work; 1 KB of LDS per wave.  While stage A gathered the norm bytes
+// doc by doc this bought nothing (round 4: the chain was payload -> norm gather -> doc-matrix gather); with the norm
+// bytes in posting order the chain is payload + norm line -> doc-matrix gather and the prefetch takes its first link
+// off: headline batch, four alternating runs each — kernels 0.762 ms against 0.780 (0.795 before the norm tables),
+// step 0.909-0.931 against 0.926-0.942 (0.940-0.943 before), profiles/lnorm_ab.txt
+#define TQ_AS_PREFETCH 1
 #endif
 
 namespace {
@@ -68,11 +74,12 @@ constexpr uint32_t AS_GROUP = TQD_AS_GROUP;
 // (block, family) pairs, 64 stage-C candidates, 256 blocks decoded, 512 stage-C steps, 4096 / 8192 / 16384
 // compactions / flush selects / flushes; bytes the lanes consume (bench.py's useful_bytes): 0x100000 payload +
 // record bytes of the decoded blocks, 0x200000 fieldnorm bytes, 0x400000 doc-matrix words gathered, 0x800000
-// range-maxima bytes.  None of them changes a result.
-constexpr uint32_t AS_COUNTER_BITS = 0x7FE0u | 0xF00000u;
+// range-maxima bytes; 0x40000000 the fieldnorm bytes among those that were gathered doc by doc out of the fieldnorm file
+// (a leader without norm bytes in posting order, TermHost::lnorm_blob).  None of them changes a result.
+constexpr uint32_t AS_COUNTER_BITS = 0x7FE0u | 0xF00000u | 0x40000000u;
 
 template <bool BOOLQ>
-struct AShareLds {  // per wavefront: 4868 bytes (32 wavefronts per CU fit the 160 KB); boolean leads: + 1 KB
+struct AShareLds {  // per wavefront: 4.8 KB either way — 3.8 KB + `bw` (boolean leads) or + `pay` (intersections); 20 wavefronts per CU
   float cache[256];                            // Bm25Weight.cache of the task's queries
   uint32_t q_doc[127], q_tf[127], q_tag[127];  // survivors: doc, leader tf, lead slot | fieldnorm id << 8
   TqdALeadLds lead[AS_GROUP];                  // the leads of the task (what the scoring stage needs)
@@ -81,9 +88,7 @@ struct AShareLds {  // per wavefront: 4868 bytes (32 wavefronts per CU fit the 1
   uint32_t cnt[AS_GROUP];                      // bits 0..15: entries in the slot's staging list; 16..31: docs scored
   uint32_t flen[AS_GROUP];                     // per family head: leads in the family (itself + its twins)
   float bw[BOOLQ ? AS_GROUP * TQD_AS_MAX_TERMS : 1];  // boolean leads: what every list of the query can add to the lead's docs
-#if TQ_AS_PREFETCH
-  uint32_t pay[260];                           // the NEXT wanted block's bitpacked payload (<= 1008 B), landed by LDS-DMA
-#endif
+  uint32_t pay[(TQ_AS_PREFETCH && !BOOLQ) ? 260 : 1];  // the NEXT wanted block's bitpacked payload (<= 1008 B), landed by LDS-DMA
 };
 
 // k-th largest of the n (<= 64 R) keys held R per lane (0 = empty); n >= k
@@ -123,6 +128,7 @@ template <int KPL, bool BOOLQ, bool RD = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(TQ_BS_SGPR), amdgpu_waves_per_eu(BOOLQ ? TQ_BS_WAVES : TQ_AS_WAVES, 8))) void
 ashare_kernel(TqkAShareParams p) {
   constexpr bool USE_DPP = true;
+  constexpr bool PF = TQ_AS_PREFETCH && !BOOLQ;  // the next wanted block is fetched under the current one's work
   constexpr int R = KPL + 1;                    // staging registers per lane
   constexpr uint32_t CAPL = (uint32_t)R * 64u;  // staging entries per lead slot
   __shared__ AShareLds<BOOLQ> L;
@@ -336,11 +342,13 @@ ashare_kernel(TqkAShareParams p) {
     const bool more = alive && nt > 2u;
     const uint64_t more_m = __ballot(more);
     float w1 = ld.rest;
+    // (intersections read their queries' compact records; lists 1.. of a query of three and more lists — weights,
+    // handles — are in its full record in the side array)
     if (more_m) {
-      if (more) w1 = p.queries[q].weight[1];
+      if (more) w1 = p.xqueries[p.aqueries[q].ext].weight[1];
     }
     if (__ballot(alive && tf1 == esc)) {  // tf >= 255 (65535): block record -> packed tf
-      if (alive && tf1 == esc) tf1 = as_exact_tf(idx, p.terms, p.queries[q].term[1], pi);
+      if (alive && tf1 == esc) tf1 = as_exact_tf(idx, p.terms, p.aqueries[q].term1, pi);
     }
     if (alive) s = s + bm25(w1, norm, tf1);
     if (more_m) {  // lists 2.. of a 3+ term query: term table -> bitmap word -> tf byte, one list at a time
@@ -356,8 +364,9 @@ ashare_kernel(TqkAShareParams p) {
         }
         if (!__ballot(on)) break;  // (lanes with more lists than m are among the lanes with more than m - 1)
         if (on) {
-          const uint32_t h = p.queries[q].term[m];
-          const float wm = p.queries[q].weight[m];
+          const TqdQuery *XQ = p.xqueries + p.aqueries[q].ext;
+          const uint32_t h = XQ->term[m];
+          const float wm = XQ->weight[m];
           const TqdTerm *T = p.terms + h;
           const uint2 *dn = T->dense;
           const uint8_t *t8 = T->tf8;
@@ -452,6 +461,13 @@ ashare_kernel(TqkAShareParams p) {
     const uint32_t j0 = trec.y, nb_task = trec.z & 0xFFFFu, ci = trec.z >> 24, lead0 = trec.w;
     n_leads = (trec.z >> 16) & 0xFFu;
     const TermRef lead = load_term(p.terms, trec.x);
+    // (intersections) the leader's fieldnorm ids in posting order, 128 bytes per block (TermHost::lnorm_blob; every lead
+    // of a task has the same leader: the offset rides in the first lead's any2_lo, 0 = the list has no such table)
+    uint32_t lnorm = 0;
+    if constexpr (!BOOLQ) lnorm = sload(&p.leads[lead0].any2_lo);
+    auto norm_pair = [&](uint32_t j) __attribute__((always_inline)) -> uint32_t {  // lane l: the bytes of docs 2 l, 2 l + 1 of block j
+      return reinterpret_cast<const uint16_t *>(tbase + ((uint64_t)lnorm << 3))[(size_t)j * 64u + (uint32_t)lane];
+    };
     if (ci != cache_loaded) {
       const float *cg = p.caches + (size_t)ci * 256u;
       wave_mem_fence();
@@ -638,13 +654,14 @@ ashare_kernel(TqkAShareParams p) {
       uint64_t todo = __ballot(pass_mask != 0u);
       uint32_t since_refresh = 0;
       te(3u);
-#if TQ_AS_PREFETCH
-      // The payload of the NEXT wanted block travels to LDS (global_load_lds: one 16-byte row per lane,
+      // (PF) The payload of the NEXT wanted block travels to LDS (global_load_lds: one 16-byte row per lane,
       // no registers) while the current block's doc-matrix gathers, tests and scoring run: a block's
       // chain of dependent round trips loses its first link.
+      uint32_t npair_next = 0;  // ... and, in a register, the norm bytes of this lane's two docs of that block
       auto prefetch = [&](uint64_t rest) __attribute__((always_inline)) {
-        if (!rest) return;
+        if (!PF || !rest) return;
         const uint32_t nb2 = (uint32_t)__builtin_ctzll(rest);
+        if (lnorm) npair_next = norm_pair(i_base + nb2);
         const uint32_t meta = (uint32_t)__builtin_amdgcn_readlane((int)rec_mine.y, (int)nb2);
         const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)rec_mine.z, (int)nb2);
         if (meta == META_TAIL) return;
@@ -654,9 +671,10 @@ ashare_kernel(TqkAShareParams p) {
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(idx + lead.payload_base + off + o),
                                            (__attribute__((address_space(3))) void *)L.pay, 16, 0, 0);
       };
-      wave_mem_fence();
-      prefetch(todo);
-#endif
+      if constexpr (PF) {
+        wave_mem_fence();
+        prefetch(todo);
+      }
       while (todo) {
         const uint32_t b = (uint32_t)__builtin_ctzll(todo);
         todo &= todo - 1ull;
@@ -673,27 +691,26 @@ ashare_kernel(TqkAShareParams p) {
         const uint32_t prev_l = (uint32_t)__builtin_amdgcn_readlane((int)prev_mine, (int)b);
         const uint2 mo_l = make_uint2((uint32_t)__builtin_amdgcn_readlane((int)rec_mine.y, (int)b),
                                       (uint32_t)__builtin_amdgcn_readlane((int)rec_mine.z, (int)b));
-#if TQ_AS_PREFETCH
-        if (!lm) {  // (its families died since the pre-filter: the landed payload is dropped)
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          wave_mem_fence();
-          prefetch(todo);
-          te(4u);
-          continue;
-        }
-#else
         if (!lm) {
+          if constexpr (PF) {  // (its families died since the pre-filter: the landed payload is dropped)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wave_mem_fence();
+            prefetch(todo);
+          }
           te(4u);
           continue;
         }
-#endif
         if (p.debug & 256u) ++n_scored;  // COUNTERS
         if (p.debug & 0x100000u)
           n_scored += 16u + (mo_l.x == META_TAIL ? 8u * lead.n_tail : 16u * ((mo_l.x & 31u) + (lead.has_freq ? (mo_l.x >> 8) & 0xFFu : 0u)));
         // ---- stage A: decode the block once
         uint32_t c0, c1, t0, t1;
-#if TQ_AS_PREFETCH
+        // (the block's line of norm bytes is asked for WITH its payload: its address does not depend on the docs)
+        uint32_t npair = 0;
+        if constexpr (PF) {
+        npair = npair_next;  // (asked for under the block before; the waits below cover it)
         if (mo_l.x == META_TAIL) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           decode_docs<USE_DPP>(idx, lead, mo_l, prev_l, lane, c0, c1);
           decode_tfs(idx, lead, mo_l, lane, t0, t1);
         } else {
@@ -716,10 +733,11 @@ ashare_kernel(TqkAShareParams p) {
         }
         wave_mem_fence();  // (every lane has read its payload words: the next block's may land)
         prefetch(todo);
-#else
+        } else {
+        if (lnorm) npair = norm_pair(i_base + b);
         decode_docs<USE_DPP>(idx, lead, mo_l, prev_l, lane, c0, c1);
         decode_tfs(idx, lead, mo_l, lane, t0, t1);
-#endif
+        }
         if (TQ_AS_TIMERS && tphase == 4u && c0 == 0xFFFFFFFEu) ++n_scored;  // (the decode has to land inside the region)
         te(4u);
         tb(5u);
@@ -742,7 +760,13 @@ ashare_kernel(TqkAShareParams p) {
             block_need = nb > block_need ? nb : block_need;
           }
         }
-        const uint32_t nid0 = v0 ? fieldnorm_id(seg, c0) : 0u, nid1 = v1 ? fieldnorm_id(seg, c1) : 0u;
+        // (both docs' fieldnorm ids stay in ONE register up to the survivor queue; a lane without a doc reads the
+        // table's zero padding or 0: it never reaches the queue)
+        if (!lnorm) {  // boolean leads, a leader without the table, a segment without a fieldnorm file: one byte per doc
+          npair = (v0 ? fieldnorm_id(seg, c0) : 0u) | ((v1 ? fieldnorm_id(seg, c1) : 0u) << 8);
+          if (p.debug & 0x40000000u) n_scored += (uint32_t)(__popcll(__ballot(v0)) + __popcll(__ballot(v1)));  // COUNTERS
+        }
+        const uint32_t nid0 = npair & 0xFFu, nid1 = npair >> 8;
         const float f0 = (float)t0, f1 = (float)t1;
         const float tfn0 = f0 * __builtin_amdgcn_rcpf(f0 + L.cache[nid0]);
         const float tfn1 = f1 * __builtin_amdgcn_rcpf(f1 + L.cache[nid1]);
@@ -871,7 +895,7 @@ ashare_kernel(TqkAShareParams p) {
             if (a) {
               L.q_doc[pos] = e ? c1 : c0;
               L.q_tf[pos] = e ? t1 : t0;
-              L.q_tag[pos] = g | ((e ? nid1 : nid0) << 8) | (BOOLQ ? (e ? pb1 : pb0) << 16 : 0u);
+              L.q_tag[pos] = g | ((e ? npair >> 8 : npair & 0xFFu) << 8) | (BOOLQ ? (e ? pb1 : pb0) << 16 : 0u);
             }
             wave_mem_fence();
             qn += (uint32_t)__popcll(m);
@@ -948,7 +972,8 @@ ashare_kernel(TqkAShareParams p) {
       if (!keep_n) continue;
       // one append per member: its place in its query's result list
       uint32_t at_mine = 0;
-      if ((uint32_t)lane < fl) at_mine = p.queries[mq].part_start + atomicAdd(p.list_count + mq, keep_n);
+      if ((uint32_t)lane < fl)
+        at_mine = (BOOLQ ? p.queries[mq].part_start : p.aqueries[mq].part_start) + atomicAdd(p.list_count + mq, keep_n);
       for (uint32_t i = 0; i < fl; ++i) {
         const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)at_mine, (int)i);
         uint64_t *dst = p.lists + (size_t)at;

@@ -175,6 +175,20 @@ struct TqdALead {            // 64 bytes, written by the host planner
   // such clause).  Further clauses are verified by the scoring stage only.
   uint32_t excl_lo, excl_hi, any1_lo, any1_hi, any2_lo, any2_hi;
 };
+// What the shared-intersection launch and its merge read of a query of the intersections' group (the boolean leads
+// keep TqdQuery): built straight into the staging blob from the planner's TqdQuery records — 32 bytes per query up
+// the bus instead of 328.
+struct TqdAQuery {
+  uint32_t part_start;   // first entry of the query's result list (TqdQuery::part_start)
+  uint32_t chunk_first;  // the query whose list_count word counts that list (itself, or the identical query evaluated in its place)
+  uint32_t k;
+  uint32_t term1;        // handle of list 1 (a saturated tf byte: the packed value is read through it)
+  uint32_t n_terms;
+  uint32_t ext;          // three and more lists: index of the query's TqdQuery in the side array (term / weight of
+                         // lists 1..), 0xFFFFFFFF = none
+  uint32_t reserved[2];
+};
+static_assert(sizeof(TqdAQuery) == 32, "TqdAQuery is uploaded as raw bytes");
 struct TqdALeadLds {  // what the scoring stage keeps of a lead in LDS
   uint32_t query, info;
   float w, rest;

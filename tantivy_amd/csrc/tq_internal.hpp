@@ -124,6 +124,9 @@ struct TermHost {
   uint32_t rmax_list = 255;    // ... the largest of them
   void *flat_blob = nullptr;   // a list without a bitmap as plain arrays (doc ids | byte-wide tfs), built on
                                // first use by an unpruned union batch (tq_xunion.hip)
+  void *lnorm_blob = nullptr;  // the fieldnorm ids of the list's docs in posting order (byte i = fieldnorm[doc of
+                               // posting i], 128 bytes per block), built the first time the list LEADS queries of a
+                               // shared-intersection launch: stage A reads one line per block instead of 128 gathers
   uint32_t doc_freq = 0, n_blocks = 0, n_full = 0, n_tail = 0;
   uint32_t last_doc = 0;
   bool wants_col = true;  // false: the segment's columns are reserved for other lists
@@ -315,6 +318,7 @@ struct tq_segment {
   size_t share_span_terms = 0;  // number of terms the span was computed over
   uint64_t share_table_lo = 0;
   bool share_span_ok = true;
+  bool lnorm_off = false;  // a leader-norm table came to lie outside that span (build_lnorm): no more of them are built
   uint32_t last_batch_queries = 0;
   std::vector<uint32_t> last_query_kernel;  // option "record_query_kernels": TQ_KERNEL_* of every query of the last batch
   PinnedBuf h_stage, h_out;
@@ -482,6 +486,7 @@ struct Group {
   int kpl = 1;
   // offsets inside the staging blob
   size_t o_queries = 0, o_tiles = 0, o_outidx = 0, o_chunks = 0, o_sinks = 0;
+  size_t o_xqueries = 0;  // (shared intersections) the full records of the queries with three and more lists
   size_t o_leads = 0, o_tasks = 0, o_lists = 0;  // the extra tables of the shared, doc-major and tree groups
   void reset() {  // keeps the vectors' capacity
     queries.clear();
@@ -495,7 +500,7 @@ struct Group {
     list_entries = 0;
     max_k = 1;
     kpl = 1;
-    o_queries = o_tiles = o_outidx = o_chunks = o_sinks = 0;
+    o_queries = o_tiles = o_outidx = o_chunks = o_sinks = o_xqueries = 0;
     o_leads = o_tasks = o_lists = 0;
   }
 };
@@ -550,6 +555,7 @@ inline uint32_t group_kernel_bit(int gi, bool or_windows) {
 }
 struct RouteTotals {  // what routing a run of queries adds up besides the groups' descriptors
   uint32_t n_thr_rows = 0;
+  uint32_t n_ashare_ext = 0;  // shared intersections of three and more lists (their full records ride in a side array)
   uint64_t algo_bytes = 0;
   bool phrase_all_dense = true;  // (the phrase group may run the lean instantiation)
 };
@@ -761,6 +767,7 @@ void dense_arena_free(tq_segment *s);  // (tq_terms.cpp: the arena of the dense 
 int sync_terms(tq_segment *s, hipStream_t st);
 void mark_term_dirty(tq_segment *s, uint32_t handle);
 int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok);
+void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st);
 int order_after_last_batch(tq_segment *s, hipStream_t st);
 int wait_segment_idle(tq_segment *s);
 // must: the caller cannot run without the tables (nested boolean queries): any segment size, the least recently used

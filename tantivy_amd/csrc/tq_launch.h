@@ -68,7 +68,9 @@ struct TqkShareParams {
 struct TqkAShareParams {
   TqdSegment seg;
   const TqdTerm *terms;
-  const TqdQuery *queries;      // the launch group's queries (part_start / n_parts count list ENTRIES)
+  const TqdQuery *queries;      // boolean leads: the launch group's queries (part_start / n_parts count list ENTRIES)
+  const TqdAQuery *aqueries;    // intersections: their compact records ...
+  const TqdQuery *xqueries;     // ... and the full records of those with three and more lists (TqdAQuery::ext)
   const float *caches;
   const TqdALead *leads;
   const uint4 *tasks;           // {leader term handle, first block, n_blocks | n_leads << 16 | cache << 24, first lead}
@@ -139,7 +141,7 @@ struct TqkDenseParams {
 };
 
 struct TqkMergeParams {
-  const TqdQuery *queries;
+  const TqdQuery *queries;    // (tqk_launch_merge_lists with `compact`: TqdAQuery records)
   const uint64_t *partials;
   const uint32_t *out_index;  // query -> output row (null = identity)
   float *out_scores;
@@ -242,7 +244,8 @@ hipError_t tqk_launch_docsig_batch(const TqdSegment &seg, const TqdTerm *const *
 // ... from a decoded list (docs / tfs: n postings, ascending)
 hipError_t tqk_launch_rdir_fill(const uint32_t *docs, const uint32_t *tfs, uint32_t n, uint32_t max_doc, uint32_t *dir,
                                 uint32_t S, hipStream_t st);
-hipError_t tqk_launch_merge_lists(const TqkMergeParams &m, const uint32_t *list_count, int kpl,
+// (compact: m.queries points at TqdAQuery records — the shared intersections' group)
+hipError_t tqk_launch_merge_lists(const TqkMergeParams &m, const uint32_t *list_count, int kpl, bool compact,
                                   hipStream_t st);
 uint32_t tqk_share_capl(int kpl);  // staging entries per lead slot
 // ---- Count collector over bitmaps (tq_count.hip)
@@ -343,6 +346,9 @@ hipError_t tqk_launch_xunion(const TqkDenseParams &p, int kpl, hipStream_t st);
 // a list without a bitmap as plain arrays: doc ids and min(tf, 255) per posting
 hipError_t tqk_launch_flat_list(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle,
                                 uint32_t n_blocks, uint32_t *docs, uint8_t *tf8, hipStream_t st);
+// the fieldnorm ids of a list's docs in posting order, 128 bytes per block (TermHost::lnorm_blob; needs a fieldnorm file)
+hipError_t tqk_launch_lead_norms(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle, uint32_t n_blocks,
+                                 uint8_t *out, hipStream_t st);
 hipError_t tqk_launch_decode_list(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle,
                                   uint32_t n_blocks, uint32_t *docs, uint32_t *tfs, bool use_dpp,
                                   hipStream_t st);

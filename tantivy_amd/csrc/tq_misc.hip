@@ -289,12 +289,35 @@ __global__ void tf8_pack_kernel(const uint32_t *tfs, uint32_t n, uint8_t *out) {
   if (i < n) out[i] = (uint8_t)(tfs[i] < 255u ? tfs[i] : 255u);
 }
 
+// The fieldnorm ids of a list's docs in POSTING order (TermHost::lnorm_blob: byte i = fieldnorm[doc of posting i]; one
+// wave per 128-doc block, the vint tail through tail_docs): what stage A of the shared-intersection launch reads as
+// one 128-byte line per leader block instead of 128 gathers out of the fieldnorm file.  Bytes behind the last posting
+// of the last block are zero.
+__global__ __launch_bounds__(256) void lead_norms_kernel(TqdSegment seg, const TqdTerm *terms, uint32_t handle, uint8_t *out) {
+  const int lane = (int)__lane_id();
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const TermRef t = load_term(terms, handle);
+  const uint32_t j = blockIdx.x * 4u + wave;
+  if (j >= t.n_blocks) return;
+  uint32_t d0, d1;
+  decode_docs<true>(uni_ptr(seg.idx), t, uni_mo(t, j), block_prev_last(t, j), lane, d0, d1);
+  // (a doc id beyond the segment — a malformed list, rejected by the host — reads nothing)
+  const uint32_t n0 = d0 < seg.max_doc ? (uint32_t)seg.fieldnorm[d0] : 0u, n1 = d1 < seg.max_doc ? (uint32_t)seg.fieldnorm[d1] : 0u;
+  reinterpret_cast<uint16_t *>(out)[j * 64u + (uint32_t)lane] = (uint16_t)(n0 | (n1 << 8));
+}
+
 }  // namespace
 
 // =================================================================== launch wrappers
 hipError_t tqk_launch_tf8_pack(const uint32_t *tfs, uint32_t n, uint8_t *out, hipStream_t st) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(tf8_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tfs, n, out);
+  return hipGetLastError();
+}
+hipError_t tqk_launch_lead_norms(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle, uint32_t n_blocks,
+                                 uint8_t *out, hipStream_t st) {
+  if (n_blocks == 0 || !seg.fieldnorm) return hipSuccess;
+  hipLaunchKernelGGL(lead_norms_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, st, seg, terms, handle, out);
   return hipGetLastError();
 }
 hipError_t tqk_launch_docmat_init(uint64_t *mat, const uint8_t *fieldnorm, uint32_t const_id,

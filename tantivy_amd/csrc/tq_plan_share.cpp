@@ -435,6 +435,8 @@ int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean) {
           memcpy(&ld.any1_lo, &others, sizeof(float));
           ld.any1_hi = (ld.excl_lo || (kUseRanges && rdir)) ? t1.rmax_list : 255u;
         }
+        // (the leader's fieldnorm ids in posting order, TermHost::lnorm_blob: the boolean leads' any2 words are free here)
+        ld.any2_lo = off_of(s->terms[dq.term[0]].lnorm_blob);
         ld.k = dq.k;
         ld.thr_row = dq.thr_index;
         unsorted[lead0[q]] = ld;

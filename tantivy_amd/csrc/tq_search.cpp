@@ -65,7 +65,7 @@ void update_table_span(tq_segment *s) {
   if (s->share_span_terms == s->terms.size()) return;  // (terms are prepared rarely)
   uint64_t lo = ~0ull, hi = 0;
   for (const TermHost &th : s->terms)
-    for (const void *ptr : {th.dense_blob, th.tf8_blob, th.probe_dense_blob, th.probe_tf8_blob, th.rmax_blob, th.posdir_blob, th.probe_posdir_blob})
+    for (const void *ptr : {th.dense_blob, th.tf8_blob, th.probe_dense_blob, th.probe_tf8_blob, th.rmax_blob, th.posdir_blob, th.probe_posdir_blob, th.lnorm_blob})
       if (ptr) {
         lo = std::min<uint64_t>(lo, (uint64_t)ptr);
         hi = std::max<uint64_t>(hi, (uint64_t)ptr);
@@ -313,6 +313,16 @@ void count_leaders(Batch &b) {
                        : TQD_AND_TILE;
 }
 
+// The leaders of this batch's shared-intersection launch get their norm bytes in posting order (build_lnorm, tq_terms.cpp)
+// the first time they lead: a launch each on the batch's stream, ahead of the batch's kernels.
+void build_leader_norms(Batch &b) {
+  if (!b.ashare_and || !b.s->dseg.fieldnorm) return;
+  const PlanScratch &ps = *b.ps;
+  for (size_t h = 0; h < ps.and_lead_count.size(); ++h)
+    if (ps.and_lead_count[h] >= knobs().ashare_min && !b.s->terms[h].lnorm_blob) build_lnorm(b.s, (uint32_t)h, b.st);
+  update_table_span(b.s);  // (new tables moved it; share_span_ok decided the batch's route before they existed)
+}
+
 // One query's routing: its descriptor and the launch group it joins.
 struct Route {
   TqdQuery dq{};
@@ -409,6 +419,7 @@ void route_and(const Batch &b, uint32_t qi, Route &r, RouteTotals &t) {
     t.n_thr_rows += q.k <= 16u ? 1u : 4u;  // 64 hashed score slots for k <= 16, 256 above
     r.n_tiles = 0;
     r.group = kGAShare;
+    t.n_ashare_ext += q.n_terms > 2u ? 1u : 0u;
   } else if (!b.exhaustive && nonneg) {  // block-max bounds need weights >= 0
     dq.flags |= TQD_QF_PRUNE;
     // the shared threshold pays off on long lists only; k-th largest of 64 slots needs k <= 64
@@ -679,6 +690,7 @@ int route_in_slabs(Batch &b, uint32_t q_slabs) {
     }
     thr_base[sb + 1] = thr_base[sb] + qs[sb].t.n_thr_rows;
     b.t.algo_bytes += qs[sb].t.algo_bytes;
+    b.t.n_ashare_ext += qs[sb].t.n_ashare_ext;
     b.t.phrase_all_dense = b.t.phrase_all_dense && qs[sb].t.phrase_all_dense;
     for (int gi = 0; gi < kNGroups; ++gi) g_base[gi][sb + 1] = g_base[gi][sb] + qs[sb].groups[gi].queries.size();
   }
@@ -808,6 +820,7 @@ int plan_batch(Batch &b) {
   b.or_windows = b.s->opt.or_windows < 0 ? b.exhaustive : b.s->opt.or_windows != 0;
   if ((rc = build_flat_probe_tables(b)) != TQ_OK || (rc = build_tree_probe_tables(b)) != TQ_OK) return rc;
   count_leaders(b);
+  build_leader_norms(b);
   if ((rc = route_queries(b)) != TQ_OK) return rc;
   return plan_group_tasks(b);
 }
@@ -831,7 +844,12 @@ int lay_out_stage(Batch &b) {
   for (int gi = 0; gi < kNGroups; ++gi) {
     Group &g = b.groups[gi];
     if (g.queries.empty()) continue;
-    g.o_queries = put(16, g.queries.data(), g.queries.size() * sizeof(TqdQuery));
+    if (gi == kGAShare) {  // compact records + the full records of the queries with three and more lists: built by fill_stage
+      g.o_queries = put(16, nullptr, g.queries.size() * sizeof(TqdAQuery));
+      g.o_xqueries = put(16, nullptr, (size_t)b.t.n_ashare_ext * sizeof(TqdQuery));
+    } else {
+      g.o_queries = put(16, g.queries.data(), g.queries.size() * sizeof(TqdQuery));
+    }
     g.o_tiles = put(16, g.tile_starts.data(), g.tile_starts.size() * sizeof(uint32_t));
     g.o_outidx = put(16, g.out_index.data(), g.out_index.size() * sizeof(uint32_t));
     g.o_chunks = put(16, g.chunk_recs.data(), g.chunk_recs.size() * sizeof(uint4));
@@ -880,6 +898,28 @@ int fill_stage(Batch &b) {
       const size_t x = (c.bytes * pi / parts) & ~(size_t)63, y = pi + 1 == parts ? c.bytes : (c.bytes * (pi + 1) / parts) & ~(size_t)63;
       memcpy(hs + c.off + x, (const uint8_t *)c.src + x, y - x);
     });
+  }
+  {  // the shared intersections' queries as the launch and its merge read them (TqdAQuery)
+    const Group &g = b.groups[kGAShare];
+    TqdAQuery *aq = (TqdAQuery *)(hs + g.o_queries);
+    TqdQuery *xq = (TqdQuery *)(hs + g.o_xqueries);
+    uint32_t n_ext = 0;
+    for (size_t q = 0; q < g.queries.size(); ++q) {
+      const TqdQuery &dq = g.queries[q];
+      TqdAQuery r{};
+      r.part_start = dq.part_start;
+      r.chunk_first = dq.chunk_first;
+      r.k = dq.k;
+      r.term1 = dq.term[1];
+      r.n_terms = dq.n_terms;
+      r.ext = 0xFFFFFFFFu;
+      if (dq.n_terms > 2u) {
+        if (n_ext == b.t.n_ashare_ext) return fail(TQ_ERR_INVALID, "shared intersections: more queries of three and more lists than were routed");
+        r.ext = n_ext;
+        xq[n_ext++] = dq;
+      }
+      aq[q] = r;
+    }
   }
   for (int gi = 0; gi < kNGroups; ++gi) {
     const Group &g = b.groups[gi];
@@ -1003,6 +1043,11 @@ int launch_ashare(const Batch &b, int gi, hipStream_t gst) {
   const size_t n_a = g.queries.size();
   TqkAShareParams ap{};
   common_params(ap, b, g);
+  if (gi == kGAShare) {
+    ap.queries = nullptr;
+    ap.aqueries = (const TqdAQuery *)(b.ds + g.o_queries);
+    ap.xqueries = (const TqdQuery *)(b.ds + g.o_xqueries);
+  }
   ap.leads = (const TqdALead *)(b.ds + g.o_leads);
   ap.tasks = (const uint4 *)(b.ds + g.o_tasks);
   ap.qlists = (const uint2 *)(b.ds + g.o_lists);
@@ -1200,7 +1245,7 @@ int launch_merges(const Batch &b) {
         m.pre_slices = std::min<uint32_t>(32u, std::max<uint32_t>(2u, (uint32_t)std::sqrt((double)max_parts)));
     }
     const int rc = launched(kGroupTraits[gi].result_lists
-                                ? tqk_launch_merge_lists(m, (const uint32_t *)list_words(b.s, gi).p + g.queries.size(), g.kpl, b.st)
+                                ? tqk_launch_merge_lists(m, (const uint32_t *)list_words(b.s, gi).p + g.queries.size(), g.kpl, gi == kGAShare, b.st)
                                 : tqk_launch_merge(m, g.kpl, b.st),
                             "merge kernel");
     if (rc != TQ_OK) return rc;

@@ -380,6 +380,39 @@ int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok) {
   return TQ_OK;
 }
 
+// A leader's fieldnorm ids in posting order (TermHost::lnorm_blob) — 128 bytes per block, the tail block included, so
+// that lane l of block j reads its two docs' bytes at 128 j + 2 l.  Built like the plain arrays above: one launch on the
+// batch's stream the first time the list leads queries of a shared-intersection launch, no host synchronisation (this
+// batch's kernels follow on the same stream, later batches on other streams wait for this batch's end), counted
+// against the side tables' budget.  Over the budget, or no memory: the list stays without (stage A gathers as before).
+void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st) {
+  TermHost &t = s->terms[handle];
+  if (t.lnorm_blob || s->lnorm_off || !t.n_blocks || !t.d_self || !s->dseg.fieldnorm) return;
+  const size_t bytes = (size_t)t.n_blocks * 128u;
+  if (s->dense_bytes_total + bytes > s->dense_budget()) return;
+  void *blob = nullptr;
+  if (dense_alloc(s, bytes + PAD, &blob) != TQ_OK) {
+    (void)hipGetLastError();
+    return;
+  }
+  // (the batch has been admitted to the shared launch with the span as it is: a table outside it — an allocation of
+  // its own, far from the arena — cannot be named by a 32-bit offset)
+  if ((uint64_t)blob < s->share_table_lo + 8u || (uint64_t)blob + bytes - s->share_table_lo >= (8ull << 32)) {
+    dense_release(s, blob);
+    s->lnorm_off = true;
+    return;
+  }
+  if (tqk_launch_lead_norms(s->dseg, t.d_self, 0u, t.n_blocks, (uint8_t *)blob, st) != hipSuccess) {
+    (void)hipGetLastError();
+    dense_release(s, blob);
+    return;
+  }
+  t.lnorm_blob = blob;
+  s->dense_bytes_total += bytes;
+  s->bytes_bitmaps += bytes;
+  s->share_span_terms = ~(size_t)0;  // (the tables' address span is taken again: tq_search.cpp)
+}
+
 // Orders work about to be enqueued on `st` after the segment's previous batch, whatever stream
 // that batch ran on (no-op when it is the same stream: stream order already holds).
 int order_after_last_batch(tq_segment *s, hipStream_t st) {

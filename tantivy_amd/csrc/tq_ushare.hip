@@ -872,12 +872,13 @@ ushare_kernel(TqkShareParams p) {
 }
 
 // One wavefront per query: the query's result list (list_count entries) -> sorted top-k.
-template <int KPL>
+// QT: the group's query record — TqdQuery, or the shared intersections' TqdAQuery (k, chunk_first, part_start).
+template <int KPL, typename QT>
 __global__ __launch_bounds__(64) void merge_lists_kernel(TqkMergeParams p, const uint32_t *list_count) {
   const int lane = (int)__lane_id();
   const uint32_t q = blockIdx.x;
   if (q >= p.n_queries) return;
-  const TqdQuery *Q = uni_ptr(p.queries + q);
+  const QT *Q = uni_ptr(reinterpret_cast<const QT *>(p.queries) + q);
   const uint32_t k = uni(Q->k);
   // (chunk_first: the query that owns the list — q itself, or the identical query of the batch that was
   // evaluated in its place, build_ashare_plan)
@@ -929,13 +930,20 @@ hipError_t tqk_launch_share(const TqkShareParams &p, int kpl, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t tqk_launch_merge_lists(const TqkMergeParams &m, const uint32_t *list_count, int kpl,
+hipError_t tqk_launch_merge_lists(const TqkMergeParams &m, const uint32_t *list_count, int kpl, bool compact,
                                   hipStream_t st) {
   if (m.n_queries == 0) return hipSuccess;
   const dim3 grid(m.n_queries), block(64);
+  if (compact) {
+    switch (kpl) {
+      case 1: merge_lists_kernel<1, TqdAQuery><<<grid, block, 0, st>>>(m, list_count); break;
+      default: merge_lists_kernel<2, TqdAQuery><<<grid, block, 0, st>>>(m, list_count); break;
+    }
+    return hipGetLastError();
+  }
   switch (kpl) {
-    case 1: merge_lists_kernel<1><<<grid, block, 0, st>>>(m, list_count); break;
-    default: merge_lists_kernel<2><<<grid, block, 0, st>>>(m, list_count); break;
+    case 1: merge_lists_kernel<1, TqdQuery><<<grid, block, 0, st>>>(m, list_count); break;
+    default: merge_lists_kernel<2, TqdQuery><<<grid, block, 0, st>>>(m, list_count); break;
   }
   return hipGetLastError();
 }
