@@ -76,6 +76,11 @@ class TqSegmentStats(C.Structure):
         ("device_scratch_bytes", C.c_uint64)]
 
 
+class TqTermInfo(C.Structure):  # tq_term_info: the fields of a TermInfo as tq_term_prepare_batch takes them
+    _fields_ = [("postings_off", C.c_uint64), ("positions_off", C.c_uint64), ("postings_len", C.c_uint32),
+                ("positions_len", C.c_uint32), ("doc_freq", C.c_uint32), ("pad_", C.c_uint32)]
+
+
 class TqhTermInfo(C.Structure):
     _fields_ = [("term_id", C.c_uint32), ("doc_freq", C.c_uint32), ("postings_start", C.c_uint64),
                 ("postings_end", C.c_uint64), ("positions_start", C.c_uint64),
@@ -95,7 +100,7 @@ _lib = None
 EXPORTS = [
     "tq_init", "tq_shutdown", "tq_last_error", "tq_segment_upload", "tq_segment_upload_device",
     "tq_segment_free",
-    "tq_term_prepare", "tq_search_batch", "tq_search_batch_device", "tq_search_batch_opts",
+    "tq_term_prepare", "tq_term_prepare_batch", "tq_search_batch", "tq_search_batch_device", "tq_search_batch_opts",
     "tq_search_batch_device_opts", "tq_merge_topk",
     "tq_merge_topk_device", "tq_copy_to_host_async", "tq_decode_postings", "tq_decode_position_deltas",
     "tq_last_batch_stats", "tq_segment_get_stats", "tq_segment_reserve_columns", "tq_set_option", "tq_segment_set_alive_bitset", "tq_count_batch",
@@ -136,6 +141,7 @@ def lib():
     L.tq_segment_free.argtypes = [vp]
     L.tq_term_prepare.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                   u32p]
+    L.tq_term_prepare_batch.argtypes = [vp, C.POINTER(TqTermInfo), C.c_uint32, u32p]
     L.tq_search_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, f32p, u32p, u32p]
     L.tq_search_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, vp, vp,
                                          vp, vp]

@@ -25,6 +25,10 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_prepare.hip"),
     os.path.join(HERE, "csrc", "tq_api.cpp"),
     os.path.join(HERE, "csrc", "tq_terms.cpp"),
+    os.path.join(HERE, "csrc", "tq_term_walk.cpp"),
+    os.path.join(HERE, "csrc", "tq_term_arena.cpp"),
+    os.path.join(HERE, "csrc", "tq_term_tables.cpp"),
+    os.path.join(HERE, "csrc", "tq_term_probe.cpp"),
     os.path.join(HERE, "csrc", "tq_plan_chunks.cpp"),
     os.path.join(HERE, "csrc", "tq_plan_share.cpp"),
     os.path.join(HERE, "csrc", "tq_plan_misc.cpp"),

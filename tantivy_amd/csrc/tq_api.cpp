@@ -1,6 +1,6 @@
 // tq_api.cpp — the C ABI of include/tantivy_amd.h: contexts, segment residency, options, statistics,
 // deletes and counting, codec access, the cross-segment merge.  Compiled with hipcc.  The other entry
-// points: tq_terms.cpp (tq_term_prepare), tq_search.cpp (tq_search_batch*), tq_submit.cpp (tq_submit /
+// points: tq_terms.cpp (tq_term_prepare*), tq_search.cpp (tq_search_batch*), tq_submit.cpp (tq_submit /
 // tq_wait / tq_search_one), tq_encode.hip, tq_comm.cpp.
 #include "tq_internal.hpp"
 #include "../host/bm25.hpp"
@@ -190,7 +190,7 @@ void tq_segment_free(tq_segment *s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->batch_in_flight && s->ev_batch_done) (void)hipEventSynchronize(s->ev_batch_done);
-  for (void *slab : s->term_slabs) (void)hipFree(slab);  // (the terms' table blobs: tq_terms.cpp term_alloc)
+  for (void *slab : s->term_slabs) (void)hipFree(slab);  // (the terms' table blobs: tq_term_arena.cpp term_alloc)
   // (bitmaps, byte-wide tfs, position directories, plain lists: the arena and its overflow)
   dense_arena_free(s);
   for (void *ptr : s->dense_extra) (void)hipFree(ptr);
@@ -252,6 +252,25 @@ void tq_segment_free(tq_segment *s) {
 }
 
 }  // extern "C"
+
+namespace tqi {
+// Orders work about to be enqueued on `st` after the segment's previous batch, whatever stream
+// that batch ran on (no-op when it is the same stream: stream order already holds).
+int order_after_last_batch(tq_segment *s, hipStream_t st) {
+  if (s->batch_in_flight && s->last_stream != st)
+    HIP_TRY(hipStreamWaitEvent(st, s->ev_batch_done, 0));
+  return TQ_OK;
+}
+// Host-side wait for everything the segment has in flight (its own stream and the last batch).
+int wait_segment_idle(tq_segment *s) {
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (s->batch_in_flight) {
+    HIP_TRY(hipEventSynchronize(s->ev_batch_done));
+    s->batch_in_flight = false;
+  }
+  return TQ_OK;
+}
+}  // namespace tqi
 
 extern "C" {
 

@@ -2,7 +2,12 @@
 // (include/tantivy_amd.h): the segment and context objects, device buffers, the host planner's
 // scratch and its launch groups, the planner thread pool, and the internal entry points of
 //   tq_api.cpp          the ABI's object lifecycle, options, statistics, codec access, merges
-//   tq_terms.cpp        tq_term_prepare: skip-list unrolling, dense side tables, doc matrix
+//   tq_terms.cpp        tq_term_prepare / tq_term_prepare_batch and its stages, the device walk, term-table sync
+//   tq_term_walk.cpp    the host format walker (no HIP call: tools/planbench/walk_check.cpp), the term blob's layout
+//   tq_term_arena.cpp   term slabs, the arena of the side tables (hipMalloc or a mapped address range), directory chunks
+//   tq_term_tables.cpp  side tables of a list: tf bytes, range maxima, plain arrays, leader norms, doc matrix and
+//                       signatures, range directories, the dense lists' bitmaps
+//   tq_term_probe.cpp   the probe pool (slots, eviction) and the tables built into it
 //   tq_plan_chunks.cpp  tiles -> chunks -> launch order of the per-query kernels
 //   tq_plan_share.cpp   the term-major launches: shared unions (leads / tasks), shared intersections
 //   tq_plan_misc.cpp    the doc-major union plan, boolean query layout
@@ -110,7 +115,7 @@ struct TermHost {
                                // use ("probe_budget_x"); the other kernels do not see them
   void *probe_posdir_blob = nullptr;  // ... and its position directory (TqdTerm::pos_dir layout), built the first time
                                       // a phrase INSIDE a boolean query names the list (tq_tree.hip)
-  int32_t probe_slot = -1;            // the slot of the segment's probe pool that holds them (tq_terms.cpp), or -1
+  int32_t probe_slot = -1;            // the slot of the segment's probe pool that holds them (tq_term_probe.cpp), or -1
   // a list below "dense_ratio": its range directory (rdir_lookup, tq_common.hpp: one u32 per posting in posting order +
   // a directory of posting counts per 2^rdir_shift docs; 6-8 bytes per posting), built when the term is prepared, while
   // such tables stay within "rdir_budget_x": the shared intersection launch asks it "is d in the list, with which tf" —
@@ -259,7 +264,7 @@ struct tq_segment {
   uint32_t n_mat_slots = 0;
   TqdSegment dseg{};
   std::vector<TermHost> terms;
-  std::vector<std::pair<void *, size_t>> rdir_chunks;  // the range directories' chunks (rdir_alloc, tq_terms.cpp)
+  std::vector<std::pair<void *, size_t>> rdir_chunks;  // the range directories' chunks (rdir_alloc, tq_term_arena.cpp)
   uint8_t *rdir_chunk_cur = nullptr;
   size_t rdir_chunk_left = 0;
   bool rdir_span_ok = false;       // ... all within the 32 GB the shared launches' table offsets reach (tq_search.cpp)
@@ -762,21 +767,101 @@ struct CallOpts {
   float bound_slack;
   bool no_ashare = false, no_bshare = false;  // (internal) this call keeps intersections / boolean queries off the shared launch
 };
-// ---- tq_terms.cpp
-void dense_arena_free(tq_segment *s);  // (tq_terms.cpp: the arena of the dense lists' side tables — a hipMalloc or a mapped address range)
-int sync_terms(tq_segment *s, hipStream_t st);
-void mark_term_dirty(tq_segment *s, uint32_t handle);
-int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok);
-void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st);
+// ---- tq_api.cpp: the segment's stream
 int order_after_last_batch(tq_segment *s, hipStream_t st);
 int wait_segment_idle(tq_segment *s);
+// ---- tq_terms.cpp
+// the handle of a new term: its records appended to the host tables (the five facts every preparation path registers)
+uint32_t add_term(tq_segment *s, const TqdTerm &dt, const TermHost &th, uint64_t postings_off);
+int register_term(tq_segment *s, const TqdTerm &dt, const TermHost &th, uint64_t postings_off, tq_term_handle *out);
+int sync_terms(tq_segment *s, hipStream_t st);
+void mark_term_dirty(tq_segment *s, uint32_t handle);
+// a TermInfo's postings range lies inside the idx sub-file's body (idx_len counts its 8-byte header)
+inline bool postings_range_ok(size_t idx_len, uint64_t off, uint32_t len) {
+  return off <= idx_len - 8 && (uint64_t)len <= idx_len - 8 - off;
+}
+inline int bad_postings_range(size_t idx_len, uint64_t off, uint32_t len) {
+  return fail(TQ_ERR_FORMAT, "postings_range [%llu,+%u) outside the idx body (%zu)", (unsigned long long)off, len, idx_len - 8);
+}
+// "this list is dense enough for tables of its own" (0.25 B/doc per bitmap: worth it for lists whose 128-doc blocks
+// span few docs) ... and only while the side tables together stay within the budget (dense_fits: under the lock)
+inline size_t bitmap_words(const tq_segment *s) { return ((size_t)s->max_doc + 31) / 32 + 1; }
+inline size_t dense_table_bytes(const tq_segment *s) { return bitmap_words(s) * sizeof(uint2); }
+inline bool dense_candidate(const tq_segment *s, uint32_t doc_freq) {
+  return s->opt.dense && s->max_doc >= 4096u && (uint64_t)doc_freq * (uint64_t)s->opt.dense_ratio >= s->max_doc;
+}
+inline bool dense_fits(const tq_segment *s) { return s->dense_bytes_total + dense_table_bytes(s) <= s->dense_budget(); }
+// ---- tq_term_walk.cpp: pure host code
+struct WalkSource {  // what the walker reads of a segment
+  const uint8_t *idx;  // the idx sub-file (8-byte header + body) and the pos sub-file (pos_len 0: none)
+  size_t idx_len;
+  const uint8_t *pos;
+  size_t pos_len;
+  uint8_t record_option;
+  uint32_t max_doc;
+};
+inline WalkSource walk_source(const tq_segment *s) {
+  return {s->h_idx.data(), s->h_idx.size(), s->h_pos.data(), s->h_pos.size(), s->record_option, s->max_doc};
+}
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// A term's blob: block records (+ the terminator), coarse table, tail docs / tfs, position-block table, position
+// tail (both empty: no positions part), the term's own record — each 16-byte aligned — and PAD.
+struct TermBlobLayout {
+  size_t o_rec = 0, o_coarse = 0, o_tdocs = 0, o_ttfs = 0, o_pboff = 0, o_ptail = 0, o_self = 0, total = 0;
+};
+TermBlobLayout term_blob_layout(uint32_t n_blocks, uint32_t n_buckets, uint32_t n_tail, uint32_t n_pos_blocks, uint32_t n_pos_tail);
+// coarse[b] = first block whose last doc >= b << shift, about one block per bucket: the shift, *n_buckets
+uint32_t coarse_shift(uint32_t max_doc, uint32_t n_blocks, uint32_t *n_buckets);
+// What the host walk of one posting list leaves: the bytes of the term's blob and everything of its records but the
+// device pointers.
+struct WalkedTerm {
+  std::vector<uint8_t> hb;
+  TermBlobLayout lay;
+  TqdTerm dt{};
+  TermHost th;
+  uint64_t postings_off = 0;
+};
+int host_walk_term(const WalkSource &src, uint64_t postings_off, uint32_t postings_len, uint64_t positions_off,
+                   uint32_t positions_len, uint32_t doc_freq, WalkedTerm &w);
+void place_walked_term(WalkedTerm &w, uint8_t *blob);  // the device pointers of a walked term whose blob lives at `blob`
+const char *tqp_message(uint32_t st);
+// ---- tq_term_arena.cpp
+int term_alloc(tq_segment *s, size_t bytes, uint8_t **out);
+void term_release(tq_segment *s, uint8_t *blob, size_t bytes);
+int dense_alloc(tq_segment *s, size_t bytes, void **out);
+void dense_release(tq_segment *s, void *ptr);
+void dense_arena_free(tq_segment *s);  // (the arena of the dense lists' side tables — a hipMalloc or a mapped address range)
+int rdir_alloc(tq_segment *s, size_t bytes, void **out);
+// ---- tq_term_tables.cpp
+// A list decoded into the segment's d_misc: doc ids, term freqs, then scratch for the scans and the range maxima's
+// accumulators (null: not asked for).
+struct DecodedList {
+  uint32_t *dd = nullptr, *dt = nullptr, *scan_scratch = nullptr, *rm_acc = nullptr;
+};
+int decode_list(tq_segment *s, const TermHost &t, size_t scan_words, bool want_rm, DecodedList &dl);
+// enqueue: bitmap + rank directory of a decoded list into `blob` (validity flag: d_tp_info); its range maxima into `out`;
+// then wait and read back the flag / the list's maximum (null: not wanted)
+hipError_t enqueue_bitmap(tq_segment *s, const DecodedList &dl, uint32_t doc_freq, void *blob);
+hipError_t enqueue_rmax(tq_segment *s, const DecodedList &dl, uint32_t doc_freq, uint8_t *out);
+hipError_t finish_tables(tq_segment *s, const DecodedList &dl, uint32_t *bad, uint32_t *lmax);
+inline uint32_t rmax_list_of(uint32_t lmax) { return lmax ? std::min<uint32_t>(lmax, 255u) : 255u; }
+inline uint32_t sig_bit(uint32_t handle) { return (handle * 0x9E3779B1u) >> (32 - 4); }  // 0 .. TQD_SIG_BITS - 1
+uint32_t rdir_plan(tq_segment *s, uint32_t doc_freq);
+int attach_rdir(tq_segment *s, uint32_t handle, uint32_t S, void **tab);  // allocates the list's range directory and names it in its TermHost
+int ensure_docmat(tq_segment *s);
+int add_to_doc_signatures(tq_segment *s, uint32_t handle);
+int build_dense_device(tq_segment *s, uint32_t handle);
+int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok);
+void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st);
+void prep_apply_lmax(tq_segment *s, bool wait);    // rmax_list of lists prepared by finished tq_term_prepare_batch calls
+// ---- tq_term_probe.cpp
 // must: the caller cannot run without the tables (nested boolean queries): any segment size, the least recently used
 // slot if none is free; else: only a free slot or one idle for a while
 int build_probe_tables(tq_segment *s, uint32_t handle, bool *ok, bool must = false);
 int build_probe_posdir(tq_segment *s, uint32_t handle, bool *ok);
-void prep_apply_lmax(tq_segment *s, bool wait);    // rmax_list of lists prepared by finished tq_term_prepare_batch calls
 void probe_begin_batch(tq_segment *s);             // a new batch is being planned (the pool's clock)
 void probe_touch(tq_segment *s, uint32_t handle);  // the batch being planned uses the list's probe tables
+// ---- tq_count.cpp
 int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_counts);
 // a query as a bitwise expression over bitmap words (tq_count.cpp; checked on the CPU by tools/planbench/plan_check.cpp)
 bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool &known, uint64_t &driver_postings,
