@@ -82,6 +82,18 @@ typedef struct tq_ctx tq_ctx;
 typedef struct tq_segment tq_segment;
 typedef uint32_t tq_term_handle;
 #define TQ_TERM_ABSENT 0xFFFFFFFFu /* term not in this segment (TermInfo lookup returned None) */
+/* tq_query.terms[i] == TQ_TERM_ALL: clause i is an AllQuery (src/query/all_query.rs:23-112) — every doc below max_doc
+ * matches (the alive filter applies as everywhere) and scores weights[i], its boost: 1.0 is a bare AllScorer, anything
+ * else BoostScorer(AllScorer) (all_query.rs:24-31).  Allowed in TQ_MODE_AND (occur Must), TQ_MODE_OR (occur Should) and
+ * flat TQ_MODE_BOOL, always as a clause of its own; TQ_MODE_PHRASE: TQ_ERR_INVALID; sharing a clause_of value with
+ * another entry or inside a nested query: TQ_ERR_UNSUPPORTED.  What the query then is — BooleanWeight::complex_scorer
+ * read literally (boolean_weight.rs:114-171, 236-431, 440-456) — is decided by tq_all_query_form below (DESIGN.md
+ * "AllQuery"): EMPTY, PLAIN (the All clauses vanish without a trace, scores included: `+* +a` scores bm25(a)) or
+ * ALL-BASED (every doc, or the docs with at least min_should Should clauses, minus the MustNot lists; score = the sum
+ * of the present Should clauses + 1.0 however many All clauses there were).  A boosted All (weights[i] != 1.0) is
+ * taken by the scoring entry points only as the sole non-MustNot clause that holds anything (`*^b`, `+*^b -a`); doc
+ * sets and counts do not depend on the boost. */
+#define TQ_TERM_ALL 0xFFFFFFFEu
 
 /* One query against one segment.  Replaces the per-segment scorer tree the reference builds in
  * BooleanWeight::complex_scorer / TermWeight::specialized_scorer / PhraseWeight::phrase_scorer.
@@ -121,6 +133,25 @@ typedef struct tq_query {
                                         phrase that is a clause of its own is a clause_of group of one atom.
                                         A UNION one level further down (nested_occurs | TQ_NESTED_ANY, round 6): see above. */
 } tq_query;
+
+/* The normal form of a query with TQ_TERM_ALL clauses (pure: needs no segment; handles other than TQ_TERM_ALL /
+ * TQ_TERM_ABSENT count as present lists).  kind: TQ_ALL_EMPTY = no doc matches; TQ_ALL_PLAIN = the query is its
+ * entries in keep_mask with minimum_number_should_match = min_should, evaluated as a query without All clauses is;
+ * TQ_ALL_BASED = the doc set is every doc (min_should == 0) or the docs that hold at least min_should of the Should
+ * clauses in keep_mask, minus the MustNot lists in keep_mask, and the score is the sum of the present Should clauses
+ * + base.  keep_mask: bit i = entry i holds a list that survives (0 for TQ_ALL_EMPTY).  Returns TQ_ERR_INVALID for
+ * null arguments, a malformed query, an All clause in a phrase or a non-finite boost; TQ_ERR_UNSUPPORTED for an All
+ * clause inside a nested query or a clause_of union, and for a boosted All beside another scoring clause or a second
+ * All — `out` then still holds the doc-set form (which the boost does not change) with base = NaN.
+ * weights == NULL: every boost is 1.0. */
+enum tq_all_kind { TQ_ALL_EMPTY = 0, TQ_ALL_PLAIN = 1, TQ_ALL_BASED = 2 };
+typedef struct tq_all_form {
+  uint32_t kind;       /* enum tq_all_kind */
+  float base;          /* TQ_ALL_BASED: the score every doc of the set starts from */
+  uint32_t min_should; /* the minimum left after the Should-All clauses were counted off */
+  uint32_t keep_mask;
+} tq_all_form;
+int tq_all_query_form(const tq_query *q, tq_all_form *out);
 
 /* ---- lifecycle ---- */
 /* replaces: nothing in the reference (device bring-up).  device_ids==NULL => {0}. */
@@ -474,6 +505,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_TREE 0x1000u         /* tree_kernel (nested boolean queries over bitmap words) */
 #define TQ_KERNEL_DOCSET 0x2000u       /* docset_count / docset_write kernels (tq_docset_batch* over bitmap words) */
 #define TQ_KERNEL_DOCSET_SCORE 0x4000u /* docset_score kernel (tq_docset_scored_batch*: the scoring pass behind the write pass) */
+#define TQ_KERNEL_ALL 0x8000u          /* all_kernel (ALL-BASED queries: TQ_TERM_ALL clauses, over bitmap words) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py

@@ -36,7 +36,10 @@ typedef struct tqh_term_info {
  *       the lists' bitmaps (TQ_KERNEL_TREE); deeper trees and phrases inside boolean queries are
  *       TQ_ERR_UNSUPPORTED and stay on tantivy's CPU scorer;
  *       min_should_match as BooleanQuery::set_minimum_number_should_match —
- *       plus TQH_MODE_TERM (4) = TermQuery.  Anything else: TQ_ERR_INVALID. */
+ *       plus TQH_MODE_TERM (4) = TermQuery.  Anything else: TQ_ERR_INVALID.
+ *       terms[i] == TQ_TERM_ALL (every mode but TQ_MODE_PHRASE): the clause is an AllQuery (Query::all()), boosts[i] its
+ *       BoostQuery factor; a query of that one term is the AllQuery itself, and a one-clause BooleanQuery of it ignores
+ *       min_should_match (BooleanWeight::scorer, boolean_weight.rs:463-469).  Inside a nested query: TQ_ERR_UNSUPPORTED. */
 #define TQH_MODE_TERM 4
 typedef struct tqh_query {
   uint8_t mode;

@@ -11,6 +11,8 @@ if os.environ.get("TQ_LIB_PATH"):  # experiments: a variant build (tools/build_v
 
 TERMINATED = 0x7FFFFFFF
 TERM_ABSENT = 0xFFFFFFFF
+TERM_ALL = 0xFFFFFFFE  # TQ_TERM_ALL: the clause is an AllQuery; accepted as a term id in every query tuple, its boost in "boosts" / weights
+ALL_EMPTY, ALL_PLAIN, ALL_BASED = 0, 1, 2  # enum tq_all_kind
 MODE_AND, MODE_OR, MODE_PHRASE, MODE_BOOL, MODE_TERM = 0, 1, 2, 3, 4  # enum tq_mode + TQH_MODE_TERM
 SHOULD, MUST, MUST_NOT = 0, 1, 2  # src/query/occur.rs
 BASIC, WITH_FREQS, WITH_FREQS_AND_POSITIONS = 0, 1, 2
@@ -54,14 +56,19 @@ KERNEL_COUNT_BITMAPS = 0x800
 KERNEL_TREE = 0x1000
 KERNEL_DOCSET = 0x2000
 KERNEL_DOCSET_SCORE = 0x4000
+KERNEL_ALL = 0x8000
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
-                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score"}
+                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all"}
 
 
 def kernel_names(mask):
     return [n for b, n in sorted(KERNEL_NAMES.items()) if mask & b]
+
+
+class TqAllForm(C.Structure):  # tq_all_form
+    _fields_ = [("kind", C.c_uint32), ("base", C.c_float), ("min_should", C.c_uint32), ("keep_mask", C.c_uint32)]
 
 
 class TqSubmitStats(C.Structure):
@@ -117,6 +124,7 @@ EXPORTS = [
     "tqh_count_prepared", "tqh_searcher_add_segment_device_with_store",
     "tq_docset_batch", "tq_docset_batch_device", "tqh_docset_prepared",
     "tq_docset_scored_batch", "tq_docset_scored_batch_device", "tqh_docset_scored_prepared",
+    "tq_all_query_form",
 ]
 
 
@@ -171,6 +179,7 @@ def lib():
     L.tq_docset_scored_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, vp, vp, C.c_uint64, vp, vp]
     L.tqh_docset_scored_prepared.argtypes = [vp, u32p, u32p, f32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_last_batch_query_kernels.argtypes = [vp, u32p, C.c_uint32]
+    L.tq_all_query_form.argtypes = [C.POINTER(TqQuery), C.POINTER(TqAllForm)]
     u64p = C.POINTER(C.c_uint64)
     L.tq_encoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.tq_encoder_free.argtypes = [vp]
@@ -257,6 +266,32 @@ def bm25_for_terms(doc_freqs, total_num_docs, total_num_tokens, boost=1.0):
     _check(lib().tqh_bm25_for_terms(dfs, len(doc_freqs), int(total_num_docs), int(total_num_tokens),
                                     C.c_float(boost), C.byref(w), _f32(cache)), host=True)
     return float(w.value), cache
+
+
+def all_query_form(handles, weights=None, mode=MODE_BOOL, occurs=None, clause_of=None, min_should_match=0):
+    """tq_all_query_form: the normal form of a query with TERM_ALL clauses -> (rc, kind, base, min_should, keep_mask).
+    handles: term HANDLES (TERM_ALL, TERM_ABSENT, anything else counts as a present list); weights None = NULL."""
+    n = len(handles)
+    q = TqQuery()
+    hs = (C.c_uint32 * max(1, n))(*[int(h) for h in handles])
+    q.n_terms, q.terms, q.mode, q.k = n, C.cast(hs, C.POINTER(C.c_uint32)), int(mode), 1
+    q.min_should_match = int(min_should_match)
+    keep = [hs]
+    if weights is not None:
+        ws = (C.c_float * max(1, n))(*[float(w) for w in weights])
+        keep.append(ws)
+        q.weights = C.cast(ws, C.POINTER(C.c_float))
+    if occurs is not None:
+        oc = (C.c_uint8 * max(1, n))(*[int(o) for o in occurs])
+        keep.append(oc)
+        q.occurs = C.cast(oc, C.POINTER(C.c_uint8))
+    if clause_of is not None:
+        co = (C.c_uint8 * max(1, n))(*[int(o) for o in clause_of])
+        keep.append(co)
+        q.clause_of = C.cast(co, C.POINTER(C.c_uint8))
+    f = TqAllForm()
+    rc = lib().tq_all_query_form(C.byref(q), C.byref(f))
+    return rc, int(f.kind), float(f.base), int(f.min_should), int(f.keep_mask)
 
 
 def term_dictionary_values(field_file):
@@ -706,6 +741,8 @@ class DeviceIndex:
         return C.c_void_p(lib().tqh_segment_raw(self._s, segment_ord))
 
     def term_handle(self, term_id, segment_ord=0):
+        if int(term_id) == TERM_ALL:  # (an AllQuery clause names no list: the value is its own handle)
+            return TERM_ALL
         return lib().tqh_term_handle(self._s, segment_ord, int(term_id))
 
     def decode_postings(self, term_id, doc_freq, segment_ord=0):
@@ -885,10 +922,31 @@ class DeviceIndex:
                                                  else range(len(terms))))
                 keep.append(oa)
                 qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
+            if len(q) > 3 and q[3] is not None:  # TQ_MODE_BOOL, as raw_search takes it: occurs, clause_of, minimum
+                oc = (C.c_uint8 * len(terms))(*q[3])
+                keep.append(oc)
+                qs[i].occurs = C.cast(oc, C.POINTER(C.c_uint8))
+            if len(q) > 4 and q[4] is not None:
+                co = (C.c_uint8 * len(terms))(*q[4])
+                keep.append(co)
+                qs[i].clause_of = C.cast(co, C.POINTER(C.c_uint8))
+            if len(q) > 5:
+                qs[i].min_should_match = int(q[5])
             qs[i].k = 1
         counts = np.zeros(max(1, n), np.uint32)
         _check(lib().tq_count_batch(self.segment_raw(segment_ord), qs, n, _u32(counts)))
         return counts[:n]
+
+    def raw_search_one(self, query, weights, cache, k, segment_ord=0):
+        """Direct tq_search_one (tq_submit + tq_wait) of one query in the tuple form of _raw_flat_queries ->
+        (scores[k], docs[k], count)."""
+        qs, keep = self._raw_scored_queries([query], [weights], cache, segment_ord)
+        qs[0].k = int(k)
+        scores = np.zeros(k, np.float32)
+        docs = np.zeros(k, np.uint32)
+        count = C.c_uint32()
+        _check(lib().tq_search_one(self.segment_raw(segment_ord), qs, None, _f32(scores), _u32(docs), C.byref(count)))
+        return scores, docs, int(count.value)
 
     def raw_search(self, queries, weights, cache, k, segment_ord=0, stride=None, opts=None):
         """Direct tq_search_batch[_opts]: queries = list of (mode, [term ids], offsets|None);

@@ -14,6 +14,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_ashare.hip"),
     os.path.join(HERE, "csrc", "tq_count.hip"),
     os.path.join(HERE, "csrc", "tq_tree.hip"),
+    os.path.join(HERE, "csrc", "tq_all.hip"),
+    os.path.join(HERE, "csrc", "tq_all.cpp"),
     os.path.join(HERE, "csrc", "tq_count.cpp"),
     os.path.join(HERE, "csrc", "tq_docset.hip"),
     os.path.join(HERE, "csrc", "tq_docset.cpp"),
@@ -72,7 +74,7 @@ def csrc_hash():
 
 # which translation unit a scan kernel of a rocprofv3 trace comes from
 KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip", "union_kernel": "tq_union.hip",
-                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "tree_kernel": "tq_tree.hip", "xunion_kernel": "tq_xunion.hip",
+                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "tree_kernel": "tq_tree.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
                 "phrase_sweep_kernel": "tq_phrase.hip", "phrase_kernel": "tq_phrase.hip"}
 
 

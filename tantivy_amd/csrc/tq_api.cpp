@@ -299,6 +299,9 @@ int tq_segment_set_alive_bitset(tq_segment *s, const uint8_t *bytes, size_t len)
   HIP_TRY(hipMemcpy(s->d_alive, bytes + 4, len - 4, hipMemcpyHostToDevice));
   s->bytes_alive = len - 4;
   s->dseg.alive = s->d_alive;
+  s->alive_docs = 0;  // (what a query that matches every doc counts: tq_count_batch needs no kernel for it)
+  for (uint32_t d = 0; d + 8u <= s->max_doc; d += 8u) s->alive_docs += (uint32_t)__builtin_popcount(bytes[4 + (d >> 3)]);
+  if (s->max_doc & 7u) s->alive_docs += (uint32_t)__builtin_popcount(bytes[4 + (s->max_doc >> 3)] & ((1u << (s->max_doc & 7u)) - 1u));
   return TQ_OK;
 }
 

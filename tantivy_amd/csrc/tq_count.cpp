@@ -3,6 +3,7 @@
 // tq_count.hip (a bitwise expression per 32 docs); the others by an exhaustive scan with the smallest top-k.
 #include "tq_internal.hpp"
 
+#include <deque>
 #include <unordered_map>
 
 namespace tqi {
@@ -12,8 +13,25 @@ namespace tqi {
 // malformed input (*why says what).
 int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why) {
   fc.n_cl = fc.n_must = fc.n_should = 0;
-  fc.empty = false;
+  fc.empty = fc.all_based = fc.all_boost_mixed = false;
+  fc.msm = 0;
   *why = "";
+  if (query_has_all(q)) {  // AllQuery clauses: the clauses of what is left of the query (tq_all.cpp)
+    AllForm f;
+    const int arc = all_query_form(q, f, why);
+    if (arc != TQ_OK) return arc == TQ_ERR_UNSUPPORTED ? FLAT_UNSUPPORTED : FLAT_INVALID;
+    AllView v;
+    all_strip_view(q, f, v);
+    const int prc = parse_flat_clauses(s, v.q, fc, why);
+    if (prc != FLAT_OK) return prc;
+    for (uint32_t c = 0; c < fc.n_cl; ++c)
+      for (uint32_t i = 0; i < fc.cl[c].n; ++i) fc.cl[c].pos[i] = v.pos[fc.cl[c].pos[i]];
+    fc.all_based = f.kind == TQ_ALL_BASED;
+    fc.all_base = f.base;
+    fc.all_boost_mixed = f.boost_mixed;
+    return FLAT_OK;
+  }
+  fc.msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
   if (!q.terms || q.n_terms == 0 || q.n_terms > TQ_MAX_TERMS) return *why = "n_terms out of range (1..TQ_MAX_TERMS) or no terms", FLAT_INVALID;
   if (q.mode == TQ_MODE_PHRASE) return *why = "a phrase query", FLAT_UNSUPPORTED;
   if (q.mode > TQ_MODE_BOOL) return *why = "unknown mode", FLAT_INVALID;
@@ -81,7 +99,8 @@ bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool 
       const uint32_t h = cl[c].terms[i];
       if (!(s->terms[h].dense_blob && s->opt.use_dense) && !temp_slot.count(h) && temp_slot.size() >= max_temp) return false;
     }
-  uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
+  if (fc.all_based) return false;  // (count_batch counts these itself: never the scan)
+  uint32_t msm = fc.msm;
   if (msm > n_should) empty = true;
   bool should_is_must = false;
   if (!empty && msm >= 2) {
@@ -145,9 +164,44 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
   const uint32_t words_per_list = (n_words + 63u) & ~63u;
   const uint32_t max_temp = (uint32_t)std::min<uint64_t>(4096u, kTempBudget / ((uint64_t)words_per_list * 4u));
   std::vector<TqkCountQuery> cqs;
-  std::vector<uint32_t> bitmap_q, scan_q;
+  std::vector<uint32_t> bitmap_q, scan_q, all_q;
   std::unordered_map<uint32_t, uint32_t> temp_slot, trial;  // lists without a bitmap -> slot of the batch's scratch
+  // Queries with AllQuery clauses (tq_all.cpp): EMPTY counts 0; PLAIN is counted as its stripped view is; ALL-BASED
+  // never falls back to the scan — without a MustNot list and a minimum it counts the segment's alive docs, no kernel
+  // at all; the others go through the doc-set count pass (its expression masks the segment's last word).
+  std::deque<AllView> views;
+  std::vector<tq_query> eff;
+  std::vector<uint8_t> done;
+  const tq_query *const given = queries;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    if (!query_has_all(given[qi])) continue;
+    if (eff.empty()) {
+      eff.assign(given, given + n_queries);
+      done.assign(n_queries, 0);
+    }
+    AllForm f;
+    const char *why = "";
+    const int arc = all_query_form(given[qi], f, &why);
+    if (arc != TQ_OK) return fail(arc, "tq_count_batch: query %u: %s", qi, why);
+    views.emplace_back();
+    all_strip_view(given[qi], f, views.back());
+    eff[qi] = views.back().q;
+    if (f.kind != TQ_ALL_BASED) continue;
+    done[qi] = 1;
+    bool any_not = false;
+    for (uint32_t i = 0; i < given[qi].n_terms; ++i) {
+      if (!((f.keep_mask >> i) & 1u)) continue;
+      if (given[qi].terms[i] >= s->terms.size()) return fail(TQ_ERR_INVALID, "tq_count_batch: query %u: term handle out of range", qi);
+      any_not = any_not || (given[qi].occurs && given[qi].occurs[i] == TQ_MUST_NOT);
+    }
+    if (f.min_should == 0 && !any_not)
+      out_counts[qi] = s->d_alive ? s->alive_docs : s->max_doc;
+    else
+      all_q.push_back(qi);
+  }
+  if (!eff.empty()) queries = eff.data();
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    if (!done.empty() && done[qi]) continue;
     TqkCountQuery cq;
     bool known = false;
     uint64_t driver = 0;
@@ -233,6 +287,17 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
       algo_bytes += (uint64_t)cqs[i].n_terms * p.n_words * 4u;  // the lists' bits (the rank halves of the words ride along)
     }
     mask |= TQ_KERNEL_COUNT_BITMAPS;
+  }
+  if (!all_q.empty()) {  // ALL-BASED queries with a MustNot list or a minimum: the doc-set count pass, no doc written
+    const uint32_t n = (uint32_t)all_q.size();
+    std::vector<tq_query> qs(n);
+    for (uint32_t i = 0; i < n; ++i) qs[i] = given[all_q[i]];
+    std::vector<uint64_t> starts((size_t)n + 1u);
+    const int rc = docset_batch(s, qs.data(), n, nullptr, nullptr, 0, starts.data(), false, false, nullptr, true);
+    if (rc != TQ_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) out_counts[all_q[i]] = (uint32_t)(starts[i + 1u] - starts[i]);
+    algo_bytes += s->stats.algorithmic_bytes;
+    mask |= TQ_KERNEL_DOCSET;
   }
   s->stats.kernel_mask = mask;
   s->stats.algorithmic_bytes = algo_bytes;

@@ -18,14 +18,15 @@ int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, cons
   if (prc != FLAT_OK) return prc;
   using Clause = FlatClauses::Clause;
   // BooleanWeight::complex_scorer (boolean_weight.rs:236-431), as count_expression restates it
-  uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
-  if (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0)) {
+  uint32_t msm = fc.msm;
+  if (!fc.all_based && (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0))) {
     dq.min_should = 1;  // no lists, one Should clause wanted: the empty set
     return FLAT_OK;
   }
-  const bool should_is_must = msm >= 2 && msm == fc.n_should;  // all of them: Must clauses
+  const bool should_is_must = !fc.all_based && msm >= 2 && msm == fc.n_should;  // all of them: Must clauses
   if (should_is_must) msm = 0;
-  const bool has_must = fc.n_must > 0 || should_is_must;
+  // an ALL-BASED query (tq_all.cpp) is the expression with must = all ones: docset_word's start value
+  const bool has_must = fc.n_must > 0 || should_is_must || fc.all_based;
   uint32_t n = 0;
   auto put = [&](const Clause &c, uint32_t kind) {
     for (uint32_t i = 0; i < c.n; ++i) {
@@ -65,9 +66,9 @@ int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, cons
 void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, TqkScoreQuery &sq) {
   sq = TqkScoreQuery{};
   using Clause = FlatClauses::Clause;
-  uint32_t msm = q.mode == TQ_MODE_BOOL ? q.min_should_match : 0u;
-  if (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0)) return;  // the empty set
-  const bool should_is_must = msm >= 2 && msm == fc.n_should;
+  const uint32_t msm = fc.msm;
+  if (!fc.all_based && (fc.empty || msm > fc.n_should || (fc.n_must == 0 && fc.n_should == 0))) return;  // the empty set
+  const bool should_is_must = !fc.all_based && msm >= 2 && msm == fc.n_should;
   const Clause *must[TQ_MAX_TERMS];
   uint32_t n_must = 0;
   for (uint32_t c = 0; c < fc.n_cl; ++c)
@@ -104,6 +105,8 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
     for (uint32_t c = 0; c < fc.n_cl; ++c)
       if (fc.cl[c].occur == TQ_SHOULD && fc.cl[c].n) put(fc.cl[c]);
   sq.n_lists = n;
+  // an ALL-BASED query: the sum of the present Should clauses, then + base (a doc that no Should list holds: the base)
+  if (fc.all_based) memcpy(&sq.all_base_bits, &fc.all_base, sizeof(float));
 }
 
 namespace {
@@ -119,8 +122,8 @@ enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
 }  // namespace
 
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
-                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream) {
-  const char *const fn = scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only) {
+  const char *const fn = count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
                                 : (device_out ? "tq_docset_batch_device" : "tq_docset_batch");
   // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
   static const uint32_t kStageMin = tune_u32("TQ_DOCSET_STAGE_MIN", 2048);
@@ -155,7 +158,10 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (has_list)
       for (uint32_t i = 0; i < q.n_terms; ++i)
         if (!std::isfinite(q.weights[i])) return fail(TQ_ERR_INVALID, "%s: query %u: weight %u is not finite", fn, qi, i);
-    if (has_list) score_expression(s, q, fc, sqs[qi]);
+    if (fc.all_boost_mixed)
+      return fail(TQ_ERR_UNSUPPORTED, "%s: query %u has a boosted match-all clause beside another scoring clause or a second match-all clause: its scores stay on the CPU",
+                  fn, qi);
+    if (has_list || fc.all_based) score_expression(s, q, fc, sqs[qi]);
     if (sqs[qi].n_lists) {
       uint32_t ci = (uint32_t)caches.size();
       while (ci > 0 && caches[ci - 1] != q.tf_cache) --ci;  // (last first: neighbours share one)
@@ -349,6 +355,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   HIP_TRY(hipStreamSynchronize(st));
   const uint64_t total = out_starts[n_queries];
   s->stats.matches = total;
+  if (count_only) return TQ_OK;  // (tq_count_batch: the row starts are the counts)
   s->stats.algorithmic_bytes += (scored ? 9u : 4u) * total;
   if (total > out_cap)
     return fail(TQ_ERR_INVALID, "%s: the batch has %llu docs, out_cap is %llu (out_starts is filled: retry with that many)", fn,

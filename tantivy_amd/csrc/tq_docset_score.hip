@@ -55,7 +55,7 @@ __global__ __launch_bounds__(SC_THREADS) void docset_score_kernel(TqkScoreParams
   const uint32_t n = (uint32_t)(p.out_cap - start < (uint64_t)tile_docs ? p.out_cap - start : (uint64_t)tile_docs);
   const TqkScoreQuery *Q = p.queries + q;
   const uint32_t n_lists = sload(&Q->n_lists), access = sload(&Q->access), clause_end = sload(&Q->clause_end);
-  const uint32_t n_must_lists = sload(&Q->n_must_lists);
+  const uint32_t n_must_lists = sload(&Q->n_must_lists), all_base_bits = sload(&Q->all_base_bits);
   const float *cache = p.caches + (size_t)sload(&Q->cache_idx) * 256u;
   const TqdSegment &seg = p.seg;
   for (uint32_t base = (threadIdx.x & ~63u); base < n; base += SC_THREADS) {  // (uniform for the wavefront)
@@ -151,6 +151,8 @@ __global__ __launch_bounds__(SC_THREADS) void docset_score_kernel(TqkScoreParams
     }
     float s = n_must == 0u ? opt : (n_must == 1u ? first : (first + second) + others);
     if (n_must != 0u && n_lists > n_must_lists) s = s + opt;
+    // an ALL-BASED query: the AllScorer's share comes last (fl32(s + base)); alone it is the score
+    if (all_base_bits) s = n_lists ? s + __uint_as_float(all_base_bits) : __uint_as_float(all_base_bits);
     if (on) p.out_scores[start + j] = s;
   }
 }

@@ -299,6 +299,7 @@ struct tq_segment {
   // resident bytes by kind (tq_segment_get_stats)
   size_t bytes_term_tables = 0, bytes_bitmaps = 0, bytes_docmat = 0, bytes_posdir = 0, bytes_alive = 0;
   uint32_t n_dense_lists = 0;
+  uint32_t alive_docs = 0;  // docs below max_doc the alive bitset keeps (counted when it is set; without one: max_doc)
   std::unordered_map<uint64_t, uint32_t> term_by_off;
   // lists named by tq_segment_reserve_columns (postings_off): only they get doc-matrix columns
   std::unordered_map<uint64_t, bool> reserved_cols;
@@ -486,6 +487,7 @@ struct Group {
   std::vector<uint4> chunk_recs;      // launch order: {first tile, end tile, first query, chunk}
   std::vector<uint32_t> tile_cost;  // per query, cost units per tile
   std::vector<TqdTreeQuery> tree;   // kGTree: the nested boolean queries' descriptors (tq_tree.hip), one per query
+  std::vector<TqdAllQuery> all;     // kGAll: the ALL-BASED queries' descriptors (tq_all.hip), one per query
   uint32_t total_tiles = 0, n_chunks = 0, max_k = 1;
   uint64_t list_entries = 0;  // term-major / doc-major groups: 8-byte entries of the group's result lists
   int kpl = 1;
@@ -500,6 +502,7 @@ struct Group {
     chunk_recs.clear();
     tile_cost.clear();
     tree.clear();
+    all.clear();
     total_tiles = 0;
     n_chunks = 0;
     list_entries = 0;
@@ -545,7 +548,8 @@ enum GroupId : int {
   kGAShare = 8,    // shared intersections (leader-major for the batch, tq_ashare.hip)
   kGBShare = 9,    // boolean queries through the shared-intersection launch
   kGTree = 10,     // nested boolean queries over bitmaps (tq_tree.hip)
-  kNGroups = 11
+  kGAll = 11,      // ALL-BASED queries (TQ_TERM_ALL clauses) over bitmaps (tq_all.hip)
+  kNGroups = 12
 };
 // per group: the TQ_MODE_* of its descriptors; whether it writes result lists (part_start / n_parts count 8-byte
 // entries) rather than per-tile partials; its TQ_KERNEL_* bit (the union group's: group_kernel_bit)
@@ -554,7 +558,8 @@ constexpr GroupTraits kGroupTraits[kNGroups] = {
     {TQ_MODE_AND, false, TQ_KERNEL_AND_DENSE}, {TQ_MODE_OR, false, TQ_KERNEL_UNION}, {TQ_MODE_PHRASE, false, TQ_KERNEL_PHRASE},
     {TQ_MODE_AND, false, TQ_KERNEL_AND},       {TQ_MODE_OR, false, TQ_KERNEL_BOOL},  {TQ_MODE_OR, true, TQ_KERNEL_USHARE},
     {TQ_MODE_PHRASE, false, TQ_KERNEL_PHRASE_SWEEP}, {TQ_MODE_OR, true, TQ_KERNEL_XUNION}, {TQ_MODE_AND, true, TQ_KERNEL_ASHARE},
-    {TQ_MODE_OR, true, TQ_KERNEL_BSHARE},      {TQ_MODE_OR, false, TQ_KERNEL_TREE}};
+    {TQ_MODE_OR, true, TQ_KERNEL_BSHARE},      {TQ_MODE_OR, false, TQ_KERNEL_TREE},
+    {TQ_MODE_OR, false, TQ_KERNEL_ALL}};
 inline uint32_t group_kernel_bit(int gi, bool or_windows) {
   return gi == kGUnion && or_windows ? TQ_KERNEL_OR_WINDOWS : kGroupTraits[gi].kernel;
 }
@@ -861,6 +866,29 @@ int build_probe_tables(tq_segment *s, uint32_t handle, bool *ok, bool must = fal
 int build_probe_posdir(tq_segment *s, uint32_t handle, bool *ok);
 void probe_begin_batch(tq_segment *s);             // a new batch is being planned (the pool's clock)
 void probe_touch(tq_segment *s, uint32_t handle);  // the batch being planned uses the list's probe tables
+// ---- tq_all.cpp: AllQuery clauses (TQ_TERM_ALL), the normal form of a flat query that holds them
+inline bool query_has_all(const tq_query &q) {
+  if (!q.terms || q.n_terms > TQ_MAX_TERMS) return false;
+  for (uint32_t i = 0; i < q.n_terms; ++i)
+    if (q.terms[i] == TQ_TERM_ALL) return true;
+  return false;
+}
+struct AllForm {
+  uint32_t kind = TQ_ALL_EMPTY;  // enum tq_all_kind
+  float base = 0.0f;
+  uint32_t min_should = 0, keep_mask = 0;
+  bool boost_mixed = false;  // a boosted All beside another scoring clause or a second All: doc sets only
+};
+// TQ_OK, or TQ_ERR_INVALID / TQ_ERR_UNSUPPORTED with *why (the caller names the query)
+int all_query_form(const tq_query &q, AllForm &f, const char **why);
+struct AllView {  // the entries of keep_mask as a query of their own (borrows q's tf_cache); EMPTY: one absent Must term
+  tq_query q;
+  tq_term_handle terms[TQ_MAX_TERMS];
+  float weights[TQ_MAX_TERMS];
+  uint8_t occurs[TQ_MAX_TERMS], clause_of[TQ_MAX_TERMS];
+  uint32_t pos[TQ_MAX_TERMS];  // where entry i of the view stands in the caller's query
+};
+void all_strip_view(const tq_query &q, const AllForm &f, AllView &v);
 // ---- tq_count.cpp
 int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_counts);
 // a query as a bitwise expression over bitmap words (tq_count.cpp; checked on the CPU by tools/planbench/plan_check.cpp)
@@ -876,6 +904,10 @@ struct FlatClauses {
   Clause cl[TQ_MAX_TERMS];
   uint32_t n_cl = 0, n_must = 0, n_should = 0;  // (n_should: the Should clauses that hold a list)
   bool empty = false;                           // a Must clause without a list: no doc matches
+  uint32_t msm = 0;                             // minimum_number_should_match (a query with All clauses: what they left of it)
+  // a query with All clauses that came out ALL-BASED (tq_all.cpp): the Should and MustNot clauses above, over every doc
+  bool all_based = false, all_boost_mixed = false;
+  float all_base = 0.0f;
 };
 enum { FLAT_OK = 0, FLAT_UNSUPPORTED, FLAT_INVALID };
 int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why);
@@ -886,9 +918,10 @@ int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, cons
 // the scoring lists of the same query in summation order (weights and access paths; cache_idx is left to the caller)
 void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, TqkScoreQuery &sq);
 // out_docs / out_scores / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on
-// hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used
+// hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used;
+// count_only (host outputs): the count pass and the row starts alone, no doc is written (tq_count_batch's ALL-BASED queries)
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
-                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream);
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false);
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);

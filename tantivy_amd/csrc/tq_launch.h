@@ -214,6 +214,36 @@ struct TqkTreeParams {
 hipError_t tqk_launch_tree(const TqkTreeParams &p, int kpl, hipStream_t st);
 uint32_t tqk_tree_tiles(uint32_t n_words);
 
+// ---- ALL-BASED queries (tq_all.hip): a flat query whose AllQuery clauses (TQ_TERM_ALL) make every doc a candidate
+// (tq_all.cpp).  Lists: the Should lists in score-sum order (clause by clause, query order), then the MustNot lists.
+constexpr uint32_t TQK_ALL_TILE_WORDS = 2048;  // bitmap words (65 536 docs) per (query, tile) wavefront
+struct TqdAllQuery {              // 288 bytes
+  uint32_t n_lists, n_should;     // lists [0, n_should): Should; [n_should, n_lists): MustNot (bits only)
+  uint32_t clause_end;            // bit t: Should list t is the last of its clause (a clause counts once and sums first)
+  uint32_t min_should;            // 0: every doc; m >= 1: the docs that hold at least m Should clauses (m <= 15)
+  uint32_t base_bits;             // (float) what every doc of the set scores before its Should clauses: 1.0, or the sole All's boost
+  uint32_t k, cache_idx;
+  uint32_t part_start;            // first partial top-k list (one per scanned tile)
+  uint32_t n_tiles;               // tiles the query scans: the segment's, or — no list, no alive bitset — the ceil(k / 65 536) first
+  uint32_t extra_matches;         // docs of the tiles it does not scan (they all match)
+  uint32_t pad_[2];
+  uint32_t dense_off[TQD_MAX_TERMS];    // bitmap + rank directory / byte-wide tfs of the list, as offsets from
+  uint32_t tf8_off[TQD_MAX_TERMS];      // TqkAllParams::table_base in 8-byte units
+  uint32_t weight_bits[TQD_MAX_TERMS];  // (float) idf * (1 + k1) * boost
+  uint32_t handle[TQD_MAX_TERMS];       // term handle (saturated tf bytes read the packed value)
+};
+struct TqkAllParams {
+  TqdSegment seg;
+  const TqdTerm *terms;
+  const TqdAllQuery *queries;
+  const float *caches;
+  const TqkSinks *sinks;
+  const uint8_t *table_base;
+  uint32_t n_queries, n_words, max_tiles;  // max_tiles: the most tiles a query of the launch scans
+};
+hipError_t tqk_launch_all(const TqkAllParams &p, int kpl, hipStream_t st);
+uint32_t tqk_all_tiles(uint32_t n_words);
+
 hipError_t tqk_launch_and(const TqkScanParams &p, int kpl, bool use_dpp, hipStream_t st);
 hipError_t tqk_launch_or(const TqkScanParams &p, int kpl, bool use_dpp, hipStream_t st);
 hipError_t tqk_launch_phrase(const TqkScanParams &p, int kpl, bool use_dpp, hipStream_t st);
@@ -318,7 +348,8 @@ struct TqkScoreQuery {             // 472 bytes: every non-MustNot list of the q
   uint32_t clause_end;             // bit m: list m is the last of its clause (a clause = the sum of its present lists)
   uint32_t n_must_lists;           // lists [0, n_must_lists): the Must clauses, cheapest first (Intersection::score: first +
                                    // second + the sum of the others); behind them the Should clauses (req + opt, or the union)
-  uint32_t pad_;
+  uint32_t all_base_bits;          // an ALL-BASED query (TQ_TERM_ALL clauses, tq_all.cpp): the float added LAST to the sum of the
+                                   // present Should clauses — a doc that no list holds scores it; 0 = not such a query
   uint32_t handle[TQD_MAX_TERMS];  // term record (exact tfs of saturated entries, the block search)
   float weight[TQD_MAX_TERMS];
   uint32_t shift[TQD_MAX_TERMS];

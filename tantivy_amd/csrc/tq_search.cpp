@@ -41,6 +41,7 @@ struct Batch {
   size_t terms_from = 0, terms_to = 0;  // term records appended to the device table through the staging blob
   std::vector<const float *> caches;    // the Bm25Weight caches, in order of first use (PlanScratch::q_cache)
   uint32_t n_union_queries = 0, n_bool_queries = 0, n_sparse2 = 0;
+  uint32_t n_all_queries = 0;  // ALL-BASED queries (TQ_TERM_ALL clauses that make every doc a candidate): counted by strip_all_clauses
   bool and_probe = false, ashare_on = false, ashare_and = false;
   uint32_t and_tile_cap = TQD_AND_TILE, dense_min_queries = 1;
   uint64_t unique_bytes = 0, dense_ratio = 0;
@@ -228,6 +229,30 @@ int build_tree_probe_tables(Batch &b) {
   return TQ_OK;
 }
 
+// ALL-BASED queries (tq_all.hip) reach every list through a bitmap too: the MustNot lists for their bits, the Should
+// lists for bits, rank and tf bytes.  The probe pool's tables, no new kind.
+int build_all_probe_tables(Batch &b) {
+  if (!b.n_all_queries || !b.s->opt.use_dense || !b.s->opt.dense || b.s->opt.probe_budget_x <= 0) return TQ_OK;
+  bool built = false;
+  for (uint32_t qi = 0; qi < b.n_queries; ++qi) {
+    const tq_query &q = b.queries[qi];
+    if (!query_has_all(q)) continue;
+    for (uint32_t i = 0; i < q.n_terms; ++i) {
+      const uint32_t h = q.terms[i];
+      if (h >= b.s->terms.size()) continue;  // (All, absent, or reported by plan_query)
+      const TermHost &th = b.s->terms[h];
+      if (th.dense_blob && th.tf8_blob) continue;
+      const bool had = th.probe_dense_blob && th.probe_tf8_blob;
+      bool ok = false;
+      const int prc = build_probe_tables(b.s, h, &ok, true);
+      if (prc != TQ_OK) return prc;
+      built = built || (ok && !had);
+    }
+  }
+  if (built) b.s->share_span_terms = ~(size_t)0;
+  return TQ_OK;
+}
+
 // Which list would lead an AND query in the shared-intersection launch (0xFFFFFFFF: the query does not qualify).
 uint32_t ashare_leader(const Batch &b, const tq_query &q, uint32_t cache_idx) {
   if (q.mode != TQ_MODE_AND || q.n_terms < 2 || q.n_terms > TQD_AS_MAX_TERMS || q.k == 0 || q.k > 128u ||
@@ -353,7 +378,7 @@ int check_query(const Batch &b, uint32_t qi) {
     if (!std::isfinite(q.weights[i]))
       return fail(TQ_ERR_INVALID, "query %u: weight %u is not finite", qi, i);
   for (uint32_t i = 0; i < q.n_terms; ++i)
-    if (q.terms[i] != TQ_TERM_ABSENT && q.terms[i] >= b.s->terms.size())
+    if (q.terms[i] != TQ_TERM_ABSENT && q.terms[i] != TQ_TERM_ALL && q.terms[i] >= b.s->terms.size())
       return fail(TQ_ERR_INVALID, "query %u: unknown term handle %u", qi, q.terms[i]);
   return TQ_OK;
 }
@@ -489,6 +514,59 @@ int route_tree(const Batch &b, uint32_t qi, Route &r, Group &tree_group) {
   r.dq.n_terms = tq.n_terms;
   r.n_tiles = 0;
   r.group = kGTree;
+  return TQ_OK;
+}
+
+// A query whose AllQuery clauses make every doc a candidate (tq_all.cpp: ALL-BASED; strip_all_clauses has replaced the
+// EMPTY and PLAIN ones by their views): the Should lists in score-sum order, then the MustNot lists, over bitmaps.
+int route_all(const Batch &b, uint32_t qi, Route &r, Group &all_group) {
+  const tq_query &q = b.queries[qi];
+  FlatClauses fc;
+  const char *why = "";
+  const int prc = parse_flat_clauses(b.s, q, fc, &why);
+  if (prc != FLAT_OK) return fail(prc == FLAT_UNSUPPORTED ? TQ_ERR_UNSUPPORTED : TQ_ERR_INVALID, "query %u: %s", qi, why);
+  TqdAllQuery aq{};
+  aq.k = q.k;
+  aq.cache_idx = r.dq.cache_idx;
+  aq.min_should = fc.msm;
+  memcpy(&aq.base_bits, &fc.all_base, sizeof(float));
+  if (aq.min_should > 15u) return fail(TQ_ERR_UNSUPPORTED, "query %u: minimum_number_should_match above 15", qi);
+  uint32_t n = 0;
+  for (uint32_t pass = 0; pass < 2; ++pass) {
+    for (uint32_t c = 0; c < fc.n_cl; ++c) {
+      const FlatClauses::Clause &C = fc.cl[c];
+      if (C.occur != (pass == 0 ? (uint32_t)TQ_SHOULD : (uint32_t)TQ_MUST_NOT)) continue;
+      for (uint32_t i = 0; i < C.n; ++i) {
+        const TermHost &th = b.s->terms[C.terms[i]];
+        const bool own = th.dense_blob && th.tf8_blob;
+        const void *bm = own ? th.dense_blob : th.probe_dense_blob, *t8 = own ? th.tf8_blob : th.probe_tf8_blob;
+        if (!b.s->share_span_ok || !b.s->opt.use_dense || !bm || !t8)
+          return fail(TQ_ERR_UNSUPPORTED,
+                      "query %u: a query with a match-all clause names a list without a bitmap (options \"dense\" / \"use_dense\" / \"probe_budget_x\" off, "
+                      "a list whose tables did not fit \"dense_budget_x\", or the tables span more than 32 GB)", qi);
+        aq.dense_off[n] = (uint32_t)(((uint64_t)bm - b.s->share_table_lo) >> 3);
+        aq.tf8_off[n] = (uint32_t)(((uint64_t)t8 - b.s->share_table_lo) >> 3);
+        memcpy(&aq.weight_bits[n], &q.weights[C.pos[i]], sizeof(float));
+        aq.handle[n] = C.terms[i];
+        if (pass == 0 && i + 1 == C.n) aq.clause_end |= 1u << n;
+        ++n;
+      }
+    }
+    if (pass == 0) aq.n_should = n;
+  }
+  aq.n_lists = n;
+  // Without a list and without deletes the top-k is the first k docs: their tiles alone; the other docs are counted here.
+  const uint32_t n_words = (b.s->max_doc + 31u) / 32u, tiles = tqk_all_tiles(n_words);
+  aq.n_tiles = tiles;
+  if (n == 0 && !b.s->d_alive) aq.n_tiles = std::min<uint32_t>(tiles, (q.k + TQK_ALL_TILE_WORDS * 32u - 1u) / (TQK_ALL_TILE_WORDS * 32u));
+  const uint64_t scanned_docs = std::min<uint64_t>(b.s->max_doc, (uint64_t)aq.n_tiles * TQK_ALL_TILE_WORDS * 32u);
+  aq.extra_matches = (uint32_t)(b.s->max_doc - scanned_docs);
+  r.qbytes += (scanned_docs + 31u) / 32u * (8ull * n + (b.s->d_alive ? 4u : 0u));  // the HBM model of tq_all.hip
+  all_group.all.push_back(aq);
+  r.dq.n_terms = n;
+  r.dq.n_parts = aq.n_tiles;
+  r.n_tiles = 0;
+  r.group = kGAll;
   return TQ_OK;
 }
 
@@ -637,7 +715,9 @@ int plan_query(const Batch &b, uint32_t qi, Group *groups, RouteTotals &t) {
   r.dq.cache_idx = b.ps->q_cache[qi];
   r.qbytes = 8ull * q.k;
   const bool any_absent = std::find(q.terms, q.terms + q.n_terms, TQ_TERM_ABSENT) != q.terms + q.n_terms;
-  if (q.mode == TQ_MODE_BOOL) {
+  if (b.n_all_queries && query_has_all(q)) {
+    rc = route_all(b, qi, r, groups[kGAll]);
+  } else if (q.mode == TQ_MODE_BOOL) {
     rc = bool_query_is_tree(q) ? route_tree(b, qi, r, groups[kGTree]) : route_bool(b, qi, r, t);
   } else if (q.mode == TQ_MODE_OR || (q.mode == TQ_MODE_AND && q.n_terms == 1 && !any_absent)) {
     rc = route_union(b, qi, r, groups, t);
@@ -703,6 +783,7 @@ int route_in_slabs(Batch &b, uint32_t q_slabs) {
     g.out_index.resize(total);
     for (uint32_t sb = 0; sb < q_slabs; ++sb) g.max_k = std::max(g.max_k, qs[sb].groups[gi].max_k);
     for (uint32_t sb = 0; sb < q_slabs; ++sb) g.tree.insert(g.tree.end(), qs[sb].groups[gi].tree.begin(), qs[sb].groups[gi].tree.end());
+    for (uint32_t sb = 0; sb < q_slabs; ++sb) g.all.insert(g.all.end(), qs[sb].groups[gi].all.begin(), qs[sb].groups[gi].all.end());
   }
   parallel_slabs(q_slabs, [&](uint32_t sb) {
     for (int gi = 0; gi < kNGroups; ++gi) {
@@ -777,6 +858,12 @@ int plan_group_tasks(Batch &b) {
       g.n_chunks = g.total_tiles = (uint32_t)g.queries.size() * tiles;
       continue;
     }
+    if (gi == kGAll) {  // one partial list per (query, scanned tile): route_all set n_parts
+      g.kpl = kpl_for(g.max_k);
+      for (const TqdQuery &dq : g.queries) g.total_tiles += dq.n_parts;
+      g.n_chunks = g.total_tiles;
+      continue;
+    }
     const int rc = gi == kGUShare   ? build_share_plan(b.s, g, ps)
                    : gi == kGAShare ? build_ashare_plan(b.s, g, ps, false)
                    : gi == kGBShare ? build_ashare_plan(b.s, g, ps, true)
@@ -807,6 +894,8 @@ int plan_group_tasks(Batch &b) {
   }
   Group &tree = b.groups[kGTree];
   for (size_t i = 0; i < tree.tree.size(); ++i) tree.tree[i].part_start = tree.queries[i].part_start;
+  Group &all = b.groups[kGAll];
+  for (size_t i = 0; i < all.all.size(); ++i) all.all[i].part_start = all.queries[i].part_start;
   return TQ_OK;
 }
 
@@ -818,7 +907,7 @@ int plan_batch(Batch &b) {
   if (rc != TQ_OK) return rc;
   look_at_queries(b);
   b.or_windows = b.s->opt.or_windows < 0 ? b.exhaustive : b.s->opt.or_windows != 0;
-  if ((rc = build_flat_probe_tables(b)) != TQ_OK || (rc = build_tree_probe_tables(b)) != TQ_OK) return rc;
+  if ((rc = build_flat_probe_tables(b)) != TQ_OK || (rc = build_tree_probe_tables(b)) != TQ_OK || (rc = build_all_probe_tables(b)) != TQ_OK) return rc;
   count_leaders(b);
   build_leader_norms(b);
   if ((rc = route_queries(b)) != TQ_OK) return rc;
@@ -864,6 +953,8 @@ int lay_out_stage(Batch &b) {
       g.o_lists = put(16, A.alists.data(), gi == kGBShare ? A.alists.size() * sizeof(uint2) : 0);
     } else if (gi == kGTree) {  // (o_leads: the tree descriptors)
       g.o_leads = put(64, g.tree.data(), g.tree.size() * sizeof(TqdTreeQuery));
+    } else if (gi == kGAll) {  // (o_leads: the ALL-BASED descriptors)
+      g.o_leads = put(64, g.all.data(), g.all.size() * sizeof(TqdAllQuery));
     } else if (gi == kGXUnion) {  // (o_leads: the rows, o_tasks: the queries)
       g.o_leads = put(64, ps.xrows.data(), ps.xrows.size() * sizeof(TqkDenseRow));
       g.o_tasks = put(16, ps.xqueries.data(), ps.xqueries.size() * sizeof(TqkDenseQuery));
@@ -1128,6 +1219,22 @@ int launch_tree(const Batch &b, hipStream_t gst) {
   return launched(tqk_launch_tree(tp, g.kpl, gst), "nested boolean");
 }
 
+// The ALL-BASED queries over bitmap words.
+int launch_all(const Batch &b, hipStream_t gst) {
+  const Group &g = b.groups[kGAll];
+  TqkAllParams ap{};
+  ap.seg = b.s->dseg;
+  ap.terms = b.s->d_terms;
+  ap.queries = (const TqdAllQuery *)(b.ds + g.o_leads);
+  ap.caches = (const float *)(b.ds + b.o_caches);
+  ap.sinks = (const TqkSinks *)(b.ds + g.o_sinks);
+  ap.table_base = (const uint8_t *)b.s->share_table_lo;
+  ap.n_queries = (uint32_t)g.queries.size();
+  ap.n_words = (b.s->max_doc + 31u) / 32u;
+  for (const TqdAllQuery &aq : g.all) ap.max_tiles = std::max(ap.max_tiles, aq.n_tiles);
+  return launched(tqk_launch_all(ap, g.kpl, gst), "match-all");
+}
+
 // The doc-major union launch.
 int launch_xunion(const Batch &b, hipStream_t gst) {
   const PlanScratch &ps = *b.ps;
@@ -1204,12 +1311,13 @@ int launch_groups(Batch &b) {
   for (int gi = 0; main_group < 0 && gi < kNGroups; ++gi)
     if (!groups[gi].queries.empty()) main_group = gi;
   // long serial chains first
-  for (const int gi : {kGAnd, kGBool, kGBShare, kGUShare, kGXUnion, kGTree, kGUnion, kGPhrase, kGPhSweep, kGAndDense, kGAShare}) {
+  for (const int gi : {kGAnd, kGBool, kGBShare, kGUShare, kGXUnion, kGTree, kGAll, kGUnion, kGPhrase, kGPhSweep, kGAndDense, kGAShare}) {
     if (groups[gi].queries.empty()) continue;
     const hipStream_t gst = (fork && gi != main_group) ? b.s->side_stream : b.st;
     const int rc = gi == kGAShare || gi == kGBShare ? launch_ashare(b, gi, gst)
                    : gi == kGUShare                ? launch_ushare(b, gst)
                    : gi == kGTree                  ? launch_tree(b, gst)
+                   : gi == kGAll                   ? launch_all(b, gst)
                    : gi == kGXUnion                ? launch_xunion(b, gst)
                                                    : launch_scan(b, gi, gst);
     if (rc != TQ_OK) return rc;
@@ -1321,6 +1429,36 @@ struct DrainOnError {
   }
 };
 
+// Queries with AllQuery clauses (TQ_TERM_ALL) before anything is planned: the normal form of tq_all.cpp decides each —
+// EMPTY and PLAIN ones are replaced by their stripped views (today's kernels see a query without All clauses, and a
+// PLAIN query's rows are that query's, bit for bit), ALL-BASED ones stay as they are for route_all.  A batch without
+// such a clause is not copied.
+struct AllStrip {
+  std::vector<tq_query> eff;
+  std::deque<AllView> views;  // (a deque: the views' arrays stay where they are)
+  uint32_t n_all_based = 0;
+};
+int strip_all_clauses(const tq_query *queries, uint32_t n_queries, AllStrip &st) {
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    if (!query_has_all(queries[qi])) continue;
+    AllForm f;
+    const char *why = "";
+    const int rc = all_query_form(queries[qi], f, &why);
+    if (rc != TQ_OK) return fail(rc, "query %u: %s", qi, why);
+    if (f.boost_mixed)
+      return fail(TQ_ERR_UNSUPPORTED, "query %u has a boosted match-all clause beside another scoring clause or a second match-all clause: its scores stay on the CPU", qi);
+    if (f.kind == TQ_ALL_BASED) {
+      ++st.n_all_based;
+      continue;
+    }
+    if (st.eff.empty()) st.eff.assign(queries, queries + n_queries);
+    st.views.emplace_back();
+    all_strip_view(queries[qi], f, st.views.back());
+    st.eff[qi] = st.views.back().q;
+  }
+  return TQ_OK;
+}
+
 // The pinned rows of a host-output batch: scores | docs | counts, each 256-byte aligned; returns the total bytes.
 size_t host_rows_layout(uint32_t n_queries, uint32_t out_stride, size_t &o_docs, size_t &o_counts) {
   const size_t n = (size_t)n_queries * out_stride;
@@ -1337,12 +1475,18 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
   if (!s || (!queries && n_queries) || !d_out_scores || !d_out_docs || !d_out_counts)
     return fail(TQ_ERR_INVALID, "tq_search_batch: null argument");
   if (n_queries == 0) return TQ_OK;
+  AllStrip strip;
+  int rc = strip_all_clauses(queries, n_queries, strip);
+  if (rc != TQ_OK) return rc;
+  if (!strip.eff.empty()) queries = strip.eff.data();
   Batch b{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, co};
-  int rc = plan_batch(b);
+  b.n_all_queries = strip.n_all_based;
+  rc = plan_batch(b);
   // a shared launch's result lists over the budget even with the longest tasks: the same batch again, that family
   // through the per-query kernels
   while (rc != TQ_OK && b.replan) {
     b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co};
+    b.n_all_queries = strip.n_all_based;
     rc = plan_batch(b);
   }
   if (rc != TQ_OK) return rc;

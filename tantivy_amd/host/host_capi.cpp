@@ -209,6 +209,7 @@ static Query build_query(const tqh_query &q) {
       return q.nested_occurs && q.nested_occurs[tt] != 255 && (q.nested_occurs[tt] & TQ_NESTED_PHRASE) != 0;
     };
     auto leaf_of = [&](uint32_t tt) {
+      if (q.terms[tt] == TQ_TERM_ALL) return Query::all().boosted(q.boosts ? q.boosts[tt] : 1.0f);  // an AllQuery clause
       if (in_phrase(tt))  // (the phrase's first term: the others are appended to phrase_terms below)
         return Query::phrase_with_offsets({{q.phrase_offsets ? q.phrase_offsets[tt] : 0u, q.terms[tt]}}).boosted(q.boosts ? q.boosts[tt] : 1.0f);
       return Query::term_query(q.terms[tt]).boosted(q.boosts ? q.boosts[tt] : 1.0f);
@@ -290,6 +291,8 @@ static Query build_query(const tqh_query &q) {
         }
     query = Query::boolean(std::move(clauses));
     query.set_minimum_number_should_match(q.min_should_match);
+  } else if (q.n_terms == 1 && q.mode != TQ_MODE_PHRASE && q.terms[0] == TQ_TERM_ALL) {
+    query = Query::all().boosted(q.boosts ? q.boosts[0] : 1.0f);
   } else if (q.mode == TQH_MODE_TERM || (q.n_terms == 1 && q.mode != TQ_MODE_PHRASE)) {
     query = Query::term_query(q.terms[0]).boosted(q.boosts ? q.boosts[0] : 1.0f);
   } else if (q.mode == TQ_MODE_PHRASE) {
@@ -304,7 +307,7 @@ static Query build_query(const tqh_query &q) {
     std::vector<std::pair<Occur, Query>> clauses;
     for (uint32_t t = 0; t < q.n_terms; ++t)
       clauses.emplace_back(q.mode == TQ_MODE_AND ? Occur::Must : Occur::Should,
-                           Query::term_query(q.terms[t]).boosted(q.boosts ? q.boosts[t] : 1.0f));
+                           (q.terms[t] == TQ_TERM_ALL ? Query::all() : Query::term_query(q.terms[t])).boosted(q.boosts ? q.boosts[t] : 1.0f));
     query = Query::boolean(std::move(clauses));
   }
   return query;
@@ -333,7 +336,9 @@ static void prepare_into(tqh_searcher *s, const tqh_query *queries, uint32_t n, 
     const tqh_query &q = queries[i];
     // unboosted all-Must / all-Should term clauses (what a query parser makes of `+a +b` / `a b c`): the weight
     // without the detour through a Query tree — the same f32 arithmetic as Searcher::weight
-    if ((q.mode == TQ_MODE_AND || q.mode == TQ_MODE_OR) && !q.boosts && q.n_terms >= 1 && q.terms) {
+    bool any_all = false;  // (an AllQuery clause is no term: the Query tree knows it)
+    for (uint32_t t = 0; q.terms && t < q.n_terms; ++t) any_all = any_all || q.terms[t] == TQ_TERM_ALL;
+    if ((q.mode == TQ_MODE_AND || q.mode == TQ_MODE_OR) && !q.boosts && q.n_terms >= 1 && q.terms && !any_all) {
       if (!fc.cache) fc = s->searcher->flat_context();
       s->searcher->weight_flat_into(fc, q.mode, q.terms, q.n_terms, out[i]);
     } else {

@@ -61,6 +61,7 @@ const TermInfo *SegmentReader::get_term_info(uint32_t term_id) const {
   return &it->second;
 }
 tq_term_handle SegmentReader::term_handle(uint32_t term_id) {
+  if (term_id == TQ_TERM_ALL) return TQ_TERM_ALL;  // an AllQuery clause names no list: the value passes through
   if (term_id < kFastHandles) {  // (the table exists from the first prepared term on)
     std::atomic<tq_term_handle> *fast = fast_handles_.load(std::memory_order_acquire);
     if (fast) {
@@ -105,6 +106,7 @@ void SegmentReader::prepare_terms(const uint32_t *term_ids, size_t n) {
     std::unordered_map<uint32_t, char> seen;
     for (size_t i = 0; i < n; ++i) {
       const uint32_t t = term_ids[i];
+      if (t == TQ_TERM_ALL) continue;
       if (t < kFastHandles && fast && fast[t].load(std::memory_order_acquire) != kHandleUnknown) continue;
       if (!seen.emplace(t, 1).second) continue;
       {
@@ -258,6 +260,11 @@ Weight Searcher::weight(const Query &query) const {
     return boost_by(idf(doc_freq(term), nd) * (1.0f + K1), boost);
   };
   switch (query.kind) {
+    case Query::All:  // AllWeight::scorer (all_query.rs:24-31): AllScorer, under a BoostScorer when boost != 1
+      w.mode = TQ_MODE_OR;
+      w.terms = {(uint32_t)TQ_TERM_ALL};
+      w.weights = {b0};
+      return w;
     case Query::Term:
       // TermWeight::for_each_pruning == one-scorer block-WAND == every doc of the list
       w.mode = TQ_MODE_OR;
@@ -285,6 +292,13 @@ Weight Searcher::weight(const Query &query) const {
       // Intersection / RequiredOptionalScorer / Exclude / Disjunction on the union kernel.
       if (query.clauses.empty())
         throw TantivyError(TantivyError::Unsupported, "empty boolean query");
+      // BooleanWeight::scorer (boolean_weight.rs:463-469): a one-clause query is its clause's scorer, whatever
+      // minimum_number_should_match says (a MustNot clause alone: the EmptyScorer, which the device finds itself)
+      if (query.clauses.size() == 1 && query.clauses[0].second.kind == Query::All && query.clauses[0].first != Occur::MustNot) {
+        Query only = query.clauses[0].second;
+        only.boost *= b0;
+        return weight(only);
+      }
       // A Must clause that is itself a BooleanQuery with at least one Must term (`+a +(+b +c)`,
       // `+a +(+b -c)`, `+a +(+b c)`) is an Intersection of the parent's required scorers with the
       // nested query's scorer (boolean_weight.rs:308-431): the same doc set and the same score
@@ -365,6 +379,7 @@ Weight Searcher::weight(const Query &query) const {
         if (c.second.kind == Query::Phrase) {
           any_phrase = tree = true;
           flat = false;
+        } else if (c.second.kind == Query::All) {  // (a clause of its own, like a term: TQ_TERM_ALL)
         } else if (c.second.kind != Query::Term) {
           if (!is_query_of_terms(c.second))
             throw TantivyError(TantivyError::Unsupported,
@@ -429,7 +444,18 @@ Weight Searcher::weight(const Query &query) const {
             w.atom_of.push_back(member);
           }
         };
-        if (c.second.kind == Query::Term) {
+        if (c.second.kind == Query::All) {  // weights[i] = the boost, which is the score every doc gets
+          w.terms.push_back((uint32_t)TQ_TERM_ALL);
+          w.weights.push_back(bc);
+          if (w.mode == TQ_MODE_BOOL) {
+            w.occurs.push_back(oc);
+            w.clause_of.push_back(clause);
+            if (tree) {
+              w.nested_occurs.push_back((uint8_t)TQ_MUST);
+              w.atom_of.push_back(member);
+            }
+          }
+        } else if (c.second.kind == Query::Term) {
           add(c.second.term, bc, Occur::Must);  // (a one-term clause: the term itself)
         } else if (c.second.kind == Query::Phrase) {
           add_phrase(c.second, bc, Occur::Must);  // (a clause of its own: a one-member nested query)

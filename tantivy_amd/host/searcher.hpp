@@ -99,7 +99,7 @@ enum class Occur { Should, Must, MustNot };  // src/query/occur.rs
 // TantivyError::Unsupported so that the caller keeps tantivy's own CPU scorer for it
 // (the `SpecializedScorer::Other` branch, boolean_weight.rs:595-597).
 struct Query {
-  enum Kind { Term, Boolean, Phrase } kind;
+  enum Kind { Term, Boolean, Phrase, All } kind;
   // Term
   uint32_t term = 0;
   // Boolean: clauses of (Occur, sub query)
@@ -115,6 +115,13 @@ struct Query {
     Query q;
     q.kind = Term;
     q.term = term;
+    return q;
+  }
+  // AllQuery (src/query/all_query.rs:23-112): every doc, score = the boost.  At the top level or as a direct clause
+  // of a BooleanQuery (TQ_TERM_ALL with weights = boost); inside a nested BooleanQuery: Unsupported
+  static Query all() {
+    Query q;
+    q.kind = All;
     return q;
   }
   static Query boolean(std::vector<std::pair<Occur, Query>> clauses) {
