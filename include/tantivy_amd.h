@@ -429,6 +429,18 @@ int tq_last_batch_match_counts(tq_segment *seg, uint32_t *out, uint32_t n_querie
  * as a whole with TQ_ERR_UNSUPPORTED, tq_last_error() names the index of the first such query, nothing is launched and
  * the segment stays usable; malformed queries (mixed occurs in one clause, occur > 2, handle out of range, n_terms 0
  * or > TQ_MAX_TERMS) return TQ_ERR_INVALID the same way.  Scores (Weight::for_each): tq_docset_scored_batch below.
+ * With the option "docset_trees" = 1 both variants TAKE those shapes: TQ_MODE_PHRASE (phrase_offsets required), phrases
+ * as boolean clauses and nested queries — whatever tq_search_batch takes as a tree: 2..8 terms per phrase, a field with
+ * positions, minimums <= 15; weights may still be NULL.  A TQ_TERM_ALL clause inside a nested query, and whatever else
+ * the tree planner refuses, fails the batch as above with the planner's code.  Every list of such a query is reached
+ * through a bitmap (its own tables or the probe pool's, built on first use as for TQ_KERNEL_TREE; "use_dense" off:
+ * TQ_ERR_UNSUPPORTED).  Cost: ONE result bitmap of batch scratch per such query (max_doc / 8 bytes, counted against
+ * "docset_temp_lists" like a scattered list), written by docset_tree_bits_kernel — the tree's bitwise expression over
+ * the lists' words, a phrase decided per candidate doc by walking its positions to the first place where the terms line
+ * up — in front of the count pass, which then reads the query as one list.  kernel_mask gains TQ_KERNEL_DOCSET_TREE
+ * when a query of the call took that kernel, and such a query adds (lists + 2) x bitmap words x 4 to algorithmic_bytes
+ * (every list's bits once, the result word written and read back; positions are not counted) in place of lists x
+ * bitmap words x 4.  tq_count_batch keeps its routes, and the scored calls below refuse these shapes under either value.
  * Afterwards tq_last_batch_match_counts gives the per-query sizes, tq_batch_stats.matches the total docs,
  * kernel_mask = TQ_KERNEL_DOCSET and algorithmic_bytes = lists x bitmap words x 4 + 4 x docs. */
 int tq_docset_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
@@ -445,7 +457,8 @@ int tq_docset_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_
  * (TopDocs::tweak_score / custom_score, a MultiCollector with a scoring child, a user collector that reads the score):
  * every ALIVE matching doc with its BM25 score, however many there are (top-k stops at TQ_MAX_K).
  * out_docs / out_starts are exactly what tq_docset_batch returns for the same queries — same query shapes, same
- * refusals (TQ_MODE_PHRASE and nested queries: TQ_ERR_UNSUPPORTED naming the first such query, nothing launched), same
+ * refusals (TQ_MODE_PHRASE and nested queries: TQ_ERR_UNSUPPORTED naming the first such query, nothing launched —
+ * also with "docset_trees" = 1, which only concerns the unscored calls), same
  * capacity protocol — and out_scores[i] is the score of out_docs[i]; one out_cap covers both arrays (host variant, total
  * > out_cap: TQ_ERR_INVALID, out_starts complete, no doc and no score written).  Unlike tq_docset_batch, weights and
  * tf_cache are REQUIRED for every query that has a scoring (non-MustNot, present) list — TQ_ERR_INVALID naming the
@@ -506,6 +519,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_DOCSET 0x2000u       /* docset_count / docset_write kernels (tq_docset_batch* over bitmap words) */
 #define TQ_KERNEL_DOCSET_SCORE 0x4000u /* docset_score kernel (tq_docset_scored_batch*: the scoring pass behind the write pass) */
 #define TQ_KERNEL_ALL 0x8000u          /* all_kernel (ALL-BASED queries: TQ_TERM_ALL clauses, over bitmap words) */
+#define TQ_KERNEL_DOCSET_TREE 0x10000u /* docset_tree_bits_kernel (tq_docset_batch*, option "docset_trees": phrases and nested queries as match bits) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -582,6 +596,10 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        4096; never below TQ_MAX_TERMS, so a single query always fits): tq_docset_batch* — how many lists without a
  *        bitmap one launch scatters into batch scratch; a batch that names more of them runs as consecutive
  *        sub-batches of whole queries (out_starts continues across them; the caller sees one call),
+ *        "docset_trees" (0/1, default 0; any other value: TQ_ERR_INVALID): tq_docset_batch / tq_docset_batch_device
+ *        also take TQ_MODE_PHRASE, phrases as boolean clauses and nested queries (TQ_KERNEL_DOCSET_TREE; one scratch
+ *        bitmap per such query, see "doc sets"); 0: they are refused with TQ_ERR_UNSUPPORTED as before.  The scored
+ *        variants refuse them under either value,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

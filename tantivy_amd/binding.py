@@ -57,10 +57,11 @@ KERNEL_TREE = 0x1000
 KERNEL_DOCSET = 0x2000
 KERNEL_DOCSET_SCORE = 0x4000
 KERNEL_ALL = 0x8000
+KERNEL_DOCSET_TREE = 0x10000
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
-                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all"}
+                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree"}
 
 
 def kernel_names(mask):
@@ -839,6 +840,19 @@ class DeviceIndex:
                     na = (C.c_uint8 * len(terms))(*[int(o) for o in extra["nested_occurs"]])
                     keep.append(na)
                     qs[i].nested_occurs = C.cast(na, C.POINTER(C.c_uint8))
+                # the rest of a tree (doc sets under the option "docset_trees"): conjunctions / phrases, nested minimums
+                if extra and extra.get("atom_of") is not None:
+                    aa = (C.c_uint8 * len(terms))(*[int(o) for o in extra["atom_of"]])
+                    keep.append(aa)
+                    qs[i].atom_of = C.cast(aa, C.POINTER(C.c_uint8))
+                if extra and extra.get("phrase_offsets") is not None:
+                    pa = (C.c_uint32 * len(terms))(*[int(o) for o in extra["phrase_offsets"]])
+                    keep.append(pa)
+                    qs[i].phrase_offsets = C.cast(pa, C.POINTER(C.c_uint32))
+                if extra and extra.get("clause_min_should") is not None:  # {clause_of value: nested minimum}
+                    ma = (C.c_uint8 * 16)(*[int(extra["clause_min_should"].get(c, 0)) for c in range(16)])
+                    keep.append(ma)
+                    qs[i].clause_min_should = C.cast(ma, C.POINTER(C.c_uint8))
             elif mode == MODE_PHRASE:
                 oa = (C.c_uint32 * len(terms))(*(q[2] if len(q) > 2 and q[2] is not None else range(len(terms))))
                 keep.append(oa)

@@ -233,6 +233,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_docset_squeries.release();
   s->d_docset_caches.release();
   s->d_docset_scores.release();
+  s->d_docset_trees.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
@@ -490,6 +491,8 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.count_bitmap_ratio = (int)value;
   else if (!strcmp(name, "docset_temp_lists") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.docset_temp_lists = (int)value;
+  else if (!strcmp(name, "docset_trees") && (value == 0 || value == 1))
+    s->opt.docset_trees = (int)value;
   else if (!strcmp(name, "ashare_min_batch") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.ashare_min_batch = (int)value;
   else if (!strcmp(name, "xunion_min_queries") && value >= 1 && value <= 0x7FFFFFFF)

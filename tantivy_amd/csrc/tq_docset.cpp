@@ -4,8 +4,14 @@
 // one — bits scattered into the batch's scratch (count_scatter_kernel); tq_docset.hip counts, scans and writes.
 // tq_docset_scored_batch*: the same rows with every doc's BM25 score (Weight::for_each, src/query/weight.rs:9-18,89-97):
 // tq_docset_score.hip's pass behind every write pass, over a scoring descriptor of its own (score_expression).
+// Option "docset_trees": a phrase or a nested boolean query (unscored calls) is planned by plan_tree_query, its exact match
+// bits are written into ONE slot of the same scratch by tq_docset_tree.hip behind the sub-batch's scatter, and the
+// passes see one Must list that is bits in scratch.  The host variant with one sub-batch keeps the bits between its
+// count and write passes, so positions are walked once; with several sub-batches each one is evaluated twice, like the
+// scattered lists.
 #include "tq_internal.hpp"
 
+#include <deque>
 #include <unordered_map>
 
 namespace tqi {
@@ -109,11 +115,33 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
   if (fc.all_based) memcpy(&sq.all_base_bits, &fc.all_base, sizeof(float));
 }
 
+void docset_tree_view(const tq_query &q, TreeView &v) {
+  static_assert(TQ_MAX_TERMS == 16, "kOnes holds one weight per term");
+  static const float kOnes[TQ_MAX_TERMS] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
+  v.q = q;
+  v.q.weights = kOnes;  // (plan_tree_query reads them and refuses negative boosts: a doc set has neither)
+  if (q.mode != TQ_MODE_PHRASE) return;
+  for (uint32_t i = 0; i < q.n_terms && i < TQ_MAX_TERMS; ++i) {
+    v.occurs[i] = TQ_MUST;
+    v.clause_of[i] = v.atom_of[i] = 0;
+    v.nested_occurs[i] = TQ_MUST | TQ_NESTED_PHRASE;
+  }
+  v.q.mode = TQ_MODE_BOOL;
+  v.q.occurs = v.occurs;
+  v.q.clause_of = v.clause_of;
+  v.q.atom_of = v.atom_of;
+  v.q.nested_occurs = v.nested_occurs;
+  v.q.clause_min_should = nullptr;
+  v.q.min_should_match = 0;
+}
+
 namespace {
 
-struct SubBatch {  // consecutive whole queries whose lists without a bitmap fit the scratch together
+struct SubBatch {  // consecutive whole queries whose lists without a bitmap and tree results fit the scratch together
   uint32_t q0 = 0, q1 = 0;
   size_t wg0 = 0, wg1 = 0;  // its part of the scatter work list
+  uint32_t t0 = 0, t1 = 0;  // ... and of the tree records (tq_docset_tree.hip)
+  bool any_phrase = false;  // some tree of its queries has a phrase atom
   uint32_t n_temp = 0;
   bool score_blocks = false;  // some scoring list of its queries is reached by the block search
 };
@@ -142,11 +170,18 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   std::vector<TqkScoreQuery> sqs(scored ? n_queries : 0u);
   std::vector<const float *> caches;  // the batch's Bm25Weight caches in order of first use (pointer identity, as in search)
   uint64_t algo_bytes = 0;
+  std::vector<uint32_t> tree_q;     // the queries that take the tree path (option "docset_trees"), ascending
+  std::vector<TqdTreeQuery> tqs;    // ... and their records, in the same order
+  const bool trees_on = s->opt.docset_trees && !scored && !count_only;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     const char *why = "";
     FlatClauses fc;
     const tq_query &q = queries[qi];
     const int rc = docset_expression(s, q, dqs[qi], &why, scored ? &fc : nullptr);
+    if (rc == FLAT_UNSUPPORTED && trees_on && !query_has_all(q) && (q.mode == TQ_MODE_PHRASE || bool_query_is_tree(q))) {
+      tree_q.push_back(qi);
+      continue;
+    }
     if (rc == FLAT_UNSUPPORTED)
       return fail(TQ_ERR_UNSUPPORTED, "%s: query %u is %s: doc sets of phrases and nested queries stay on the CPU", fn, qi, why);
     if (rc != FLAT_OK) return fail(TQ_ERR_INVALID, "%s: query %u: %s", fn, qi, why);
@@ -173,16 +208,46 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     algo_bytes += (uint64_t)sqs[qi].n_lists * n_words * 8u;
   }
+  if (!tree_q.empty()) {
+    // every list of a tree as a bitmap + tf bytes, a phrase term's position directory: the list's own tables or the probe
+    // pool's, built now; a probe batch like a search batch's, so that no list of this call is evicted for another
+    probe_begin_batch(s);
+    std::deque<TreeView> views;
+    bool built = false;
+    for (const uint32_t qi : tree_q) {
+      views.emplace_back();
+      docset_tree_view(queries[qi], views.back());
+      const int prc = build_tree_query_probe_tables(s, views.back().q, &built);
+      if (prc != TQ_OK) return prc;
+    }
+    if (built) s->share_span_terms = ~(size_t)0;
+    update_table_span(s);
+    if (!s->share_span_ok || !s->opt.use_dense) return fail_tree_tables(s, tree_q[0]);
+    tqs.resize(tree_q.size());
+    for (size_t i = 0; i < tree_q.size(); ++i) {
+      uint64_t qbytes = 0;
+      const int prc = plan_tree_query(s, views[i].q, tree_q[i], tqs[i], qbytes, s->share_table_lo);
+      if (prc != TQ_OK) return prc;  // (names the query)
+      TqkDocsetQuery &dq = dqs[tree_q[i]];  // to the passes: one Must list that is bits in scratch
+      dq = TqkDocsetQuery{};
+      dq.n_terms = dq.narrow = dq.clause_end = 1u;
+      // every list's bits once + the result word written and read back
+      algo_bytes += ((uint64_t)tqs[i].n_terms + 2u) * n_words * 4u;
+    }
+  }
   // sub-batches; a list without a bitmap gets a slot of the scratch for the duration of its sub-batch
   std::vector<SubBatch> subs;
   std::vector<uint4> wgs;
   std::unordered_map<uint32_t, uint32_t> slot;
   SubBatch cur;
   uint32_t max_sub_temp = 0, max_sub_n = 0;
+  uint32_t n_slots = 0;  // slots of the sub-batch so far: its lists without a bitmap and its trees' results
+  uint32_t n_trees = 0;  // tree queries so far
   auto close_sub = [&](uint32_t q1) {
     cur.q1 = q1;
     cur.wg1 = wgs.size();
-    cur.n_temp = (uint32_t)slot.size();
+    cur.t1 = n_trees;
+    cur.n_temp = n_slots;
     for (uint32_t qi = cur.q0; scored && qi < q1; ++qi)
       for (uint32_t m = 0; m < sqs[qi].n_lists; ++m)
         cur.score_blocks = cur.score_blocks || ((sqs[qi].access >> (2u * m)) & 3u) == TQK_SCORE_BLOCKS;
@@ -192,10 +257,19 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     cur = SubBatch{};
     cur.q0 = q1;
     cur.wg0 = wgs.size();
+    cur.t0 = n_trees;
     slot.clear();
+    n_slots = 0;
   };
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     TqkDocsetQuery &dq = dqs[qi];
+    if (n_trees < tree_q.size() && tree_q[n_trees] == qi) {  // a tree: one result slot, like a fresh list
+      if (qi > cur.q0 && (n_slots + 1u > max_temp || qi - cur.q0 >= max_sub_queries)) close_sub(qi);
+      cur.any_phrase = cur.any_phrase || tqs[n_trees].has_phrase;
+      tqs[n_trees++].part_start = n_slots;
+      dq.dense[0] = (const uint2 *)(uintptr_t)n_slots++;  // (the slot; the pointer below)
+      continue;
+    }
     uint32_t fresh[TQ_MAX_TERMS], n_fresh = 0;
     for (uint32_t m = 0; m < dq.n_terms; ++m) {
       if (!((dq.narrow >> m) & 1u)) continue;
@@ -203,13 +277,13 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       if (slot.count(h) || std::find(fresh, fresh + n_fresh, h) != fresh + n_fresh) continue;
       fresh[n_fresh++] = h;
     }
-    if (qi > cur.q0 && (slot.size() + n_fresh > max_temp || qi - cur.q0 >= max_sub_queries)) close_sub(qi);
+    if (qi > cur.q0 && (n_slots + n_fresh > max_temp || qi - cur.q0 >= max_sub_queries)) close_sub(qi);
     for (uint32_t m = 0; m < dq.n_terms; ++m) {
       if (!((dq.narrow >> m) & 1u)) continue;
       const uint32_t h = (uint32_t)(uintptr_t)dq.dense[m];
       auto it = slot.find(h);
       if (it == slot.end()) {
-        it = slot.emplace(h, (uint32_t)slot.size()).first;
+        it = slot.emplace(h, n_slots++).first;
         for (uint32_t j = 0; j < s->terms[h].n_blocks; j += 4u) wgs.push_back(make_uint4(h, j, it->second, 0u));
       }
       dq.dense[m] = (const uint2 *)(uintptr_t)it->second;  // (the slot; the pointer below)
@@ -224,7 +298,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (wrc != TQ_OK) return wrc;
   }
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u);
+  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE);
   s->stats.algorithmic_bytes = algo_bytes;
   s->stats_pending = false;
   s->last_batch_queries = 0;
@@ -236,14 +310,16 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     return TQ_OK;
   }
-  if (!wgs.empty() || scored) {  // (the scoring pass reads term records: saturated tfs, the block search)
+  if (!wgs.empty() || scored || !tqs.empty()) {  // (the scoring pass reads term records: saturated tfs, the block search; a phrase atom: positions)
     const int src = sync_terms(s, s->stream);
     if (src != TQ_OK) return src;
   }
   const size_t q_bytes = (size_t)n_queries * sizeof(TqkDocsetQuery), wg_bytes = wgs.size() * sizeof(uint4);
   const size_t sq_bytes = sqs.size() * sizeof(TqkScoreQuery), cache_bytes = caches.size() * 256u * sizeof(float);
+  const size_t tree_bytes = tqs.size() * sizeof(TqdTreeQuery);
   const size_t max_entries = (size_t)max_sub_n * n_tiles;
-  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes);
+  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes + tree_bytes);
+  if (rc == TQ_OK && tree_bytes) rc = s->d_docset_trees.ensure(tree_bytes);
   if (rc == TQ_OK && scored) rc = s->d_docset_squeries.ensure(sq_bytes);
   if (rc == TQ_OK && scored) rc = s->d_docset_caches.ensure(std::max<size_t>(cache_bytes, 256u * sizeof(float)));
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
@@ -275,14 +351,33 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     HIP_TRY(hipMemcpyAsync(s->d_docset_squeries.p, h_sq, sq_bytes, hipMemcpyHostToDevice, st));
     if (cache_bytes) HIP_TRY(hipMemcpyAsync(s->d_docset_caches.p, h_sq + sq_bytes, cache_bytes, hipMemcpyHostToDevice, st));
   }
+  if (tree_bytes) {
+    uint8_t *const h_tq = (uint8_t *)s->h_docset.p + q_bytes + wg_bytes + sq_bytes + cache_bytes;
+    memcpy(h_tq, tqs.data(), tree_bytes);
+    HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_bytes, hipMemcpyHostToDevice, st));
+  }
 
   uint64_t *const d_starts = device_out ? out_starts : (uint64_t *)s->d_docset_starts.p;
   auto enqueue = [&](const SubBatch &sb, uint32_t stages, uint32_t *d_docs, float *d_scores, uint64_t cap) -> int {
-    if ((stages & DS_SCATTER) && sb.n_temp) {  // the sub-batch's lists without a bitmap, as bits
+    if ((stages & DS_SCATTER) && sb.wg1 > sb.wg0) {  // the sub-batch's lists without a bitmap, as bits
       HIP_TRY(hipMemsetAsync(s->d_count_bits.p, 0, (size_t)sb.n_temp * words_per_list * sizeof(uint32_t), st));
       const hipError_t se = tqk_launch_count_scatter(s->dseg, s->d_terms, (const uint4 *)s->d_count_wgs.p + sb.wg0,
                                                      (uint32_t)(sb.wg1 - sb.wg0), (uint32_t *)s->d_count_bits.p, words_per_list, st);
       if (se != hipSuccess) return fail(TQ_ERR_HIP, "doc-set scatter launch: %s", hipGetErrorString(se));
+    }
+    if ((stages & DS_SCATTER) && sb.t1 > sb.t0) {  // its trees' match bits: every word of their slots is stored, once
+      TqkDocsetTreeParams tp{};
+      tp.seg = s->dseg;
+      tp.terms = s->d_terms;
+      tp.queries = (const TqdTreeQuery *)s->d_docset_trees.p + sb.t0;
+      tp.table_base = (const uint8_t *)s->share_table_lo;
+      tp.bits = (uint32_t *)s->d_count_bits.p;
+      tp.n_queries = sb.t1 - sb.t0;
+      tp.n_words = n_words;
+      tp.words_per_list = words_per_list;
+      tp.any_phrase = sb.any_phrase ? 1u : 0u;
+      const hipError_t te = tqk_launch_docset_tree(tp, st);
+      if (te != hipSuccess) return fail(TQ_ERR_HIP, "doc-set tree launch: %s", hipGetErrorString(te));
     }
     TqkDocsetParams p{};
     p.queries = (const TqkDocsetQuery *)s->d_docset_queries.p + sb.q0;

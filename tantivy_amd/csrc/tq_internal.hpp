@@ -195,6 +195,7 @@ struct Options {
   int probe_budget_x = 16;  // bitmaps + tf bytes built on demand for the lists boolean queries probe: at most this multiple of the segment
   int count_bitmap_ratio = 128;  // Count: bitmap words instead of a scan if the driving clause holds >= max_doc / ratio postings per list
   int docset_temp_lists = 0;     // doc sets: lists without a bitmap scattered per launch (0 = what TQ_COUNT_TEMP_MB holds, at most 4096)
+  int docset_trees = 0;          // doc sets: phrases and nested boolean queries through tq_docset_tree.hip (0 = refused, as before)
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
   // tq_submit / tq_search_one: how long the leader of a batch waits for the callers of the previous
   // batch to come back with their next query (0 = launch with whatever is pending)
@@ -312,10 +313,12 @@ struct tq_segment {
   DevBuf d_docset_queries, d_docset_counts, d_docset_offs, d_docset_partials, d_docset_starts, d_docset_docs;
   // ... with scores (tq_docset_score.hip): scoring descriptors, the batch's Bm25Weight caches, the host variant's scores
   DevBuf d_docset_squeries, d_docset_caches, d_docset_scores;
+  DevBuf d_docset_trees;  // ... of phrases and nested queries (tq_docset_tree.hip): their TqdTreeQuery records
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
-           d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap;
+           d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap +
+           d_docset_trees.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -922,6 +925,14 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
 // count_only (host outputs): the count pass and the row starts alone, no doc is written (tq_count_batch's ALL-BASED queries)
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false);
+// A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
+// whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
+// Must clause holding one phrase atom" with the caller's phrase_offsets.
+struct TreeView {
+  tq_query q;
+  uint8_t occurs[TQ_MAX_TERMS], clause_of[TQ_MAX_TERMS], atom_of[TQ_MAX_TERMS], nested_occurs[TQ_MAX_TERMS];
+};
+void docset_tree_view(const tq_query &q, TreeView &v);  // (q.n_terms <= TQ_MAX_TERMS)
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);
@@ -933,6 +944,11 @@ bool bool_query_is_tree(const tq_query &q);
 int plan_tree_query(tq_segment *s, const tq_query &q, uint32_t qi, TqdTreeQuery &tq, uint64_t &qbytes, uint64_t table_base);
 // ---- tq_search.cpp
 int resolve_opts(const tq_segment *s, const tq_search_opts *o, CallOpts &co);
+void update_table_span(tq_segment *s);
+// the probe tables one nested boolean query needs (tq_tree.hip / tq_docset_tree.hip reach EVERY list through a bitmap,
+// a phrase term's positions from the bitmap's rank); *built: some table is new (the tables' address span moved)
+int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built);
+int fail_tree_tables(const tq_segment *s, uint32_t qi);  // "use_dense" off, or the tables outside one 32 GB span: TQ_ERR_UNSUPPORTED
 int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *d_out_scores, uint32_t *d_out_docs, uint32_t *d_out_counts, void *hip_stream,
                       const CallOpts &co);

@@ -181,7 +181,7 @@ constexpr uint32_t TQK_TREE_PHRASE_TERMS = 8;  // terms of a phrase inside a boo
 struct TqdTreeQuery {
   uint32_t n_terms, n_clauses;   // 0 / 0: the planner found the query empty
   uint32_t k, cache_idx;
-  uint32_t part_start;           // first partial top-k list (one per tile)
+  uint32_t part_start;           // first partial top-k list (one per tile); tq_docset_tree.hip: the query's result slot
   uint32_t top_has_must;         // the query has Must clauses (else: the union of its Should clauses)
   uint32_t top_need;             // Should clauses that have to match: minimum_number_should_match, at least 1 without a Must clause
   uint32_t has_phrase;           // some atom is a PhraseQuery (atom_end bit 1): the bitmap expression is a superset, every doc is re-checked
@@ -213,6 +213,18 @@ struct TqkTreeParams {
 };
 hipError_t tqk_launch_tree(const TqkTreeParams &p, int kpl, hipStream_t st);
 uint32_t tqk_tree_tiles(uint32_t n_words);
+// ---- the exact match bits of such trees for doc sets (tq_docset_tree.hip): query q's alive matching docs as bits
+// [part_start * words_per_list, + n_words) of the doc-set batch's scratch, every word stored once; no scores
+struct TqkDocsetTreeParams {
+  TqdSegment seg;
+  const TqdTerm *terms;
+  const TqdTreeQuery *queries;  // [n_queries] as plan_tree_query leaves them (k / cache_idx / weight_bits are not read)
+  const uint8_t *table_base;
+  uint32_t *bits;               // the scratch's result bitmaps: words_per_list 32-bit words each
+  uint32_t n_queries, n_words, words_per_list;
+  uint32_t any_phrase;          // some query of the launch has a phrase atom (selects the kernel instantiation)
+};
+hipError_t tqk_launch_docset_tree(const TqkDocsetTreeParams &p, hipStream_t st);
 
 // ---- ALL-BASED queries (tq_all.hip): a flat query whose AllQuery clauses (TQ_TERM_ALL) make every doc a candidate
 // (tq_all.cpp).  Lists: the Should lists in score-sum order (clause by clause, query order), then the MustNot lists.

@@ -60,6 +60,8 @@ struct Batch {
   uint32_t grid[kNGroups] = {};  // persistent grid of a result-list group
 };
 
+}  // namespace
+
 // The address span of the side tables the shared launches reach through 32-bit offsets (8-byte units from its lower
 // end: 32 GB), taken again when tables were added.
 void update_table_span(tq_segment *s) {
@@ -88,6 +90,8 @@ void update_table_span(tq_segment *s) {
   s->share_span_ok = hi - s->share_table_lo < (8ull << 32);
   s->share_span_terms = s->terms.size();
 }
+
+namespace {
 
 // The batch's stream, the terms prepared on the copy stream, and the term records this batch appends to the device table.
 int sync_term_records(Batch &b) {
@@ -197,33 +201,43 @@ int build_flat_probe_tables(Batch &b) {
   return TQ_OK;
 }
 
+}  // namespace
+
 // Nested boolean queries (tq_tree.hip) reach EVERY list through a bitmap, in both modes.
+int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built) {
+  if (!s->opt.use_dense || !s->opt.dense || s->opt.probe_budget_x <= 0) return TQ_OK;
+  if (q.mode != TQ_MODE_BOOL || !q.terms || q.n_terms > TQ_MAX_TERMS || !bool_query_is_tree(q)) return TQ_OK;
+  for (uint32_t i = 0; i < q.n_terms; ++i) {
+    const uint32_t h = q.terms[i];
+    if (h >= s->terms.size()) continue;
+    const TermHost &th = s->terms[h];
+    if (!(th.dense_blob && th.tf8_blob)) {
+      const bool had = th.probe_dense_blob && th.probe_tf8_blob;
+      bool ok = false;
+      const int prc = build_probe_tables(s, h, &ok, true);
+      if (prc != TQ_OK) return prc;
+      *built = *built || (ok && !had);
+    }
+    // a term of a phrase inside the boolean query: its positions are reached from the bitmap's rank
+    if (q.nested_occurs && q.nested_occurs[i] != 255u && (q.nested_occurs[i] & TQ_NESTED_PHRASE) &&
+        !s->terms[h].posdir_blob && !s->terms[h].probe_posdir_blob) {
+      bool ok = false;
+      const int prc = build_probe_posdir(s, h, &ok);
+      if (prc != TQ_OK) return prc;
+      *built = *built || ok;
+    }
+  }
+  return TQ_OK;
+}
+
+namespace {
+
 int build_tree_probe_tables(Batch &b) {
-  if (!b.n_bool_queries || !b.s->opt.use_dense || !b.s->opt.dense || b.s->opt.probe_budget_x <= 0) return TQ_OK;
+  if (!b.n_bool_queries) return TQ_OK;
   bool built = false;
   for (uint32_t qi = 0; qi < b.n_queries; ++qi) {
-    const tq_query &q = b.queries[qi];
-    if (q.mode != TQ_MODE_BOOL || !q.terms || q.n_terms > TQ_MAX_TERMS || !bool_query_is_tree(q)) continue;
-    for (uint32_t i = 0; i < q.n_terms; ++i) {
-      const uint32_t h = q.terms[i];
-      if (h >= b.s->terms.size()) continue;
-      const TermHost &th = b.s->terms[h];
-      if (!(th.dense_blob && th.tf8_blob)) {
-        const bool had = th.probe_dense_blob && th.probe_tf8_blob;
-        bool ok = false;
-        const int prc = build_probe_tables(b.s, h, &ok, true);
-        if (prc != TQ_OK) return prc;
-        built = built || (ok && !had);
-      }
-      // a term of a phrase inside the boolean query: its positions are reached from the bitmap's rank
-      if (q.nested_occurs && q.nested_occurs[i] != 255u && (q.nested_occurs[i] & TQ_NESTED_PHRASE) &&
-          !b.s->terms[h].posdir_blob && !b.s->terms[h].probe_posdir_blob) {
-        bool ok = false;
-        const int prc = build_probe_posdir(b.s, h, &ok);
-        if (prc != TQ_OK) return prc;
-        built = built || ok;
-      }
-    }
+    const int prc = build_tree_query_probe_tables(b.s, b.queries[qi], &built);
+    if (prc != TQ_OK) return prc;
   }
   if (built) b.s->share_span_terms = ~(size_t)0;
   return TQ_OK;
@@ -498,14 +512,21 @@ void route_phrase(const Batch &b, uint32_t qi, Route &r, RouteTotals &t) {
   }
 }
 
+}  // namespace
+
+int fail_tree_tables(const tq_segment *s, uint32_t qi) {
+  return fail(TQ_ERR_UNSUPPORTED,
+              "query %u: nested boolean queries need the lists' bitmaps (\"use_dense\" %d, one 32 GB table span: %s — tables from %llx, arena %llx + %zu MB "
+              "mapped, %zu allocations outside it)",
+              qi, (int)s->opt.use_dense, s->share_span_ok ? "ok" : "exceeded", (unsigned long long)s->share_table_lo, (unsigned long long)(uintptr_t)s->dense_arena,
+              s->dense_arena_mapped >> 20, s->dense_extra.size());
+}
+
+namespace {
+
 // A clause that is itself a BooleanQuery of terms (tq_query.nested_occurs): evaluated over bitmaps, tq_tree.hip.
 int route_tree(const Batch &b, uint32_t qi, Route &r, Group &tree_group) {
-  if (!b.s->share_span_ok || !b.s->opt.use_dense)
-    return fail(TQ_ERR_UNSUPPORTED,
-                "query %u: nested boolean queries need the lists' bitmaps (\"use_dense\" %d, one 32 GB table span: %s — tables from %llx, arena %llx + %zu MB "
-                "mapped, %zu allocations outside it)",
-                qi, (int)b.s->opt.use_dense, b.s->share_span_ok ? "ok" : "exceeded", (unsigned long long)b.s->share_table_lo, (unsigned long long)(uintptr_t)b.s->dense_arena,
-                b.s->dense_arena_mapped >> 20, b.s->dense_extra.size());
+  if (!b.s->share_span_ok || !b.s->opt.use_dense) return fail_tree_tables(b.s, qi);
   TqdTreeQuery tq;
   const int rc = plan_tree_query(b.s, b.queries[qi], qi, tq, r.qbytes, b.s->share_table_lo);
   if (rc != TQ_OK) return rc;

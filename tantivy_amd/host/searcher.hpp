@@ -328,7 +328,8 @@ class Searcher {
   std::vector<uint64_t> count_batch(const std::vector<Weight> &weights);
   // Searcher::search(&query, &DocSetCollector) for a batch (docset_collector.rs:26-57: every segment's alive matching
   // docs — Weight::for_each_no_score — which merge_fruits unions into DocAddresses): per query the addresses over all
-  // segments, ordered by (segment_ord, doc_id).  Flat queries only: a phrase or a nested query throws Unsupported.
+  // segments, ordered by (segment_ord, doc_id).  A phrase or a nested query throws Unsupported unless the option
+  // "docset_trees" is set on every segment (tq_set_option): then they return their rows like flat queries.
   std::vector<std::vector<DocAddress>> docset_batch(const std::vector<Weight> &weights);
   // the same for a collector whose requires_scoring() is true (Weight::for_each, weight.rs:9-18,89-97: TopDocs::tweak_score
   // / custom_score, a MultiCollector with a scoring child): every address with its BM25 score under the searcher's

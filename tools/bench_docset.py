@@ -14,7 +14,15 @@ process: the scored call's kernel time, the scoring pass as the difference of th
 for the bytes the pass adds at the fill bandwidth of the same run, and — for context — the exhaustive top-10 search of the
 same queries, the only route that scored every match before.  Written to profiles/docset_scored_bench.json.
 
-  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3] [--scores]"""
+--trees: doc sets of phrase and nested boolean queries (option "docset_trees", tq_docset_tree.hip) on the 10 M-doc
+segment WITH positions that bench.py's phrase workloads build: `phrase2` (2-term phrases over the phrase terms) and
+`nested` (the shapes of tests/tree_shapes.py::SHAPES over Zipf ids).  Per workload, from one process: the doc-set
+call's kernel and batch ms, the docs written, and the ms of tq_count_batch for the same queries — the exhaustive
+scan, the only device route that visited every match of these shapes before, and therefore the yardstick — plus the
+fill of the output buffer, what a write of the same size costs at the least.  Written to
+profiles/docset_tree_bench.json.
+
+  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3] [--scores | --trees]"""
 import argparse
 import json
 import os
@@ -29,6 +37,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0
 OUT_BYTES_MAX = 4 << 30
 WORKLOADS = ("and2", "or5", "bool")
+TREE_WORKLOADS = ("phrase2", "nested")
+PHRASE_TERMS = 64  # ranks with planted phrase positions, as in bench.py
 
 
 def _queries(O, T, workload, n, terms):
@@ -132,6 +142,101 @@ def child(args):
     dev.close()
 
 
+def _tree_queries(O, T, workload, n, terms):
+    """-> (device tuples, oracle forms)"""
+    from tests.tree_shapes import SHAPES, to_device
+
+    if workload == "phrase2":  # two distinct ranks in rank order, offsets = the rank difference (bench.py's phrase3, one term shorter)
+        qs = []
+        for q in O.zipf_queries(n, 2, PHRASE_TERMS, seed=20260925):
+            r = sorted(int(x) for x in q)
+            qs.append((O.MODE_PHRASE, r, [0, r[1] - r[0]]))
+        return qs, [("phrase", q[1], q[2]) for q in qs]
+    specs = [(SHAPES[i % len(SHAPES)][0](q.tolist()), SHAPES[i % len(SHAPES)][1])
+             for i, q in enumerate(O.zipf_queries(n, 8, terms, seed=20260926))]
+    return [to_device(T, sp, msm) for sp, msm in specs], [("tree", sp, msm) for sp, msm in specs]
+
+
+def tree_child(args):
+    import ctypes as C
+
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a GPU")
+    from oracle import oracle as O
+    import tantivy_amd as T
+
+    seg = O.synth_segment(args.docs, n_terms=args.terms, with_positions=True, phrase_terms=PHRASE_TERMS)
+    dev = T.DeviceIndex([seg], devices=[0])
+    dev.set_option("timing", 1)
+    dev.set_option("docset_trees", 1)
+    n = args.queries
+    queries, forms = _tree_queries(O, T, args.child, n, args.terms)
+    counts = dev.count(queries)  # (the scan; it also builds the probe tables both routes use)
+    while int(counts.sum()) * 4 > OUT_BYTES_MAX and n > 1:  # size the batch by its output
+        n = max(1, int(n * OUT_BYTES_MAX / (int(counts.sum()) * 4) * 0.95))
+        queries, forms, counts = queries[:n], forms[:n], counts[:n]
+    total = int(counts.sum())
+    d_docs = torch.empty(max(1, total), dtype=torch.int32, device="cuda")
+    d_starts = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    stream = torch.cuda.Stream()
+    ds_ms, ds_wall, ct_wall, ct_kernel = [], [], [], []
+    for i in range(args.warmup + args.reps):
+        t0 = time.perf_counter()
+        rc = dev.raw_docset_device(queries, d_docs, total, d_starts, stream=stream.cuda_stream)
+        assert rc == 0, T.binding.lib().tq_last_error()
+        st = dev.last_batch_stats()  # waits for the batch; kernel_ms = HIP events around bits + count + scan + write
+        wall = (time.perf_counter() - t0) * 1e3
+        if i >= args.warmup:
+            ds_ms.append(st["kernel_ms"])
+            ds_wall.append(wall)
+    assert st["kernels"] == ["docset", "docset_tree"] and st["matches"] == total, st
+    starts = d_starts.cpu().numpy()
+    assert int(starts[-1]) == total and np.array_equal(np.diff(starts), counts.astype(np.int64))
+    checked = 0
+    for q in range(0, n, max(1, n // 6)):  # a sample of rows against the oracle
+        if counts[q] > 2_000_000:
+            continue
+        f = forms[q]
+        w = O.match_all(seg, f[1], O.MODE_PHRASE, phrase_offsets=f[2])[0] if f[0] == "phrase" else O.tree_match_all(seg, f[1], f[2])[0]
+        got = d_docs[int(starts[q]): int(starts[q + 1])].cpu().numpy().view(np.uint32)
+        assert np.array_equal(got, np.asarray(w, np.uint32)), queries[q]
+        checked += 1
+    dev.prepare(queries)
+    out = np.zeros(max(1, n), np.uint64)
+    for i in range(args.warmup + args.reps):
+        t0 = time.perf_counter()
+        T.binding._check(T.binding.lib().tqh_count_prepared(dev._s, out.ctypes.data_as(C.POINTER(C.c_uint64))), host=True)
+        if i >= args.warmup:
+            ct_wall.append((time.perf_counter() - t0) * 1e3)
+            ct_kernel.append(dev.last_batch_stats()["kernel_ms"])
+    scan = dev.last_batch_stats()
+    assert np.array_equal(out[:n], counts)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fill = []
+    for i in range(args.warmup + args.reps):  # the fill bandwidth of this run: a device memset of the output buffer
+        ev0.record()
+        d_docs.fill_(i)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            fill.append(ev0.elapsed_time(ev1))
+    k = float(np.median(ds_ms))
+    res = {"workload": args.child, "docs": args.docs, "terms": args.terms, "queries": n, "out_docs": total,
+           "docset_kernel_ms": round(k, 4), "docset_kernel_ms_min": round(float(np.min(ds_ms)), 4),
+           "docset_batch_ms": round(float(np.median(ds_wall)), 4),
+           "count_scan_ms": round(float(np.median(ct_wall)), 4), "count_scan_kernel_ms": round(float(np.median(ct_kernel)), 4),
+           "count_scan_kernels": scan["kernels"],
+           "fill_ms": round(float(np.median(fill)), 4),
+           "scan_plus_fill_ms": round(float(np.median(ct_wall)) + float(np.median(fill)), 4),
+           "algorithmic_bytes": int(st["algorithmic_bytes"]),
+           "model_GBs": round(st["algorithmic_bytes"] / (k * 1e-3) / 1e9, 1),
+           "reps": args.reps, "warmup": args.warmup, "rows_checked_against_oracle": checked}
+    print("RESULT " + json.dumps(res))
+    dev.close()
+
+
 def scored_run(args, O, T, seg, dev, queries, total, d_docs, d_starts, stream, fill_ms):
     """The batch through tq_docset_scored_batch_device, alternating with the unscored call; -> the extra result fields."""
     import torch
@@ -203,20 +308,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=10_000_000)
     ap.add_argument("--terms", type=int, default=256)
-    ap.add_argument("--queries", type=int, default=1000)
+    ap.add_argument("--queries", type=int, default=None, help="queries per batch (default: 1000; --trees: 512, one scratch bitmap each)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--scores", action="store_true")
+    ap.add_argument("--trees", action="store_true")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--child", choices=WORKLOADS)
+    ap.add_argument("--child", choices=WORKLOADS + TREE_WORKLOADS)
     args = ap.parse_args()
+    if args.scores and args.trees:
+        raise SystemExit("--scores or --trees, not both (the scored calls refuse trees)")
+    if args.queries is None:
+        args.queries = 512 if args.trees or args.child in TREE_WORKLOADS else 1000
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "docset_scored_bench.json" if args.scores else "docset_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "docset_tree_bench.json" if args.trees else
+                                "docset_scored_bench.json" if args.scores else "docset_bench.json")
     if args.child:
-        return child(args)
+        return tree_child(args) if args.child in TREE_WORKLOADS else child(args)
     results = []
-    for wl in WORKLOADS:
+    for wl in (TREE_WORKLOADS if args.trees else WORKLOADS):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", wl, "--docs", str(args.docs), "--terms", str(args.terms),
                "--queries", str(args.queries), "--reps", str(args.reps), "--warmup", str(args.warmup)]
         if args.scores:
