@@ -413,6 +413,9 @@ __global__ __launch_bounds__(64, DENSE ? TQ_PH_WAVES_DENSE : 5) void phrase_kern
             if (k >= km0) break;
             c += d[k];
             a[k] = c;
+            // popc(ok) below is the reference's count (sum over values of the minimum multiplicity) only while the
+            // leader's positions are strictly increasing: a repeated one goes to the cursor merge
+            if (k && k < lead_tf && d[k] == 0u) fast = false;
           }
         }
         uint32_t ok = (1u << lead_tf) - 1u;
@@ -443,7 +446,7 @@ __global__ __launch_bounds__(64, DENSE ? TQ_PH_WAVES_DENSE : 5) void phrase_kern
           }
           ok &= hit;
         }
-        count = (uint32_t)__popc(ok);
+        if (fast) count = (uint32_t)__popc(ok);
       }
       if (__ballot(count == 0xFFFFFFFFu)) {
         if (count == 0xFFFFFFFFu) count = phrase_count_serial();
@@ -850,6 +853,8 @@ __global__ __launch_bounds__(64, TQ_PH_SWEEP_WAVES) void phrase_sweep_kernel(Tqk
           if (k >= km0) break;
           c += d[k];
           a[k] = c;
+          // (a repeated leader position: popc(ok) would count it once per copy — the cursor merge, as in phrase_kernel)
+          if (k && k < tf[0] && d[k] == 0u) fast = false;
         }
       }
       uint32_t ok = (1u << tf[0]) - 1u;
@@ -878,7 +883,7 @@ __global__ __launch_bounds__(64, TQ_PH_SWEEP_WAVES) void phrase_sweep_kernel(Tqk
         }
         ok &= hit;
       }
-      count = (uint32_t)__popc(ok);
+      if (fast) count = (uint32_t)__popc(ok);
     }
     if (__ballot(walk && count == 0xFFFFFFFFu)) {
       if (walk && count == 0xFFFFFFFFu) {  // the n-way cursor merge, one position at a time

@@ -108,6 +108,14 @@ def legacy_posting_list(postings):
     return head + bytes(payload) + bytes(tail)
 
 
+def alive_bytes(max_doc, deleted):
+    """BitSet::serialize (common/src/bitset.rs:215-223) of the alive set: the body of a `.del` file."""
+    bits = np.ones(((max_doc + 63) // 64) * 64, dtype=np.uint8)
+    bits[max_doc:] = 0
+    bits[np.asarray(sorted(deleted), dtype=np.int64)] = 0
+    return np.uint32(max_doc).tobytes() + np.packbits(bits, bitorder="little").tobytes()
+
+
 def exhaustive_by_default(module):
     """The library executes the reference's way by default: block-max pruned top-k ("exhaustive" =
     0).  The parity tests assert match counts and full match sets next to the top-k, which only
