@@ -440,7 +440,8 @@ int tq_last_batch_match_counts(tq_segment *seg, uint32_t *out, uint32_t n_querie
  * up — in front of the count pass, which then reads the query as one list.  kernel_mask gains TQ_KERNEL_DOCSET_TREE
  * when a query of the call took that kernel, and such a query adds (lists + 2) x bitmap words x 4 to algorithmic_bytes
  * (every list's bits once, the result word written and read back; positions are not counted) in place of lists x
- * bitmap words x 4.  tq_count_batch keeps its routes, and the scored calls below refuse these shapes under either value.
+ * bitmap words x 4.  tq_count_batch keeps its routes, and the scored calls below do not look at this option: they have
+ * one of their own, "docset_score_trees".
  * Afterwards tq_last_batch_match_counts gives the per-query sizes, tq_batch_stats.matches the total docs,
  * kernel_mask = TQ_KERNEL_DOCSET and algorithmic_bytes = lists x bitmap words x 4 + 4 x docs. */
 int tq_docset_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
@@ -456,9 +457,10 @@ int tq_docset_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_
  * (src/collector/mod.rs:186-221) — what every collector whose requires_scoring() is true asks a Weight for
  * (TopDocs::tweak_score / custom_score, a MultiCollector with a scoring child, a user collector that reads the score):
  * every ALIVE matching doc with its BM25 score, however many there are (top-k stops at TQ_MAX_K).
- * out_docs / out_starts are exactly what tq_docset_batch returns for the same queries — same query shapes, same
- * refusals (TQ_MODE_PHRASE and nested queries: TQ_ERR_UNSUPPORTED naming the first such query, nothing launched —
- * also with "docset_trees" = 1, which only concerns the unscored calls), same
+ * out_docs / out_starts are exactly what tq_docset_batch returns for the same queries — same flat query shapes, same
+ * refusals (by default TQ_MODE_PHRASE and nested queries: TQ_ERR_UNSUPPORTED naming the first such query, nothing launched —
+ * also with "docset_trees" = 1, which only concerns the unscored calls; "docset_score_trees" = 1, which only concerns
+ * the scored calls, takes them: below), same
  * capacity protocol — and out_scores[i] is the score of out_docs[i]; one out_cap covers both arrays (host variant, total
  * > out_cap: TQ_ERR_INVALID, out_starts complete, no doc and no score written).  Unlike tq_docset_batch, weights and
  * tf_cache are REQUIRED for every query that has a scoring (non-MustNot, present) list — TQ_ERR_INVALID naming the
@@ -476,7 +478,27 @@ int tq_docset_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_
  * Afterwards tq_last_batch_match_counts / tq_batch_stats.matches as for doc sets, kernel_mask = TQ_KERNEL_DOCSET |
  * TQ_KERNEL_DOCSET_SCORE, and algorithmic_bytes = the doc-set figure (lists x bitmap words x 4 + 4 x docs) + per doc
  * 4 (score) + 1 (fieldnorm byte) + per scoring list of every query 8 bytes per 32 docs of the segment (a bitmap word
- * with its rank: the most a list's presence and posting index cost; tf bytes are not counted). */
+ * with its rank: the most a list's presence and posting index cost; tf bytes are not counted).
+ * With the option "docset_score_trees" = 1 both variants TAKE what the unscored calls take under "docset_trees" = 1:
+ * TQ_MODE_PHRASE (phrase_offsets required), phrases as boolean clauses and nested queries, within the tree planner's
+ * limits (2..8 terms per phrase, a field with positions, minimums <= 15).  The two options are independent.  weights and
+ * tf_cache are REQUIRED for such a query (NULL, or a weight that is not finite: TQ_ERR_INVALID naming the query) and mean
+ * what they mean to tq_search_batch: every term carries its own weight, each term of a phrase atom the phrase's weight,
+ * a plain TQ_MODE_PHRASE query its weight in weights[0].  What the tree planner refuses — a negative boost inside a
+ * nested query, a TQ_TERM_ALL clause inside a tree, a phrase on a field without positions, "use_dense" off — fails the
+ * whole batch before any launch with the planner's code and "query N"; the segment stays usable.
+ * The rows of such a query are written as for the unscored call (docset_tree_bits_kernel, then the count / scan / write
+ * passes) and scored by docset_tree_score_kernel behind the write pass, one lane per doc over the planner's record:
+ * tree_kernel's per-doc scoring stage — bitmap word, rank, tf byte (255: the packed tf of the posting's block); a phrase
+ * atom scores bm25(its weight, norm, number of aligned positions) from the full cursor walk; sums in Intersection::score
+ * / RequiredOptionalScorer / SumCombiner order, a Should clause only where it matches — so a doc scores bit for bit
+ * what tq_search_batch's TQ_KERNEL_TREE gives it.  The flat scoring pass writes nothing over such a row.
+ * kernel_mask of a scored call that held such a query: TQ_KERNEL_DOCSET | TQ_KERNEL_DOCSET_SCORE |
+ * TQ_KERNEL_DOCSET_TREE | TQ_KERNEL_DOCSET_TREE_SCORE (flat queries only: the two bits above, whatever the option's
+ * value).  Such a query adds to algorithmic_bytes the unscored tree figure, (lists + 2) x bitmap words x 4, per output
+ * doc 4 (doc) + 4 (score) + 1 (fieldnorm), and per non-MustNot list of the tree (under a MustNot on neither level) 8
+ * bytes per 32 docs of the segment; positions are not counted.  matches / tq_last_batch_match_counts as for the
+ * unscored call. */
 int tq_docset_scored_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
                            uint32_t *out_docs, float *out_scores, uint64_t out_cap, uint64_t *out_starts);
 /* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream): nothing is written at or past
@@ -520,6 +542,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_DOCSET_SCORE 0x4000u /* docset_score kernel (tq_docset_scored_batch*: the scoring pass behind the write pass) */
 #define TQ_KERNEL_ALL 0x8000u          /* all_kernel (ALL-BASED queries: TQ_TERM_ALL clauses, over bitmap words) */
 #define TQ_KERNEL_DOCSET_TREE 0x10000u /* docset_tree_bits_kernel (tq_docset_batch*, option "docset_trees": phrases and nested queries as match bits) */
+#define TQ_KERNEL_DOCSET_TREE_SCORE 0x20000u /* docset_tree_score_kernel (tq_docset_scored_batch*, option "docset_score_trees": the scores of such rows) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -599,7 +622,11 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        "docset_trees" (0/1, default 0; any other value: TQ_ERR_INVALID): tq_docset_batch / tq_docset_batch_device
  *        also take TQ_MODE_PHRASE, phrases as boolean clauses and nested queries (TQ_KERNEL_DOCSET_TREE; one scratch
  *        bitmap per such query, see "doc sets"); 0: they are refused with TQ_ERR_UNSUPPORTED as before.  The scored
- *        variants refuse them under either value,
+ *        variants do not look at it,
+ *        "docset_score_trees" (0/1, default 0; any other value: TQ_ERR_INVALID): tq_docset_scored_batch /
+ *        tq_docset_scored_batch_device also take those shapes (TQ_KERNEL_DOCSET_TREE | TQ_KERNEL_DOCSET_TREE_SCORE; weights
+ *        and tf_cache required, see "doc sets with scores"); 0: refused with TQ_ERR_UNSUPPORTED as before.  Independent
+ *        of "docset_trees", which the unscored variants alone look at,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

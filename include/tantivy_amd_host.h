@@ -100,12 +100,15 @@ int tqh_count_prepared(tqh_searcher *s, uint64_t *counts);
  * every segment (tq_docset_batch) ordered by (segment_ord, doc) — the DocAddresses merge_fruits unions.  out_starts has
  * n + 1 entries and is filled whenever the queries are valid; if out_starts[n] exceeds out_cap the call fails, has
  * written no pair, and the caller retries with buffers of out_starts[n] entries.  Flat queries only (tantivy_amd.h,
- * "doc sets"): a phrase or a nested query fails the batch as unsupported. */
+ * "doc sets"): a phrase or a nested query fails the batch as unsupported, unless the option "docset_trees" is set on
+ * every segment. */
 int tqh_docset_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, uint64_t out_cap,
                         uint64_t *out_starts);
 /* The same for a collector that needs scores (Weight::for_each: TopDocs::tweak_score / custom_score, a MultiCollector
  * with a scoring child): out_scores[i] = the BM25 score of pair i under the searcher's index-wide statistics
- * (tq_docset_scored_batch on every segment).  Same rows, same capacity protocol; one out_cap covers the three arrays. */
+ * (tq_docset_scored_batch on every segment).  Same rows, same capacity protocol; one out_cap covers the three arrays.
+ * A phrase or a nested query fails the batch as unsupported unless the option "docset_score_trees" (tantivy_amd.h, "doc
+ * sets with scores") is set on every segment; "docset_trees" does not concern this call. */
 int tqh_docset_scored_prepared(tqh_searcher *s, uint32_t *out_segment_ords, uint32_t *out_docs, float *out_scores,
                                uint64_t out_cap, uint64_t *out_starts);
 /* Collector::collect_segment of the prepared batch on one segment: [n][k] sorted. */

@@ -58,10 +58,12 @@ KERNEL_DOCSET = 0x2000
 KERNEL_DOCSET_SCORE = 0x4000
 KERNEL_ALL = 0x8000
 KERNEL_DOCSET_TREE = 0x10000
+KERNEL_DOCSET_TREE_SCORE = 0x20000
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
-                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree"}
+                0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
+                0x20000: "docset_tree_score"}
 
 
 def kernel_names(mask):
@@ -879,9 +881,15 @@ class DeviceIndex:
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =
-        np.float32[256] (or None).  -> (array, keep-alive list)"""
+        np.float32[256] (or None), or a list of one per query (the same object = the same pointer; None: left NULL).
+        -> (array, keep-alive list)"""
         qs, keep = self._raw_flat_queries(queries, segment_ord)
-        if cache is not None:
+        per_query = None
+        if isinstance(cache, (list, tuple)):
+            held = {}
+            per_query = [None if c is None else held.setdefault(id(c), np.ascontiguousarray(c, np.float32)) for c in cache]
+            keep += list(held.values())
+        elif cache is not None:
             cache = np.ascontiguousarray(cache, np.float32)
             keep.append(cache)
         for i in range(len(queries)):
@@ -889,7 +897,10 @@ class DeviceIndex:
                 ws = (C.c_float * max(1, len(weights[i])))(*weights[i])
                 keep.append(ws)
                 qs[i].weights = C.cast(ws, C.POINTER(C.c_float))
-            if cache is not None:
+            if per_query is not None:
+                if per_query[i] is not None:
+                    qs[i].tf_cache = _f32(per_query[i])
+            elif cache is not None:
                 qs[i].tf_cache = _f32(cache)
         return qs, keep
 
@@ -914,6 +925,23 @@ class DeviceIndex:
         return lib().tq_docset_scored_batch_device(self.segment_raw(segment_ord), qs, len(queries), d_docs.data_ptr(),
                                                    d_scores.data_ptr(), int(cap), d_starts.data_ptr(),
                                                    C.c_void_p(stream) if stream else None)
+
+    def raw_search_trees(self, queries, weights, cache, k, opts=None, segment_ord=0):
+        """Direct tq_search_batch_opts over the structs raw_docset_scored sends (_raw_scored_queries: atom_of /
+        phrase_offsets / clause_min_should included), every query with top-k size k; weights / cache as
+        raw_docset_scored takes them; opts = (exhaustive, bound_slack_ppm) or None
+        -> (scores[n, k], docs[n, k], counts[n])."""
+        n = len(queries)
+        qs, keep = self._raw_scored_queries(queries, weights, cache, segment_ord)
+        for i in range(n):
+            qs[i].k = int(k)
+        scores = np.zeros((max(1, n), k), np.float32)
+        docs = np.zeros((max(1, n), k), np.uint32)
+        counts = np.zeros(max(1, n), np.uint32)
+        o = TqSearchOpts(int(opts[0]), int(opts[1])) if opts is not None else None
+        _check(lib().tq_search_batch_opts(self.segment_raw(segment_ord), qs, n, k, _f32(scores), _u32(docs), _u32(counts),
+                                          C.byref(o) if o is not None else None))
+        return scores[:n], docs[:n], counts[:n]
 
     def raw_count(self, queries, weights, cache, segment_ord=0):
         """Direct tq_count_batch (Count collector): alive matches per query."""

@@ -21,6 +21,7 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_docset.cpp"),
     os.path.join(HERE, "csrc", "tq_docset_score.hip"),
     os.path.join(HERE, "csrc", "tq_docset_tree.hip"),
+    os.path.join(HERE, "csrc", "tq_docset_tree_score.hip"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_misc.hip"),
@@ -75,7 +76,7 @@ def csrc_hash():
 
 # which translation unit a scan kernel of a rocprofv3 trace comes from
 KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip", "union_kernel": "tq_union.hip",
-                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "tree_kernel": "tq_tree.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
+                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "docset_tree_score_kernel": "tq_docset_tree_score.hip", "tree_kernel": "tq_tree.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
                 "phrase_sweep_kernel": "tq_phrase.hip", "phrase_kernel": "tq_phrase.hip"}
 
 

@@ -9,6 +9,11 @@
 // passes see one Must list that is bits in scratch.  The host variant with one sub-batch keeps the bits between its
 // count and write passes, so positions are walked once; with several sub-batches each one is evaluated twice, like the
 // scattered lists.
+// Option "docset_score_trees": the same shapes in the scored calls.  The tree is planned from the caller's weights, its
+// tf_cache joins the batch's cache blob, and tq_docset_tree_score.hip scores its rows behind every sub-batch's write pass,
+// next to the flat pass — which is launched over the runs of flat queries between the trees and so writes nothing over a
+// tree's row.  The lists' tables (their own or the probe pool's) live for the whole call; only the result bits are the
+// sub-batch's, and the scoring pass does not read them.
 #include "tq_internal.hpp"
 
 #include <deque>
@@ -115,12 +120,16 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
   if (fc.all_based) memcpy(&sq.all_base_bits, &fc.all_base, sizeof(float));
 }
 
-void docset_tree_view(const tq_query &q, TreeView &v) {
+void docset_tree_view(const tq_query &q, TreeView &v, bool scored) {
   static_assert(TQ_MAX_TERMS == 16, "kOnes holds one weight per term");
   static const float kOnes[TQ_MAX_TERMS] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
   v.q = q;
-  v.q.weights = kOnes;  // (plan_tree_query reads them and refuses negative boosts: a doc set has neither)
+  if (!scored) v.q.weights = kOnes;  // (plan_tree_query reads them and refuses negative boosts: a doc set has neither)
   if (q.mode != TQ_MODE_PHRASE) return;
+  if (scored) {  // the phrase's weight on every term: the kernel reads the atom's weight at its first PRESENT term
+    for (uint32_t i = 0; i < TQ_MAX_TERMS; ++i) v.weights[i] = q.n_terms ? q.weights[0] : 1.0f;
+    v.q.weights = v.weights;
+  }
   for (uint32_t i = 0; i < q.n_terms && i < TQ_MAX_TERMS; ++i) {
     v.occurs[i] = TQ_MUST;
     v.clause_of[i] = v.atom_of[i] = 0;
@@ -172,13 +181,18 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   uint64_t algo_bytes = 0;
   std::vector<uint32_t> tree_q;     // the queries that take the tree path (option "docset_trees"), ascending
   std::vector<TqdTreeQuery> tqs;    // ... and their records, in the same order
-  const bool trees_on = s->opt.docset_trees && !scored && !count_only;
+  const bool trees_on = count_only ? false : scored ? s->opt.docset_score_trees != 0 : s->opt.docset_trees != 0;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     const char *why = "";
     FlatClauses fc;
     const tq_query &q = queries[qi];
     const int rc = docset_expression(s, q, dqs[qi], &why, scored ? &fc : nullptr);
     if (rc == FLAT_UNSUPPORTED && trees_on && !query_has_all(q) && (q.mode == TQ_MODE_PHRASE || bool_query_is_tree(q))) {
+      if (scored) {  // the rule of the flat queries; plan_tree_query reads every term's weight
+        if (!q.weights || !q.tf_cache) return fail(TQ_ERR_INVALID, "%s: query %u: null weights / tf_cache", fn, qi);
+        for (uint32_t i = 0; i < (q.mode == TQ_MODE_PHRASE ? std::min(q.n_terms, 1u) : q.n_terms); ++i)
+          if (!std::isfinite(q.weights[i])) return fail(TQ_ERR_INVALID, "%s: query %u: weight %u is not finite", fn, qi, i);
+      }
       tree_q.push_back(qi);
       continue;
     }
@@ -216,7 +230,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     bool built = false;
     for (const uint32_t qi : tree_q) {
       views.emplace_back();
-      docset_tree_view(queries[qi], views.back());
+      docset_tree_view(queries[qi], views.back(), scored);
       const int prc = build_tree_query_probe_tables(s, views.back().q, &built);
       if (prc != TQ_OK) return prc;
     }
@@ -233,6 +247,23 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       dq.n_terms = dq.narrow = dq.clause_end = 1u;
       // every list's bits once + the result word written and read back
       algo_bytes += ((uint64_t)tqs[i].n_terms + 2u) * n_words * 4u;
+      if (!scored) continue;
+      if (tqs[i].n_terms) {  // its cache in the blob the flat queries use: one index space for both scoring kernels
+        const float *tc = queries[tree_q[i]].tf_cache;
+        uint32_t ci = (uint32_t)caches.size();
+        while (ci > 0 && caches[ci - 1] != tc) --ci;
+        if (ci == 0) {
+          caches.push_back(tc);
+          ci = (uint32_t)caches.size();
+        }
+        tqs[i].cache_idx = ci - 1u;
+      }
+      // the scoring pass: one bitmap word per 32 docs for every list that scores (under no MustNot on either level)
+      uint32_t n_scoring = 0;
+      for (uint32_t c = 0; c < tqs[i].n_clauses; ++c)
+        for (uint32_t t = tqs[i].first_term[c]; t < tqs[i].first_term[c + 1u]; ++t)
+          n_scoring += tqs[i].outer[c] != TQ_MUST_NOT && tqs[i].inner[t] != TQ_MUST_NOT ? 1u : 0u;
+      algo_bytes += (uint64_t)n_scoring * n_words * 8u;
     }
   }
   // sub-batches; a list without a bitmap gets a slot of the scratch for the duration of its sub-batch
@@ -298,7 +329,8 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (wrc != TQ_OK) return wrc;
   }
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE);
+  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
+                         (scored && !tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u);
   s->stats.algorithmic_bytes = algo_bytes;
   s->stats_pending = false;
   s->last_batch_queries = 0;
@@ -317,9 +349,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   const size_t q_bytes = (size_t)n_queries * sizeof(TqkDocsetQuery), wg_bytes = wgs.size() * sizeof(uint4);
   const size_t sq_bytes = sqs.size() * sizeof(TqkScoreQuery), cache_bytes = caches.size() * 256u * sizeof(float);
   const size_t tree_bytes = tqs.size() * sizeof(TqdTreeQuery);
+  // scored: behind the records, which query of its sub-batch every tree is (tq_docset_tree_score.hip: tile_counts / tile_offs)
+  static_assert(sizeof(TqdTreeQuery) % sizeof(uint32_t) == 0, "the map stands right behind the records");
+  const size_t tree_map_bytes = scored ? tqs.size() * sizeof(uint32_t) : 0u;
   const size_t max_entries = (size_t)max_sub_n * n_tiles;
-  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes + tree_bytes);
-  if (rc == TQ_OK && tree_bytes) rc = s->d_docset_trees.ensure(tree_bytes);
+  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes + tree_bytes + tree_map_bytes);
+  if (rc == TQ_OK && tree_bytes) rc = s->d_docset_trees.ensure(tree_bytes + tree_map_bytes);
   if (rc == TQ_OK && scored) rc = s->d_docset_squeries.ensure(sq_bytes);
   if (rc == TQ_OK && scored) rc = s->d_docset_caches.ensure(std::max<size_t>(cache_bytes, 256u * sizeof(float)));
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
@@ -354,7 +389,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   if (tree_bytes) {
     uint8_t *const h_tq = (uint8_t *)s->h_docset.p + q_bytes + wg_bytes + sq_bytes + cache_bytes;
     memcpy(h_tq, tqs.data(), tree_bytes);
-    HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_bytes, hipMemcpyHostToDevice, st));
+    if (tree_map_bytes) {
+      uint32_t *const map = (uint32_t *)(h_tq + tree_bytes);
+      for (const SubBatch &sb : subs)
+        for (uint32_t t = sb.t0; t < sb.t1; ++t) map[t] = tree_q[t] - sb.q0;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_bytes + tree_map_bytes, hipMemcpyHostToDevice, st));
   }
 
   uint64_t *const d_starts = device_out ? out_starts : (uint64_t *)s->d_docset_starts.p;
@@ -406,17 +446,44 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       TqkScoreParams sp{};
       sp.seg = s->dseg;
       sp.terms = s->d_terms;
-      sp.queries = (const TqkScoreQuery *)s->d_docset_squeries.p + sb.q0;
       sp.caches = (const float *)s->d_docset_caches.p;
-      sp.tile_counts = p.tile_counts;
-      sp.tile_offs = p.tile_offs;
       sp.out_docs = d_docs;
       sp.out_scores = d_scores;
       sp.out_cap = cap;
-      sp.n_queries = p.n_queries;
       sp.n_tiles = n_tiles;
       sp.any_blocks = sb.score_blocks ? 1u : 0u;
-      e = tqk_launch_docset_score(sp, st);
+      // the flat pass over the runs of flat queries between the sub-batch's trees (no tree: the one launch it always was):
+      // a tree's row is the tree pass's alone — the flat kernel would store the empty sum over it
+      uint32_t r0 = sb.q0;
+      for (uint32_t t = sb.t0; t <= sb.t1 && e == hipSuccess; ++t) {
+        const uint32_t r1 = t < sb.t1 ? tree_q[t] : sb.q1;
+        if (r1 > r0) {
+          sp.queries = (const TqkScoreQuery *)s->d_docset_squeries.p + r0;
+          sp.tile_counts = p.tile_counts + (size_t)(r0 - sb.q0) * n_tiles;
+          sp.tile_offs = p.tile_offs + (size_t)(r0 - sb.q0) * n_tiles;
+          sp.n_queries = r1 - r0;
+          e = tqk_launch_docset_score(sp, st);
+        }
+        r0 = r1 + 1u;
+      }
+      if (e == hipSuccess && sb.t1 > sb.t0) {
+        TqkDocsetTreeScoreParams tsp{};
+        tsp.seg = s->dseg;
+        tsp.terms = s->d_terms;
+        tsp.queries = (const TqdTreeQuery *)s->d_docset_trees.p + sb.t0;
+        tsp.query_of = (const uint32_t *)((const uint8_t *)s->d_docset_trees.p + tree_bytes) + sb.t0;
+        tsp.caches = (const float *)s->d_docset_caches.p;
+        tsp.table_base = (const uint8_t *)s->share_table_lo;
+        tsp.tile_counts = p.tile_counts;
+        tsp.tile_offs = p.tile_offs;
+        tsp.out_docs = d_docs;
+        tsp.out_scores = d_scores;
+        tsp.out_cap = cap;
+        tsp.n_queries = sb.t1 - sb.t0;
+        tsp.n_tiles = n_tiles;
+        tsp.any_phrase = sb.any_phrase ? 1u : 0u;
+        e = tqk_launch_docset_tree_score(tsp, st);
+      }
     }
     if (e != hipSuccess) return fail(TQ_ERR_HIP, "doc-set kernel launch: %s", hipGetErrorString(e));
     return TQ_OK;

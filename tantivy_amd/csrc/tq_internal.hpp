@@ -196,6 +196,7 @@ struct Options {
   int count_bitmap_ratio = 128;  // Count: bitmap words instead of a scan if the driving clause holds >= max_doc / ratio postings per list
   int docset_temp_lists = 0;     // doc sets: lists without a bitmap scattered per launch (0 = what TQ_COUNT_TEMP_MB holds, at most 4096)
   int docset_trees = 0;          // doc sets: phrases and nested boolean queries through tq_docset_tree.hip (0 = refused, as before)
+  int docset_score_trees = 0;    // scored doc sets: the same shapes, scored by tq_docset_tree_score.hip (0 = refused, as before)
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
   // tq_submit / tq_search_one: how long the leader of a batch waits for the callers of the previous
   // batch to come back with their next query (0 = launch with whatever is pending)
@@ -927,12 +928,14 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false);
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
-// Must clause holding one phrase atom" with the caller's phrase_offsets.
+// Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the
+// caller's weights (not NULL) are kept, a TQ_MODE_PHRASE query's weights[0] on every term of its atom.
 struct TreeView {
   tq_query q;
   uint8_t occurs[TQ_MAX_TERMS], clause_of[TQ_MAX_TERMS], atom_of[TQ_MAX_TERMS], nested_occurs[TQ_MAX_TERMS];
+  float weights[TQ_MAX_TERMS];
 };
-void docset_tree_view(const tq_query &q, TreeView &v);  // (q.n_terms <= TQ_MAX_TERMS)
+void docset_tree_view(const tq_query &q, TreeView &v, bool scored = false);  // (q.n_terms <= TQ_MAX_TERMS)
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);

@@ -382,6 +382,25 @@ struct TqkScoreParams {
   uint32_t any_blocks;             // some list of the sub-batch is TQK_SCORE_BLOCKS (selects the instantiation with LDS)
 };
 hipError_t tqk_launch_docset_score(const TqkScoreParams &p, hipStream_t st);
+// ---- ... of phrases and nested boolean queries (tq_docset_tree_score.hip, option "docset_score_trees"): the pass behind the
+// write pass over the sub-batch's TREE queries, whose rows the flat pass leaves alone.  Tree i of the launch is query
+// query_of[i] of the sub-batch: that is where its tile_counts / tile_offs stand.
+struct TqkDocsetTreeScoreParams {
+  TqdSegment seg;
+  const TqdTerm *terms;
+  const TqdTreeQuery *queries;     // [n_queries] as plan_tree_query leaves them, cache_idx set (k / part_start are not read)
+  const uint32_t *query_of;        // [n_queries] tree -> query of the sub-batch
+  const float *caches;             // n_caches x 256: the blob the flat pass reads
+  const uint8_t *table_base;
+  const uint32_t *tile_counts;     // [sub-batch queries][n_tiles] and their prefix sum
+  const uint64_t *tile_offs;
+  const uint32_t *out_docs;        // the rows the write pass has just stored
+  float *out_scores;               // out_scores[i] = the score of out_docs[i]; nothing at or past out_cap
+  uint64_t out_cap;
+  uint32_t n_queries, n_tiles;
+  uint32_t any_phrase;             // some tree of the launch has a phrase atom (selects the instantiation with position cursors)
+};
+hipError_t tqk_launch_docset_tree_score(const TqkDocsetTreeScoreParams &p, hipStream_t st);
 hipError_t tqk_launch_ashare(const TqkAShareParams &p, int kpl, hipStream_t st);
 uint32_t tqk_ashare_waves_per_cu();  // resident wavefronts per CU the kernel is built for
 uint32_t tqk_bshare_waves_per_cu();  // ... its boolean instantiation

@@ -333,7 +333,9 @@ class Searcher {
   std::vector<std::vector<DocAddress>> docset_batch(const std::vector<Weight> &weights);
   // the same for a collector whose requires_scoring() is true (Weight::for_each, weight.rs:9-18,89-97: TopDocs::tweak_score
   // / custom_score, a MultiCollector with a scoring child): every address with its BM25 score under the searcher's
-  // index-wide statistics (tq_docset_scored_batch)
+  // index-wide statistics (tq_docset_scored_batch).  A phrase or a nested query throws Unsupported unless the option
+  // "docset_score_trees" is set on every segment: then its rows come back with tree_kernel's scores ("docset_trees"
+  // concerns docset_batch alone)
   std::vector<std::vector<std::pair<DocAddress, Score>>> docset_scored_batch(const std::vector<Weight> &weights);
   // collect_segment for a batch on one segment: per-segment top-(offset+limit), sorted
   void collect_segment_batch(size_t segment_ord, const std::vector<Weight> &weights, uint32_t k,

@@ -22,7 +22,15 @@ scan, the only device route that visited every match of these shapes before, and
 fill of the output buffer, what a write of the same size costs at the least.  Written to
 profiles/docset_tree_bench.json.
 
-  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3] [--scores | --trees]"""
+--trees --scores: the two batches of --trees through tq_docset_scored_batch_device (option "docset_score_trees",
+tq_docset_tree_score.hip), alternating with the unscored call in one process, HIP events around all kernels of a call,
+the median of --reps (default here: 10) warm repetitions: the unscored and the scored call, the scoring pass as their
+difference, what the byte model predicts for the bytes the pass adds at the fill bandwidth of the same run, and the
+exhaustive top-10 search of the same queries (tq_search_batch: the route that scored every match of these shapes
+before, ten rows per query); a sample of rows is checked against the oracle in the same process.  Written to
+profiles/docset_tree_scored_bench.json.
+
+  python tools/bench_docset.py [--docs 10000000] [--reps 20] [--warmup 3] [--scores] [--trees]"""
 import argparse
 import json
 import os
@@ -237,6 +245,108 @@ def tree_child(args):
     dev.close()
 
 
+def tree_scored_child(args):
+    import torch
+
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a GPU")
+    from oracle import oracle as O
+    import tantivy_amd as T
+
+    seg = O.synth_segment(args.docs, n_terms=args.terms, with_positions=True, phrase_terms=PHRASE_TERMS)
+    dev = T.DeviceIndex([seg], devices=[0])
+    dev.set_option("timing", 1)
+    dev.set_option("docset_trees", 1)
+    dev.set_option("docset_score_trees", 1)
+    n = args.queries
+    queries, forms = _tree_queries(O, T, args.child, n, args.terms)
+    counts = dev.count(queries)  # (it also builds the probe tables every route uses)
+    while int(counts.sum()) * 8 > OUT_BYTES_MAX and n > 1:  # size the batch by its output: docs + scores
+        n = max(1, int(n * OUT_BYTES_MAX / (int(counts.sum()) * 8) * 0.95))
+        queries, forms, counts = queries[:n], forms[:n], counts[:n]
+    total = int(counts.sum())
+    # the oracle's weights: one Bm25Weight per term, one per phrase on each of its terms; the segment's cache
+    avg = seg.avg_fieldnorm
+    one = O.bm25_for_one_term(1, seg.max_doc, avg)
+    cache = np.array(list(one.cache), np.float32)
+    w_of = {}
+    weights = []
+    for q, f in zip(queries, forms):
+        if f[0] == "phrase":
+            weights.append([float(O.default_weights(seg, f[1], O.MODE_PHRASE)[0].weight)] * len(f[1]))
+            continue
+        for t in q[1]:
+            if t not in w_of:
+                w_of[t] = float(O.bm25_for_one_term(seg.terms[t].doc_freq, seg.max_doc, avg).weight)
+        weights.append([w_of[t] for t in q[1]])
+    d_docs = torch.empty(max(1, total), dtype=torch.int32, device="cuda")
+    d_docs2 = torch.empty(max(1, total), dtype=torch.int32, device="cuda")
+    d_scores = torch.empty(max(1, total), dtype=torch.float32, device="cuda")
+    d_starts = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    stream = torch.cuda.Stream()
+    plain_ms, scored_ms = [], []
+    for i in range(args.warmup + args.reps):
+        rc = dev.raw_docset_device(queries, d_docs2, total, d_starts, stream=stream.cuda_stream)
+        assert rc == 0, T.binding.lib().tq_last_error()
+        a = dev.last_batch_stats()  # waits for the batch; kernel_ms = HIP events around all kernels of the call
+        rc = dev.raw_docset_scored_device(queries, d_docs, d_scores, total, d_starts, stream=stream.cuda_stream,
+                                          weights=weights, cache=cache)
+        assert rc == 0, T.binding.lib().tq_last_error()
+        b = dev.last_batch_stats()
+        if i >= args.warmup:
+            plain_ms.append(a["kernel_ms"])
+            scored_ms.append(b["kernel_ms"])
+    assert a["kernels"] == ["docset", "docset_tree"] and a["matches"] == total, a
+    assert b["kernels"] == ["docset", "docset_score", "docset_tree", "docset_tree_score"] and b["matches"] == total, b
+    assert torch.equal(d_docs, d_docs2)  # the rows are the unscored call's
+    starts = d_starts.cpu().numpy()
+    assert int(starts[-1]) == total and np.array_equal(np.diff(starts), counts.astype(np.int64))
+    checked = 0
+    for q in range(0, n, max(1, n // 6)):  # a sample of rows against the oracle: a phrase bit-equal, a tree within 1e-5
+        if counts[q] > 2_000_000:
+            continue
+        f = forms[q]
+        if f[0] == "phrase":
+            wd, ws = O.match_all(seg, f[1], O.MODE_PHRASE, phrase_offsets=f[2])
+        else:
+            wd, ws = O.tree_match_all(seg, f[1], f[2])
+        got_d = d_docs[int(starts[q]): int(starts[q + 1])].cpu().numpy().view(np.uint32)
+        got_s = d_scores[int(starts[q]): int(starts[q + 1])].cpu().numpy()
+        ws = np.asarray(ws, np.float32)
+        assert np.array_equal(got_d, np.asarray(wd, np.uint32)), queries[q]
+        assert np.array_equal(got_s, ws) if f[0] == "phrase" else np.allclose(got_s, ws, rtol=1e-5, atol=0), queries[q]
+        checked += 1
+    ex_ms = []
+    for i in range(1 + 3):  # the exhaustive top-10 search of the same queries
+        dev.raw_search_trees(queries, weights, cache, 10, (1, 0))
+        e = dev.last_batch_stats()
+        if i >= 1:
+            ex_ms.append(e["kernel_ms"])
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fill = []
+    for i in range(args.warmup + args.reps):  # the fill bandwidth of this run: a device memset of the output buffer
+        ev0.record()
+        d_docs.fill_(i)
+        ev1.record()
+        torch.cuda.synchronize()
+        if i >= args.warmup:
+            fill.append(ev0.elapsed_time(ev1))
+    p_ms, s_ms, fill_ms = float(np.median(plain_ms)), float(np.median(scored_ms)), float(np.median(fill))
+    added = int(b["algorithmic_bytes"]) - int(a["algorithmic_bytes"])  # 5 B per doc + 8 B per scoring list per 32 docs
+    fill_gbs = 4 * total / (fill_ms * 1e-3) / 1e9 if total else float("nan")
+    res = {"workload": args.child, "docs": args.docs, "terms": args.terms, "queries": n, "out_docs": total,
+           "unscored_kernel_ms": round(p_ms, 4), "scored_kernel_ms": round(s_ms, 4),
+           "scored_kernel_ms_min": round(float(np.min(scored_ms)), 4),
+           "score_pass_ms": round(s_ms - p_ms, 4),
+           "fill_ms": round(fill_ms, 4), "fill_GBs": round(fill_gbs, 1),
+           "unscored_algorithmic_bytes": int(a["algorithmic_bytes"]), "scored_algorithmic_bytes": int(b["algorithmic_bytes"]),
+           "score_pass_added_bytes": added, "score_pass_model_ms_at_fill_bw": round(added / (fill_gbs * 1e9) * 1e3, 4),
+           "exhaustive_top10_kernel_ms": round(float(np.median(ex_ms)), 4), "exhaustive_kernels": e["kernels"],
+           "reps": args.reps, "warmup": args.warmup, "rows_checked_against_oracle": checked}
+    print("RESULT " + json.dumps(res))
+    dev.close()
+
+
 def scored_run(args, O, T, seg, dev, queries, total, d_docs, d_starts, stream, fill_ms):
     """The batch through tq_docset_scored_batch_device, alternating with the unscored call; -> the extra result fields."""
     import torch
@@ -309,7 +419,7 @@ def main():
     ap.add_argument("--docs", type=int, default=10_000_000)
     ap.add_argument("--terms", type=int, default=256)
     ap.add_argument("--queries", type=int, default=None, help="queries per batch (default: 1000; --trees: 512, one scratch bitmap each)")
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=None, help="timed repetitions (default: 20; --trees --scores: 10)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--scores", action="store_true")
@@ -317,15 +427,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", choices=WORKLOADS + TREE_WORKLOADS)
     args = ap.parse_args()
-    if args.scores and args.trees:
-        raise SystemExit("--scores or --trees, not both (the scored calls refuse trees)")
+    if args.reps is None:
+        args.reps = 10 if args.scores and (args.trees or args.child in TREE_WORKLOADS) else 20
     if args.queries is None:
         args.queries = 512 if args.trees or args.child in TREE_WORKLOADS else 1000
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "docset_tree_bench.json" if args.trees else
+        args.out = os.path.join(ROOT, "profiles", "docset_tree_scored_bench.json" if args.trees and args.scores else
+                                "docset_tree_bench.json" if args.trees else
                                 "docset_scored_bench.json" if args.scores else "docset_bench.json")
+    if args.child in TREE_WORKLOADS:
+        return tree_scored_child(args) if args.scores else tree_child(args)
     if args.child:
-        return tree_child(args) if args.child in TREE_WORKLOADS else child(args)
+        return child(args)
     results = []
     for wl in (TREE_WORKLOADS if args.trees else WORKLOADS):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", wl, "--docs", str(args.docs), "--terms", str(args.terms),
