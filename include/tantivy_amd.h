@@ -212,6 +212,56 @@ int tq_term_prepare_batch(tq_segment *seg, const tq_term_info *infos, uint32_t n
  * depends on the order of the first queries.  Lists beyond the 40 named are ignored. */
 int tq_segment_reserve_columns(tq_segment *seg, const uint64_t *postings_offs, uint32_t n);
 
+/* ---- term sets ----
+ * replaces: the bitset loop of AutomatonWeight::scorer (src/query/automaton_weight.rs:87-111) for one segment — what
+ * FuzzyTermQuery, RegexQuery, TermSetQuery and every other AutomatonWeight query do: the docs of N posting lists OR-ed
+ * into a BitSet(max_doc) under ConstScorer(BitSetDocSet, boost) (src/query/const_score_query.rs:95-148,
+ * src/query/bitset/mod.rs:91-93).  members = n handles from tq_term_prepare(_batch) — the caller gets their TermInfos
+ * from its own term stream, exactly where the reference does; TQ_TERM_ABSENT members and duplicates are skipped; n == 0
+ * or no present member gives a valid handle with an empty bitmap (the reference keeps a ConstScorer over an empty
+ * bitset, not an EmptyScorer); a member that is TQ_TERM_ALL, a set, out of range or released: TQ_ERR_INVALID.  n up to
+ * 2^20.  Built on the segment's stream (tq_termset.hip): members with a bitmap are OR-ed word-wise in one launch, the
+ * others scattered block by block, a device scan writes the rank directory; the call returns once the set's doc count
+ * is known (one small blocking copy).  The members stay what they were.
+ * The result is a {32 doc bits, docs before the word} table of ceil(max_doc / 32) words — the layout of the dense
+ * lists' bitmaps, read unchanged by every bitmap kernel — counted in tq_segment_stats.bitmap_bytes but NOT against
+ * "dense_budget_x" (which ordinary lists get bitmaps does not depend on sets).  Deleted docs are in it, as in the
+ * reference's bitset; the alive filter applies where it always does.
+ * The handle is a slot of the segment's term table and an entry of tq_query.terms like any other.  Wherever the set is
+ * present it scores weights[i] AS GIVEN — the caller passes boost, or boost * score for ConstScoreQuery: no BM25, no
+ * fieldnorm, no tf; its cost, wherever clauses are sorted by cost, is its doc count (BitSet::len: the reference's
+ * size_hint).  Allowed in TQ_MODE_AND, TQ_MODE_OR and flat TQ_MODE_BOOL, also as one of several entries sharing a
+ * clause_of value (`+a +(b OR set)`), several sets per query.
+ *   tq_count_batch            never a scan: count_bitmap_kernel whatever "count_bitmap_ratio" says, the doc-set count
+ *                             pass for "at least m of n"
+ *   tq_docset_batch*          the set's table is one more bitmap of the expression
+ *   tq_docset_scored_batch*   presence from the bitmap word, score = weights[i], summed in the usual order
+ *   tq_search_batch*, tq_submit / tq_search_one: the reference takes the generic unpruned scorer path as soon as one
+ *                             scorer of a query is not a TermScorer (boolean_weight.rs:44-86); here the query runs as
+ *                             TQ_KERNEL_TREE whatever its mode, its other lists reached through bitmaps (their own or
+ *                             the probe pool's) — "use_dense" off, tables outside one 32 GB span or a negative weight:
+ *                             TQ_ERR_UNSUPPORTED as for any tree.  Nothing is pruned: "exhaustive" 0 and 1 give the same
+ *                             rows and tq_last_batch_match_counts is the doc-set size.
+ *   beside TQ_TERM_ALL        counts and (scored) doc sets take sets in any role; top-k takes them as MustNot lists
+ *                             (`+* -set`); a Should set beside an All clause in tq_search_batch*: TQ_ERR_UNSUPPORTED
+ * Refused, with the query index in tq_last_error(), nothing launched and the segment usable: a set in TQ_MODE_PHRASE or
+ * carrying TQ_NESTED_PHRASE (TQ_ERR_INVALID); a set in a query with nested_occurs / atom_of structure
+ * (TQ_ERR_UNSUPPORTED); tq_decode_postings / tq_decode_position_deltas of a set (TQ_ERR_INVALID).
+ * In algorithmic_bytes / unique_bytes a set enters, wherever a list enters with its postings_len, with
+ * ceil(max_doc / 32) * 4.
+ * With the option "timing" set tq_term_set_prepare leaves the build in the segment's tq_batch_stats for
+ * tq_last_batch_stats, in place of the last batch's figures: kernel_ms = total_ms = the HIP-event time from the zeroing of
+ * the table to the end of the rank pass, algorithmic_bytes = the build's HBM model (the scattered members' posting bytes
+ * + 4 B per 32 docs per member with a bitmap + 8 B per 32 docs written and read once by the scan), chunks = the members
+ * that were OR-ed word-wise (the others were scattered), batches_averaged = 1, everything else 0. */
+int tq_term_set_prepare(tq_segment *seg, const tq_term_handle *members, uint32_t n, tq_term_handle *out);
+/* *n_docs = docs in the set (deleted ones included), *bytes = its resident bytes, ceil(max_doc / 32) * 8. */
+int tq_term_set_info(tq_segment *seg, tq_term_handle set, uint32_t *n_docs, uint64_t *bytes);
+/* Waits for whatever the segment has in flight on any stream, returns the table and tombstones the slot: a query, a
+ * member list or an info / release call that names it afterwards gets TQ_ERR_INVALID; a later tq_term_set_prepare may
+ * reuse the slot.  tq_segment_free frees the sets still outstanding. */
+int tq_term_set_release(tq_segment *seg, tq_term_handle set);
+
 /* ---- search ----
  * replaces, for each query: TopBySortKeyCollector::collect_segment ->
  * SortBySimilarityScore::collect_segment_top_k -> Weight::for_each_pruning -> {block_wand,

@@ -58,7 +58,16 @@ typedef struct tqh_query {
   const uint8_t *atom_of; /* TQ_MODE_BOOL: terms of one clause_of group sharing an atom_of value are ONE member of the
                              nested query — an intersection of terms one level further down (`+a +((+b +c) d)`:
                              clause_of {0,1,1,1}, atom_of {0,1,1,2}, nested_occurs {-,0,0,0}); NULL = every term its own */
+  /* Term sets (Query::term_set: TermSetQuery and every other AutomatonWeight query — the docs of the named terms OR-ed
+   * into a bitset that scores the boost, tantivy_amd.h "term sets"): terms[i] == TQH_TERM_SET_BASE + j names set j, whose
+   * term ids are set_terms[set_starts[j] .. set_starts[j + 1]); boosts[i] its BoostQuery factor = the score of every doc
+   * of the set.  Every mode but TQ_MODE_PHRASE, as a query of its own or a direct clause; inside a nested query:
+   * TQ_ERR_UNSUPPORTED.  Both NULL: no sets.  The sets are prepared per segment when the batch first runs and released
+   * with the prepared batch. */
+  const uint32_t *set_terms;
+  const uint32_t *set_starts;
 } tqh_query;
+#define TQH_TERM_SET_BASE 0xFFFFFF00u
 
 const char *tqh_last_error(void);
 int tqh_searcher_new(tq_ctx *ctx, tqh_searcher **out);

@@ -102,7 +102,16 @@ class TqhQuery(C.Structure):
                 ("phrase_offsets", C.POINTER(C.c_uint32)), ("occurs", C.POINTER(C.c_uint8)),
                 ("clause_of", C.POINTER(C.c_uint8)), ("min_should_match", C.c_uint32),
                 ("boosts", C.POINTER(C.c_float)), ("nested_occurs", C.POINTER(C.c_uint8)),
-                ("clause_min_should", C.POINTER(C.c_uint8)), ("atom_of", C.POINTER(C.c_uint8))]
+                ("clause_min_should", C.POINTER(C.c_uint8)), ("atom_of", C.POINTER(C.c_uint8)),
+                ("set_terms", C.POINTER(C.c_uint32)), ("set_starts", C.POINTER(C.c_uint32))]
+
+
+TERM_SET_BASE = 0xFFFFFF00  # tqh_query.terms[i] == TERM_SET_BASE + j: the query's term set j (_host_queries)
+
+
+class RawHandle(int):
+    """A tq_term_handle as the C ABI returned it (DeviceIndex.term_set_prepare): DeviceIndex.term_handle passes it
+    through untouched where a plain int is a term id of the dictionary."""
 
 
 _lib = None
@@ -128,6 +137,7 @@ EXPORTS = [
     "tq_docset_batch", "tq_docset_batch_device", "tqh_docset_prepared",
     "tq_docset_scored_batch", "tq_docset_scored_batch_device", "tqh_docset_scored_prepared",
     "tq_all_query_form",
+    "tq_term_set_prepare", "tq_term_set_info", "tq_term_set_release",
 ]
 
 
@@ -183,6 +193,9 @@ def lib():
     L.tqh_docset_scored_prepared.argtypes = [vp, u32p, u32p, f32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_last_batch_query_kernels.argtypes = [vp, u32p, C.c_uint32]
     L.tq_all_query_form.argtypes = [C.POINTER(TqQuery), C.POINTER(TqAllForm)]
+    L.tq_term_set_prepare.argtypes = [vp, u32p, C.c_uint32, u32p]
+    L.tq_term_set_info.argtypes = [vp, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
+    L.tq_term_set_release.argtypes = [vp, C.c_uint32]
     u64p = C.POINTER(C.c_uint64)
     L.tq_encoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.tq_encoder_free.argtypes = [vp]
@@ -520,7 +533,9 @@ class DeviceIndex:
         `+a +(+b -c)` = (MODE_BOOL, [a, b, c], [MUST]*3, [0, 1, 1], 0, {"nested_occurs": [255, 1, 2]}).  A phrase
         inside a boolean query: its terms share an "atom_of" value, carry nested_occurs | NESTED_PHRASE and their
         "phrase_offsets" — `+"a b" +c` = (MODE_BOOL, [a, b, c], [MUST]*3, [0, 0, 1], 0, {"nested_occurs": [0x11, 0x11, 1],
-        "atom_of": [0, 0, 0], "phrase_offsets": [0, 1, 0]})."""
+        "atom_of": [0, 0, 0], "phrase_offsets": [0, 1, 0]}).  A TERM SET (Query::term_set: a TermSetQuery, or the terms a
+        fuzzy / regex automaton matched) stands in the term list as a tuple ("set", [term ids]) in place of a term id —
+        `+a +set(x y z)` = (MODE_AND, [a, ("set", [x, y, z])]); its entry of "boosts" is the score of every doc of the set."""
         n = len(queries)
         qs = (TqhQuery * max(1, n))()
         keep = []
@@ -528,7 +543,20 @@ class DeviceIndex:
             extra = q[-1] if isinstance(q[-1], dict) else None
             if extra is not None:
                 q = q[:-1]
-            mode, terms = q[0], q[1]
+            mode, terms = q[0], list(q[1])
+            if any(isinstance(t, tuple) for t in terms):  # term sets: ("set", [term ids]) -> TERM_SET_BASE + j
+                members, starts = [], [0]
+                for j, t in enumerate(terms):
+                    if isinstance(t, tuple):
+                        assert t[0] == "set", t
+                        members += [int(x) for x in t[1]]
+                        terms[j] = TERM_SET_BASE + len(starts) - 1
+                        starts.append(len(members))
+                sm = (C.c_uint32 * max(1, len(members)))(*members)
+                ss = (C.c_uint32 * len(starts))(*starts)
+                keep += [sm, ss]
+                qs[i].set_terms = C.cast(sm, C.POINTER(C.c_uint32))
+                qs[i].set_starts = C.cast(ss, C.POINTER(C.c_uint32))
             if extra and extra.get("boosts") is not None:
                 ba = (C.c_float * len(terms))(*[float(b) for b in extra["boosts"]])
                 keep.append(ba)
@@ -744,9 +772,29 @@ class DeviceIndex:
         return C.c_void_p(lib().tqh_segment_raw(self._s, segment_ord))
 
     def term_handle(self, term_id, segment_ord=0):
+        if isinstance(term_id, RawHandle):  # (a handle already: a term set of term_set_prepare)
+            return int(term_id)
         if int(term_id) == TERM_ALL:  # (an AllQuery clause names no list: the value is its own handle)
             return TERM_ALL
         return lib().tqh_term_handle(self._s, segment_ord, int(term_id))
+
+    def term_set_prepare(self, term_ids, segment_ord=0):
+        """tq_term_set_prepare on one segment: the OR of the docs of the terms `term_ids` (ids of the term dictionary, or
+        RawHandles / TERM_ABSENT as they are) as a const-scoring list -> RawHandle, which every raw_* helper takes in its
+        term lists in place of a term id."""
+        hs = np.array([self.term_handle(t, segment_ord) for t in term_ids], np.uint32)
+        out = C.c_uint32()
+        _check(lib().tq_term_set_prepare(self.segment_raw(segment_ord), _u32(hs) if hs.size else None, int(hs.size), C.byref(out)))
+        return RawHandle(out.value)
+
+    def term_set_info(self, h, segment_ord=0):
+        """tq_term_set_info -> (docs in the set, resident bytes)."""
+        n_docs, nbytes = C.c_uint32(), C.c_uint64()
+        _check(lib().tq_term_set_info(self.segment_raw(segment_ord), int(h), C.byref(n_docs), C.byref(nbytes)))
+        return int(n_docs.value), int(nbytes.value)
+
+    def term_set_release(self, h, segment_ord=0):
+        _check(lib().tq_term_set_release(self.segment_raw(segment_ord), int(h)))
 
     def decode_postings(self, term_id, doc_freq, segment_ord=0):
         h = self.term_handle(term_id, segment_ord)

@@ -224,6 +224,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_count_out.release();
   s->d_count_bits.release();
   s->d_count_wgs.release();
+  s->d_set_work.release();
   s->d_docset_queries.release();
   s->d_docset_counts.release();
   s->d_docset_offs.release();
@@ -439,7 +440,7 @@ int tq_segment_get_stats(tq_segment *s, tq_segment_stats *out) {
   r.posdir_bytes = s->bytes_posdir;
   r.scratch_bytes = s->d_stage.cap + s->d_stage_alt.cap + s->d_misc.cap + s->d_thr.cap + s->d_qmatches.cap + s->d_share_words.cap +
                     s->d_ashare_words.cap + s->d_bshare_words.cap + s->d_count_queries.cap + s->d_count_out.cap +
-                    s->d_count_bits.cap + s->d_count_wgs.cap + s->docset_scratch_bytes();
+                    s->d_count_bits.cap + s->d_count_wgs.cap + s->d_set_work.cap + s->docset_scratch_bytes();
   {
     std::lock_guard<std::mutex> lk(s->dscratch->m);
     r.device_scratch_bytes = s->dscratch->partials.cap + s->dscratch->share_stage.cap + s->dscratch->ashare_stage.cap +
@@ -514,6 +515,7 @@ int tq_decode_postings(tq_segment *s, tq_term_handle term, uint32_t *docs, uint3
   if (!s || !docs || !tfs) return fail(TQ_ERR_INVALID, "tq_decode_postings: null argument");
   TQ_SEGMENT_LOCK(s);
   if (term >= s->terms.size()) return fail(TQ_ERR_INVALID, "unknown term handle %u", term);
+  if (s->terms[term].set_kind != TermHost::kNoSet) return fail(TQ_ERR_INVALID, "tq_decode_postings: handle %u is a term set: it has no postings", term);
   HIP_TRY(hipSetDevice(s->device));
   int rc = sync_terms(s, s->stream);
   if (rc != TQ_OK) return rc;
@@ -537,6 +539,7 @@ int tq_decode_position_deltas(tq_segment *s, tq_term_handle term, uint32_t *out,
   TQ_SEGMENT_LOCK(s);
   if (term >= s->terms.size()) return fail(TQ_ERR_INVALID, "unknown term handle %u", term);
   const TermHost &t = s->terms[term];
+  if (t.set_kind != TermHost::kNoSet) return fail(TQ_ERR_INVALID, "tq_decode_position_deltas: handle %u is a term set: it has no positions", term);
   if (t.positions_len == 0) return fail(TQ_ERR_UNSUPPORTED, "term has no positions on the device");
   *n_out = t.n_positions;
   const uint64_t n = std::min<uint64_t>(cap, t.n_positions);

@@ -97,7 +97,7 @@ bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool 
   for (uint32_t c = 0; c < n_cl; ++c)
     for (uint32_t i = 0; i < cl[c].n; ++i) {
       const uint32_t h = cl[c].terms[i];
-      if (!(s->terms[h].dense_blob && s->opt.use_dense) && !temp_slot.count(h) && temp_slot.size() >= max_temp) return false;
+      if (!expression_bitmap(s, s->terms[h]) && !temp_slot.count(h) && temp_slot.size() >= max_temp) return false;
     }
   if (fc.all_based) return false;  // (count_batch counts these itself: never the scan)
   uint32_t msm = fc.msm;
@@ -118,7 +118,7 @@ bool count_expression(tq_segment *s, const tq_query &q, TqkCountQuery &cq, bool 
   auto put = [&](const Clause &c, uint32_t kind, bool clause_union) {
     for (uint32_t i = 0; i < c.n; ++i) {
       const TermHost &th = s->terms[c.terms[i]];
-      if (th.dense_blob && s->opt.use_dense) {
+      if (expression_bitmap(s, th)) {
         cq.dense[n] = (const uint2 *)th.dense_blob;
       } else {  // (the slot for now; the pointer once the scratch is allocated)
         const uint32_t slot = temp_slot.emplace(c.terms[i], (uint32_t)temp_slot.size()).first->second;
@@ -200,19 +200,37 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
       all_q.push_back(qi);
   }
   if (!eff.empty()) queries = eff.data();
+  // Queries that name a term set (tq_termset.cpp) are never scanned — a set has no postings to walk: the bitmap kernel
+  // whatever "count_bitmap_ratio" says, or — "at least m of n" — the doc-set count pass.
+  std::vector<uint8_t> set_q;
+  for (uint32_t qi = 0; s->n_set_slots && qi < n_queries; ++qi) {
+    bool has = false;
+    const int src = check_set_query(s, given[qi], qi, "tq_count_batch", &has);
+    if (src != TQ_OK) return src;
+    if (has && set_q.empty()) set_q.assign(n_queries, 0);
+    if (has) set_q[qi] = 1;
+  }
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     if (!done.empty() && done[qi]) continue;
     TqkCountQuery cq;
     bool known = false;
     uint64_t driver = 0;
     trial = temp_slot;  // (a query that ends up scanned leaves no slots behind)
-    const bool expr = kRatio && count_expression(s, queries[qi], cq, known, driver, trial, max_temp);
+    const bool names_set = !set_q.empty() && set_q[qi];
+    const bool expr = (kRatio || names_set) && count_expression(s, queries[qi], cq, known, driver, trial, max_temp);
     if (expr && known) {
       out_counts[qi] = 0;
-    } else if (expr && driver * kRatio >= (uint64_t)cq.n_terms * s->max_doc) {
+    } else if (expr && (names_set || driver * kRatio >= (uint64_t)cq.n_terms * s->max_doc)) {
       cqs.push_back(cq);
       bitmap_q.push_back(qi);
       temp_slot.swap(trial);
+    } else if (names_set) {
+      // (what the doc-set pass would refuse is reported here, under the caller's index: that pass sees a sub-batch)
+      TqkDocsetQuery dq;
+      const char *why = "";
+      const int drc = docset_expression(s, given[qi], dq, &why);
+      if (drc != FLAT_OK) return fail(drc == FLAT_UNSUPPORTED ? TQ_ERR_UNSUPPORTED : TQ_ERR_INVALID, "tq_count_batch: query %u: %s", qi, why);
+      all_q.push_back(qi);
     } else {
       scan_q.push_back(qi);
     }

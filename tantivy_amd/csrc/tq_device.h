@@ -54,7 +54,9 @@ struct TqdTermHead {  // what every kernel needs: fetched with scalar loads
   uint32_t n_blocks, n_tail;
   uint32_t has_freq;          // bit 0: 0 => every tf reads as 1; bits 8..15: doc-matrix slot + 1 (0 = none);
                               // bits 16..23: signature bit (0..15) + 1 of a list without a column (0 = none);
-                              // bit 24: the list's tf classes are in TqdSegment::doccls (its slot < TQD_CLS_SLOTS)
+                              // bit 24: the list's tf classes are in TqdSegment::doccls (its slot < TQD_CLS_SLOTS);
+                              // bit 25: the record is a TERM SET (tq_termset.cpp) — no blocks, `dense` is the OR of its
+                              // members' docs and it scores the query's weight as given (a ConstScorer)
   uint32_t coarse_shift;
 };
 struct TqdTerm : TqdTermHead {

@@ -42,7 +42,7 @@ int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, cons
   auto put = [&](const Clause &c, uint32_t kind) {
     for (uint32_t i = 0; i < c.n; ++i) {
       const TermHost &th = s->terms[c.terms[i]];
-      if (th.dense_blob && s->opt.use_dense) {
+      if (expression_bitmap(s, th)) {
         dq.dense[n] = (const uint2 *)th.dense_blob;
       } else {  // (the handle for now; the pointer once the sub-batch's scratch slot is known)
         dq.dense[n] = (const uint2 *)(uintptr_t)c.terms[i];
@@ -95,7 +95,10 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
       sq.handle[n] = c.terms[i];
       sq.weight[n] = q.weights[c.pos[i]];
       uint32_t kind = TQK_SCORE_BLOCKS;
-      if (th.dense_blob && s->opt.use_dense) {
+      if (th.set_kind == TermHost::kSet) {  // a term set: its bit, its weight as given (ConstScorer)
+        kind = TQK_SCORE_CONST;
+        sq.tab[n] = th.dense_blob;
+      } else if (th.dense_blob && s->opt.use_dense) {
         kind = TQK_SCORE_BITMAP;
         sq.tab[n] = th.dense_blob;
         sq.aux[n] = th.tf8_blob;
@@ -186,6 +189,11 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     const char *why = "";
     FlatClauses fc;
     const tq_query &q = queries[qi];
+    {  // a term set in a phrase, inside a nested query, or released: refused whatever the tree options say
+      bool names_set = false;
+      const int src = check_set_query(s, q, qi, fn, &names_set);
+      if (src != TQ_OK) return src;
+    }
     const int rc = docset_expression(s, q, dqs[qi], &why, scored ? &fc : nullptr);
     if (rc == FLAT_UNSUPPORTED && trees_on && !query_has_all(q) && (q.mode == TQ_MODE_PHRASE || bool_query_is_tree(q))) {
       if (scored) {  // the rule of the flat queries; plan_tree_query reads every term's weight

@@ -14,7 +14,8 @@
 // A list is reached through its bitmap + rank directory and byte-wide tfs, through its range directory, or — the general
 // case, in an instantiation of its own because of the LDS it needs — by seek_block + lookup_in_blocks; a saturated tf
 // byte (255) or directory entry (0xFFFF) reads the packed value of the posting's block.  The batch's scratch bitmaps
-// are not read: they belong to whichever sub-batch ran last.
+// are not read: they belong to whichever sub-batch ran last.  A TERM SET (tq_termset.cpp) is the fourth kind: its bitmap
+// word says whether the doc is in it, and it scores the query's weight as given (ConstScorer) — no rank, no tf, no norm.
 // HBM model per output doc: 4 (doc) + 4 (score) + 1 (fieldnorm) bytes; per scoring list at most one 8-byte bitmap
 // word per 32 docs of the segment.
 #include "tq_common.hpp"
@@ -78,7 +79,8 @@ __global__ __launch_bounds__(SC_THREADS) void docset_score_kernel(TqkScoreParams
       for (uint32_t u = 0; u < SC_CHUNK; ++u) {
         const uint32_t m = m0 + u;
         wd[u] = make_uint2(0u, 0u);
-        if (m < n_lists && ((access >> (2u * m)) & 3u) == TQK_SCORE_BITMAP) {  // (uniform)
+        const uint32_t kind_u = (access >> (2u * m)) & 3u;
+        if (m < n_lists && (kind_u == TQK_SCORE_BITMAP || kind_u == TQK_SCORE_CONST)) {  // (uniform)
           const uint2 *bm = reinterpret_cast<const uint2 *>(sload(reinterpret_cast<const uint64_t *>(Q->tab) + m));
           if (on) wd[u] = bm[doc >> 5];
         }
@@ -116,7 +118,9 @@ __global__ __launch_bounds__(SC_THREADS) void docset_score_kernel(TqkScoreParams
             const TermRef tr = load_term(p.terms, sload(&Q->handle[m]));
             if (present && tf == 0xFFFFu) tf = exact_tf(seg.idx, tr, pi);
           }
-        } else if constexpr (BLOCKS) {
+        } else if (kind == TQK_SCORE_CONST) {  // a term set: the bit alone
+          present = (wd[u].x >> bit) & 1u;
+        } else if constexpr (BLOCKS) {  // (TQK_SCORE_BLOCKS: the kinds above are tested explicitly)
           const TermRef tr = load_term(p.terms, sload(&Q->handle[m]));
           bool cand = on;
           uint32_t jb = 0;
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(SC_THREADS) void docset_score_kernel(TqkScoreParams
             tf = block_tf_at(seg.idx, tr, make_uint2(r.y, r.z), at);
           }
         }
-        if (present) clause = clause + bm25(w, norm, tf);
+        if (present) clause = clause + (kind == TQK_SCORE_CONST ? w : bm25(w, norm, tf));
         if ((clause_end >> m) & 1u) {  // (uniform)
           if (m < n_must_lists) {
             if (n_must == 0u)

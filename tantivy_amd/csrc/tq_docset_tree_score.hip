@@ -110,7 +110,8 @@ __global__ __launch_bounds__(TS_THREADS) void docset_tree_score_kernel(TqkDocset
         const uint32_t t = t0 + u;
         tfb[u] = 0u;
         if (t < t_end) {
-          const bool scores = sload(Q->inner + t) != TQD_ROLE_MUST_NOT && !(PH && (sload(Q->atom_end + t) & 2u));
+          // (a const-score leaf, atom_end bit 3, has no tf bytes: its tf8_off names the bitmap again)
+          const bool scores = sload(Q->inner + t) != TQD_ROLE_MUST_NOT && !(sload(Q->atom_end + t) & 8u) && !(PH && (sload(Q->atom_end + t) & 2u));
           if (scores && ((wd[u].x >> bit) & 1u))
             tfb[u] = (tbase + ((uint64_t)sload(Q->tf8_off + t) << 3))[wd[u].y + (uint32_t)__popc(wd[u].x & ((1u << bit) - 1u))];
         }
@@ -124,7 +125,9 @@ __global__ __launch_bounds__(TS_THREADS) void docset_tree_score_kernel(TqkDocset
         const bool present = has && ((wd[u].x >> bit) & 1u);
         atom_ok = atom_ok && present;
         atom_some = atom_some || present;
-        if (present && inner != TQD_ROLE_MUST_NOT && !(PH && (ae & 2u))) {
+        if (present && (ae & 8u)) {  // a const-score leaf (a term set): its weight as given
+          if (inner != TQD_ROLE_MUST_NOT) atom_sum = atom_sum + __uint_as_float(sload(Q->weight_bits + t));
+        } else if (present && inner != TQD_ROLE_MUST_NOT && !(PH && (ae & 2u))) {
           const uint32_t pi = wd[u].y + (uint32_t)__popc(wd[u].x & ((1u << bit) - 1u));
           uint32_t tf = tfb[u];
           if (tf == 255u) {  // saturated byte: block record -> packed tf (tq_common.hpp)

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -137,6 +138,11 @@ struct TermHost {
   bool wants_col = true;  // false: the segment's columns are reserved for other lists
   uint64_t postings_len = 0, positions_len = 0;
   uint64_t n_positions = 0;
+  // a TERM SET (tq_termset.cpp): the slot holds no posting list — dense_blob is the OR of its members' docs, doc_freq the
+  // number of docs in it (the reference's cost of a BitSetDocSet), postings_len the bytes of its bits, and it scores
+  // its weight as given.  kSetReleased: the tombstone tq_term_set_release leaves (a later set may take the slot)
+  enum : uint8_t { kNoSet = 0, kSet = 1, kSetReleased = 2 };
+  uint8_t set_kind = kNoSet;
 };
 
 inline uint32_t rd32(const uint8_t *p) {
@@ -301,6 +307,12 @@ struct tq_segment {
   // resident bytes by kind (tq_segment_get_stats)
   size_t bytes_term_tables = 0, bytes_bitmaps = 0, bytes_docmat = 0, bytes_posdir = 0, bytes_alive = 0;
   uint32_t n_dense_lists = 0;
+  // term sets (tq_termset.cpp): slots of `terms` that are or were sets (0: no entry point looks for them), the released
+  // slots and tables a later set takes, the build's work lists and scan scratch
+  uint32_t n_set_slots = 0;
+  std::vector<uint32_t> set_free_slots;
+  std::vector<void *> set_free_tables;
+  DevBuf d_set_work;
   uint32_t alive_docs = 0;  // docs below max_doc the alive bitset keeps (counted when it is set; without one: max_doc)
   std::unordered_map<uint64_t, uint32_t> term_by_off;
   // lists named by tq_segment_reserve_columns (postings_off): only they get doc-matrix columns
@@ -893,6 +905,21 @@ struct AllView {  // the entries of keep_mask as a query of their own (borrows q
   uint32_t pos[TQ_MAX_TERMS];  // where entry i of the view stands in the caller's query
 };
 void all_strip_view(const tq_query &q, const AllForm &f, AllView &v);
+// ---- tq_termset.cpp: term sets (tq_term_set_prepare: a slot of the term table that is a bitmap and scores a constant)
+inline bool is_term_set(const tq_segment *s, uint32_t h) { return h < s->terms.size() && s->terms[h].set_kind == TermHost::kSet; }
+// a list's bitmap as the count / doc-set expressions name it: its own where "use_dense" allows, a set's always (it has nothing else)
+inline const void *expression_bitmap(const tq_segment *s, const TermHost &th) {
+  return th.dense_blob && (s->opt.use_dense || th.set_kind == TermHost::kSet) ? th.dense_blob : nullptr;
+}
+inline bool query_names_set(const tq_segment *s, const tq_query &q) {
+  if (!q.terms || q.n_terms > TQ_MAX_TERMS) return false;
+  for (uint32_t i = 0; i < q.n_terms; ++i)
+    if (is_term_set(s, q.terms[i])) return true;
+  return false;
+}
+// Does the query name a set?  (*has; false at once while the segment has never had one.)  TQ_ERR_INVALID: it names a
+// released set, or a set in a phrase; TQ_ERR_UNSUPPORTED: a set inside a nested query — `fn: query qi: ...` either way.
+int check_set_query(const tq_segment *s, const tq_query &q, uint32_t qi, const char *fn, bool *has);
 // ---- tq_count.cpp
 int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_counts);
 // a query as a bitwise expression over bitmap words (tq_count.cpp; checked on the CPU by tools/planbench/plan_check.cpp)
@@ -950,7 +977,8 @@ int resolve_opts(const tq_segment *s, const tq_search_opts *o, CallOpts &co);
 void update_table_span(tq_segment *s);
 // the probe tables one nested boolean query needs (tq_tree.hip / tq_docset_tree.hip reach EVERY list through a bitmap,
 // a phrase term's positions from the bitmap's rank); *built: some table is new (the tables' address span moved)
-int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built);
+// flat_too: a flat TQ_MODE_BOOL query as well (one that names a term set: it takes the tree kernel)
+int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built, bool flat_too = false);
 int fail_tree_tables(const tq_segment *s, uint32_t qi);  // "use_dense" off, or the tables outside one 32 GB span: TQ_ERR_UNSUPPORTED
 int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *d_out_scores, uint32_t *d_out_docs, uint32_t *d_out_counts, void *hip_stream,

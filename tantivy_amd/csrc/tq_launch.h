@@ -194,7 +194,9 @@ struct TqdTreeQuery {
   uint32_t atom_end[TQK_TREE_MAX_TERMS];     // bit 0: the term is the last of its atom; bit 1 (on every term of the atom): the atom is
                                              // a PhraseQuery of <= TQK_TREE_PHRASE_TERMS terms (weight_bits = the phrase's weight);
                                              // bit 2 (on every term of the atom): the atom is a UNION of its terms (present where
-                                             // any of them is, scoring the present ones) instead of a conjunction
+                                             // any of them is, scoring the present ones) instead of a conjunction;
+                                             // bit 3: a CONST-SCORE leaf (a term set): present where its bit is, scoring
+                                             // weight_bits as given — neither rank nor tf is read (tf8_off = dense_off)
   uint32_t dir_off[TQK_TREE_MAX_TERMS];      // phrase terms: position directory of the list (TqdTerm::pos_dir layout), 8-byte units
   uint32_t phrase_off[TQK_TREE_MAX_TERMS];   // phrase terms: max_offset - term_offset (phrase_scorer.rs:372-385)
   uint32_t outer[TQK_TREE_MAX_TERMS];        // per clause: its occur in the query
@@ -316,6 +318,15 @@ hipError_t tqk_launch_count_bitmaps(const TqkCountParams &p, hipStream_t st);
 hipError_t tqk_launch_count_scatter(const TqdSegment &seg, const TqdTerm *terms, const uint4 *wgs, uint32_t n_wgs,
                                     uint32_t *bits, uint32_t words_per_list, hipStream_t st);
 uint32_t tqk_count_tile_words();
+// ---- term sets (tq_termset.hip): the bitmap + rank directory of the OR of many lists into `tab` (n_words + 1 entries,
+// zeroed by the caller).  d_members: the n_members bitmaps of the members that have one; d_items: {member's term handle,
+// first block} per four blocks of the members that have none; scan_scratch: tqk_termset_scratch_words(n_words) words —
+// afterwards its word ceil(n_words / tqk_termset_scan_tile()) (at least 1) holds the set's doc count
+hipError_t tqk_launch_termset_build(const TqdSegment &seg, const TqdTerm *terms, const uint2 *const *d_members, uint32_t n_members,
+                                    const uint2 *d_items, uint32_t n_items, uint2 *tab, uint32_t n_words, uint32_t *scan_scratch,
+                                    hipStream_t st);
+uint32_t tqk_termset_scan_tile();
+uint32_t tqk_termset_scratch_words(uint32_t n_words);
 // ---- full doc sets over bitmaps (tq_docset.hip): the expression of TqkCountQuery with the result bits kept
 struct TqkDocsetQuery {           // 152 bytes
   uint32_t n_terms;               // lists: Must clauses first (a clause = a union of lists), then MustNot, then Should
@@ -353,6 +364,7 @@ uint32_t tqk_docset_scan_tile();
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
 #define TQK_SCORE_RDIR 1u    // tab = its range directory, aux = the directory's entries, shift = the directory's shift
 #define TQK_SCORE_BLOCKS 2u  // seek_block + lookup_in_blocks over the packed list
+#define TQK_SCORE_CONST 3u   // a term set (tq_termset.cpp): tab = its bitmap, present = the doc's bit, score = weight as given
 struct TqkScoreQuery {             // 472 bytes: every non-MustNot list of the query, in the order its scores are summed
   uint32_t n_lists;                // 0: the query matches nothing
   uint32_t cache_idx;              // which 256-float Bm25Weight cache of the batch

@@ -455,8 +455,9 @@ int plan_tree_query(tq_segment *s, const tq_query &q, uint32_t qi, TqdTreeQuery 
       for (uint32_t i = 0; i < A.n; ++i) max_off = std::max(max_off, A.off[i]);
       for (uint32_t i = 0; i < A.n; ++i) {
         const TermHost &th = s->terms[A.handle[i]];
+        const bool cset = th.set_kind == TermHost::kSet;  // a const-score leaf: its bitmap alone (tf8_off names it again, never read)
         const bool own = th.dense_blob && th.tf8_blob;
-        const void *bm = own ? th.dense_blob : th.probe_dense_blob, *t8 = own ? th.tf8_blob : th.probe_tf8_blob;
+        const void *bm = cset || own ? th.dense_blob : th.probe_dense_blob, *t8 = cset ? th.dense_blob : own ? th.tf8_blob : th.probe_tf8_blob;
         if (!bm || !t8)
           return fail(TQ_ERR_UNSUPPORTED, "query %u: a nested boolean query names a list without a bitmap (options \"dense\" / \"use_dense\" / \"probe_budget_x\" off, or a list of more than max_doc / 32 postings whose own tables did not fit \"dense_budget_x\")", qi);
         tq.dense_off[n] = (uint32_t)(((uint64_t)bm - table_base) >> 3);
@@ -464,7 +465,7 @@ int plan_tree_query(tq_segment *s, const tq_query &q, uint32_t qi, TqdTreeQuery 
         memcpy(&tq.weight_bits[n], &A.w[A.phrase ? 0u : i], sizeof(float));  // (a phrase scores with ONE weight: the sum of its idfs)
         tq.handle[n] = A.handle[i];
         tq.inner[n] = A.inner;
-        tq.atom_end[n] = (i + 1u == A.n ? 1u : 0u) | (A.phrase ? 2u : 0u) | (A.any ? 4u : 0u);
+        tq.atom_end[n] = (i + 1u == A.n ? 1u : 0u) | (A.phrase ? 2u : 0u) | (A.any ? 4u : 0u) | (cset ? 8u : 0u);
         if (A.phrase) {
           const void *dir = own && th.posdir_blob ? th.posdir_blob : th.probe_posdir_blob;
           if (!dir)

@@ -42,6 +42,8 @@ struct Batch {
   std::vector<const float *> caches;    // the Bm25Weight caches, in order of first use (PlanScratch::q_cache)
   uint32_t n_union_queries = 0, n_bool_queries = 0, n_sparse2 = 0;
   uint32_t n_all_queries = 0;  // ALL-BASED queries (TQ_TERM_ALL clauses that make every doc a candidate): counted by strip_all_clauses
+  const uint8_t *set_q = nullptr;  // per query: it names a term set (tq_termset.cpp) and is routed to the tree group; null: no
+                                   // query of the batch does (flagged and counted by strip_all_clauses)
   bool and_probe = false, ashare_on = false, ashare_and = false;
   uint32_t and_tile_cap = TQD_AND_TILE, dense_min_queries = 1;
   uint64_t unique_bytes = 0, dense_ratio = 0;
@@ -204,9 +206,9 @@ int build_flat_probe_tables(Batch &b) {
 }  // namespace
 
 // Nested boolean queries (tq_tree.hip) reach EVERY list through a bitmap, in both modes.
-int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built) {
+int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built, bool flat_too) {
   if (!s->opt.use_dense || !s->opt.dense || s->opt.probe_budget_x <= 0) return TQ_OK;
-  if (q.mode != TQ_MODE_BOOL || !q.terms || q.n_terms > TQ_MAX_TERMS || !bool_query_is_tree(q)) return TQ_OK;
+  if (q.mode != TQ_MODE_BOOL || !q.terms || q.n_terms > TQ_MAX_TERMS || !(flat_too || bool_query_is_tree(q))) return TQ_OK;
   for (uint32_t i = 0; i < q.n_terms; ++i) {
     const uint32_t h = q.terms[i];
     if (h >= s->terms.size()) continue;
@@ -236,7 +238,8 @@ int build_tree_probe_tables(Batch &b) {
   if (!b.n_bool_queries) return TQ_OK;
   bool built = false;
   for (uint32_t qi = 0; qi < b.n_queries; ++qi) {
-    const int prc = build_tree_query_probe_tables(b.s, b.queries[qi], &built);
+    // (a flat query that names a term set takes the tree kernel too: its other lists get bitmaps the same way)
+    const int prc = build_tree_query_probe_tables(b.s, b.queries[qi], &built, b.set_q && b.set_q[qi]);
     if (prc != TQ_OK) return prc;
   }
   if (built) b.s->share_span_terms = ~(size_t)0;
@@ -560,7 +563,9 @@ int route_all(const Batch &b, uint32_t qi, Route &r, Group &all_group) {
       for (uint32_t i = 0; i < C.n; ++i) {
         const TermHost &th = b.s->terms[C.terms[i]];
         const bool own = th.dense_blob && th.tf8_blob;
-        const void *bm = own ? th.dense_blob : th.probe_dense_blob, *t8 = own ? th.tf8_blob : th.probe_tf8_blob;
+        // (a term set: a MustNot list here — strip_all_clauses — of which all_kernel reads the bits alone)
+        const bool cset = th.set_kind == TermHost::kSet && pass == 1;
+        const void *bm = cset || own ? th.dense_blob : th.probe_dense_blob, *t8 = cset ? th.dense_blob : own ? th.tf8_blob : th.probe_tf8_blob;
         if (!b.s->share_span_ok || !b.s->opt.use_dense || !bm || !t8)
           return fail(TQ_ERR_UNSUPPORTED,
                       "query %u: a query with a match-all clause names a list without a bitmap (options \"dense\" / \"use_dense\" / \"probe_budget_x\" off, "
@@ -738,6 +743,8 @@ int plan_query(const Batch &b, uint32_t qi, Group *groups, RouteTotals &t) {
   const bool any_absent = std::find(q.terms, q.terms + q.n_terms, TQ_TERM_ABSENT) != q.terms + q.n_terms;
   if (b.n_all_queries && query_has_all(q)) {
     rc = route_all(b, qi, r, groups[kGAll]);
+  } else if (b.set_q && b.set_q[qi]) {  // (a TQ_MODE_BOOL view, whatever the caller's mode was)
+    rc = route_tree(b, qi, r, groups[kGTree]);
   } else if (q.mode == TQ_MODE_BOOL) {
     rc = bool_query_is_tree(q) ? route_tree(b, qi, r, groups[kGTree]) : route_bool(b, qi, r, t);
   } else if (q.mode == TQ_MODE_OR || (q.mode == TQ_MODE_AND && q.n_terms == 1 && !any_absent)) {
@@ -1450,32 +1457,71 @@ struct DrainOnError {
   }
 };
 
-// Queries with AllQuery clauses (TQ_TERM_ALL) before anything is planned: the normal form of tq_all.cpp decides each —
-// EMPTY and PLAIN ones are replaced by their stripped views (today's kernels see a query without All clauses, and a
-// PLAIN query's rows are that query's, bit for bit), ALL-BASED ones stay as they are for route_all.  A batch without
-// such a clause is not copied.
+// The one pre-pass over the caller's queries before anything is planned: AllQuery clauses (TQ_TERM_ALL) and term sets.
+// All clauses: the normal form of tq_all.cpp decides each query — EMPTY and PLAIN ones are replaced by their stripped
+// views (today's kernels see a query without All clauses, and a PLAIN query's rows are that query's, bit for bit),
+// ALL-BASED ones stay as they are for route_all.
+// Term sets (tq_termset.cpp; looked for only on a segment that has ever had one: s->n_set_slots): the reference runs a
+// query through the generic, unpruned for_each_pruning_scorer as soon as one of its scorers is not a TermScorer
+// (boolean_weight.rs:44-86, intersection.rs:39-55): here that is tree_kernel, whatever the query's mode.  Such a query is
+// flagged (set_q[qi]: plan_query and the probe-table pass test the flag, no handle is looked at again) and counted; a
+// TQ_MODE_AND / TQ_MODE_OR one gets its occurs on call scratch.  Refused: a set in a phrase or released (TQ_ERR_INVALID),
+// inside a nested query, or as a Should clause of an ALL-BASED query (TQ_ERR_UNSUPPORTED: all_kernel takes sets as
+// MustNot lists only).  A batch without an All clause or a set is not copied.
 struct AllStrip {
   std::vector<tq_query> eff;
   std::deque<AllView> views;  // (a deque: the views' arrays stay where they are)
-  uint32_t n_all_based = 0;
+  std::deque<std::array<uint8_t, TQ_MAX_TERMS>> set_occurs;  // the occurs of TQ_MODE_AND / TQ_MODE_OR queries that name a set
+  std::vector<uint8_t> set_q;  // per query: it names a term set and runs as a tree (empty: no query of the batch does)
+  uint32_t n_all_based = 0, n_set = 0;
 };
-int strip_all_clauses(const tq_query *queries, uint32_t n_queries, AllStrip &st) {
+int strip_all_clauses(const tq_segment *s, const tq_query *queries, uint32_t n_queries, AllStrip &st) {
+  const bool sets = s->n_set_slots != 0;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
-    if (!query_has_all(queries[qi])) continue;
-    AllForm f;
-    const char *why = "";
-    const int rc = all_query_form(queries[qi], f, &why);
-    if (rc != TQ_OK) return fail(rc, "query %u: %s", qi, why);
-    if (f.boost_mixed)
-      return fail(TQ_ERR_UNSUPPORTED, "query %u has a boosted match-all clause beside another scoring clause or a second match-all clause: its scores stay on the CPU", qi);
-    if (f.kind == TQ_ALL_BASED) {
-      ++st.n_all_based;
+    bool names_set = false;
+    if (sets) {
+      const int src = check_set_query(s, queries[qi], qi, "tq_search_batch", &names_set);
+      if (src != TQ_OK) return src;
+    }
+    bool all_based = false;
+    if (query_has_all(queries[qi])) {
+      AllForm f;
+      const char *why = "";
+      const int rc = all_query_form(queries[qi], f, &why);
+      if (rc != TQ_OK) return fail(rc, "query %u: %s", qi, why);
+      if (f.boost_mixed)
+        return fail(TQ_ERR_UNSUPPORTED, "query %u has a boosted match-all clause beside another scoring clause or a second match-all clause: its scores stay on the CPU", qi);
+      all_based = f.kind == TQ_ALL_BASED;
+      if (all_based) {
+        ++st.n_all_based;
+      } else {
+        if (st.eff.empty()) st.eff.assign(queries, queries + n_queries);
+        st.views.emplace_back();
+        all_strip_view(queries[qi], f, st.views.back());
+        st.eff[qi] = st.views.back().q;
+      }
+    }
+    if (!names_set) continue;
+    const tq_query &q = st.eff.empty() ? queries[qi] : st.eff[qi];  // (what is left of it without its All clauses)
+    if (all_based) {
+      for (uint32_t i = 0; i < q.n_terms; ++i)
+        if (is_term_set(s, q.terms[i]) && !(q.mode == TQ_MODE_BOOL && q.occurs && q.occurs[i] == TQ_MUST_NOT))
+          return fail(TQ_ERR_UNSUPPORTED, "tq_search_batch: query %u: a term set as a Should clause beside a match-all clause stays on the CPU (its counts and doc sets are taken)", qi);
       continue;
     }
+    if (!query_names_set(s, q)) continue;  // (the set went with an EMPTY form's clauses)
+    if (st.set_q.empty()) st.set_q.assign(n_queries, 0);
+    st.set_q[qi] = 1;
+    ++st.n_set;
+    if (q.mode == TQ_MODE_BOOL) continue;
     if (st.eff.empty()) st.eff.assign(queries, queries + n_queries);
-    st.views.emplace_back();
-    all_strip_view(queries[qi], f, st.views.back());
-    st.eff[qi] = st.views.back().q;
+    st.set_occurs.emplace_back();
+    st.set_occurs.back().fill(q.mode == TQ_MODE_AND ? (uint8_t)TQ_MUST : (uint8_t)TQ_SHOULD);
+    tq_query &v = st.eff[qi];
+    v.mode = TQ_MODE_BOOL;
+    v.occurs = st.set_occurs.back().data();
+    v.clause_of = v.nested_occurs = v.clause_min_should = v.atom_of = nullptr;
+    v.min_should_match = 0;
   }
   return TQ_OK;
 }
@@ -1497,17 +1543,19 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
     return fail(TQ_ERR_INVALID, "tq_search_batch: null argument");
   if (n_queries == 0) return TQ_OK;
   AllStrip strip;
-  int rc = strip_all_clauses(queries, n_queries, strip);
+  int rc = strip_all_clauses(s, queries, n_queries, strip);
   if (rc != TQ_OK) return rc;
   if (!strip.eff.empty()) queries = strip.eff.data();
   Batch b{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, co};
   b.n_all_queries = strip.n_all_based;
+  b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
   rc = plan_batch(b);
   // a shared launch's result lists over the budget even with the longest tasks: the same batch again, that family
   // through the per-query kernels
   while (rc != TQ_OK && b.replan) {
     b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co};
     b.n_all_queries = strip.n_all_based;
+    b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
     rc = plan_batch(b);
   }
   if (rc != TQ_OK) return rc;

@@ -124,6 +124,7 @@ int build_probe_tables(tq_segment *s, uint32_t handle, bool *ok, bool must) {
     probe_touch(s, handle);
     return TQ_OK;
   }
+  if (t.set_kind != TermHost::kNoSet) return TQ_OK;  // (a term set is its bitmap: there is no list to build tables from)
   if (!s->opt.dense || !s->opt.use_dense || !t.doc_freq || s->opt.probe_budget_x <= 0) return TQ_OK;
   if (!must && s->probe_no_room_batch == s->probe_batch) return TQ_OK;
   // (segments below 4096 docs: the shared launches are not used there — only nested boolean queries, which reach every

@@ -168,7 +168,9 @@ __global__ __launch_bounds__(64) void tree_kernel(TqkTreeParams p) {
           const bool present = has && ((wd.x >> bit) & 1u);
           atom_ok = atom_ok && present;
           atom_some = atom_some || present;
-          if (present && inner != TQD_ROLE_MUST_NOT && !(PH && (ae & 2u))) {
+          if (present && (ae & 8u)) {  // a const-score leaf (a term set): its weight as given, neither rank nor tf
+            if (inner != TQD_ROLE_MUST_NOT) atom_sum = atom_sum + __uint_as_float(sload(Q->weight_bits + t));
+          } else if (present && inner != TQD_ROLE_MUST_NOT && !(PH && (ae & 2u))) {
             const uint32_t pi = wd.y + (uint32_t)__popc(wd.x & ((1u << bit) - 1u));
             uint32_t tf = (tbase + ((uint64_t)sload(Q->tf8_off + t) << 3))[pi];
             if (tf == 255u) {  // saturated byte: block record -> packed tf (tq_common.hpp)

@@ -71,7 +71,10 @@ struct tqh_query {
   const uint8_t *nested_occurs;    // TQ_MODE_BOOL, or null: see tantivy_amd_host.h
   const uint8_t *clause_min_should;  // TQ_MODE_BOOL, or null: minimum_number_should_match of the nested query, by clause_of value
   const uint8_t *atom_of;            // TQ_MODE_BOOL, or null: terms of one clause_of group sharing a value form a nested intersection
+  const uint32_t *set_terms;         // term sets, or null: terms[i] == TQH_TERM_SET_BASE + j names set j, whose term ids are
+  const uint32_t *set_starts;        // set_terms[set_starts[j] .. set_starts[j + 1])
 };
+#define TQH_TERM_SET_BASE 0xFFFFFF00u
 
 const char *tqh_last_error(void) { return g_err.c_str(); }
 
@@ -191,6 +194,16 @@ int tqh_searcher_add_remote_stats(tqh_searcher *s, uint64_t max_doc, uint64_t to
   });
 }
 
+// terms[t] == TQH_TERM_SET_BASE + j with set_terms / set_starts given: a TermSetQuery over set j's term ids
+static bool is_set_entry(const tqh_query &q, uint32_t t) {
+  return q.set_terms && q.set_starts && q.terms[t] >= TQH_TERM_SET_BASE && q.terms[t] < TQH_TERM_SET_BASE + TQ_MAX_TERMS;
+}
+static Query set_query_of(const tqh_query &q, uint32_t t) {
+  const uint32_t j = q.terms[t] - TQH_TERM_SET_BASE;
+  if (q.set_starts[j + 1] < q.set_starts[j]) throw TantivyError(TantivyError::InvalidArgument, "set_starts must ascend");
+  return Query::term_set(std::vector<uint32_t>(q.set_terms + q.set_starts[j], q.set_terms + q.set_starts[j + 1])).boosted(q.boosts ? q.boosts[t] : 1.0f);
+}
+
 // tqh_query -> Query (the shapes of tantivy_amd_host.h)
 static Query build_query(const tqh_query &q) {
   Query query;
@@ -209,6 +222,7 @@ static Query build_query(const tqh_query &q) {
       return q.nested_occurs && q.nested_occurs[tt] != 255 && (q.nested_occurs[tt] & TQ_NESTED_PHRASE) != 0;
     };
     auto leaf_of = [&](uint32_t tt) {
+      if (is_set_entry(q, tt)) return set_query_of(q, tt);  // a TermSetQuery clause
       if (q.terms[tt] == TQ_TERM_ALL) return Query::all().boosted(q.boosts ? q.boosts[tt] : 1.0f);  // an AllQuery clause
       if (in_phrase(tt))  // (the phrase's first term: the others are appended to phrase_terms below)
         return Query::phrase_with_offsets({{q.phrase_offsets ? q.phrase_offsets[tt] : 0u, q.terms[tt]}}).boosted(q.boosts ? q.boosts[tt] : 1.0f);
@@ -291,6 +305,8 @@ static Query build_query(const tqh_query &q) {
         }
     query = Query::boolean(std::move(clauses));
     query.set_minimum_number_should_match(q.min_should_match);
+  } else if (q.n_terms == 1 && q.mode != TQ_MODE_PHRASE && is_set_entry(q, 0)) {
+    query = set_query_of(q, 0);
   } else if (q.n_terms == 1 && q.mode != TQ_MODE_PHRASE && q.terms[0] == TQ_TERM_ALL) {
     query = Query::all().boosted(q.boosts ? q.boosts[0] : 1.0f);
   } else if (q.mode == TQH_MODE_TERM || (q.n_terms == 1 && q.mode != TQ_MODE_PHRASE)) {
@@ -307,7 +323,8 @@ static Query build_query(const tqh_query &q) {
     std::vector<std::pair<Occur, Query>> clauses;
     for (uint32_t t = 0; t < q.n_terms; ++t)
       clauses.emplace_back(q.mode == TQ_MODE_AND ? Occur::Must : Occur::Should,
-                           (q.terms[t] == TQ_TERM_ALL ? Query::all() : Query::term_query(q.terms[t])).boosted(q.boosts ? q.boosts[t] : 1.0f));
+                           is_set_entry(q, t) ? set_query_of(q, t)
+                                              : (q.terms[t] == TQ_TERM_ALL ? Query::all() : Query::term_query(q.terms[t])).boosted(q.boosts ? q.boosts[t] : 1.0f));
     query = Query::boolean(std::move(clauses));
   }
   return query;
@@ -337,7 +354,7 @@ static void prepare_into(tqh_searcher *s, const tqh_query *queries, uint32_t n, 
     // unboosted all-Must / all-Should term clauses (what a query parser makes of `+a +b` / `a b c`): the weight
     // without the detour through a Query tree — the same f32 arithmetic as Searcher::weight
     bool any_all = false;  // (an AllQuery clause is no term: the Query tree knows it)
-    for (uint32_t t = 0; q.terms && t < q.n_terms; ++t) any_all = any_all || q.terms[t] == TQ_TERM_ALL;
+    for (uint32_t t = 0; q.terms && t < q.n_terms; ++t) any_all = any_all || q.terms[t] == TQ_TERM_ALL || is_set_entry(q, t);
     if ((q.mode == TQ_MODE_AND || q.mode == TQ_MODE_OR) && !q.boosts && q.n_terms >= 1 && q.terms && !any_all) {
       if (!fc.cache) fc = s->searcher->flat_context();
       s->searcher->weight_flat_into(fc, q.mode, q.terms, q.n_terms, out[i]);

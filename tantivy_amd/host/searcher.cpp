@@ -148,6 +148,32 @@ void SegmentReader::prepare_terms(const uint32_t *term_ids, size_t n) {
   }
 }
 
+WeightTermSet::~WeightTermSet() {
+  for (auto &p : prepared_)
+    if (std::shared_ptr<SegmentReader> seg = p.first.lock()) (void)tq_term_set_release(seg->raw(), p.second);
+}
+tq_term_handle WeightTermSet::handle(const std::shared_ptr<SegmentReader> &seg) {
+  std::lock_guard<std::mutex> lk(m_);
+  for (auto &p : prepared_)
+    if (p.first.lock() == seg) return p.second;
+  seg->prepare_terms(term_ids_.data(), term_ids_.size());
+  std::vector<tq_term_handle> hs;
+  hs.reserve(term_ids_.size());
+  for (uint32_t t : term_ids_) hs.push_back(seg->term_handle(t));
+  tq_term_handle h = TQ_TERM_ABSENT;
+  const int rc = tq_term_set_prepare(seg->raw(), hs.data(), (uint32_t)hs.size(), &h);
+  if (rc != TQ_OK) throw_tq(rc);
+  prepared_.emplace_back(seg, h);
+  return h;
+}
+namespace {
+// the handle of entry `t` of a Weight on one segment: a term's, or — kTermSetBase + j — the Weight's set j there
+tq_term_handle resolve_handle(const std::shared_ptr<SegmentReader> &seg, const Weight &w, uint32_t t) {
+  if (t >= kTermSetBase && (size_t)(t - kTermSetBase) < w.sets.size()) return w.sets[t - kTermSetBase]->handle(seg);
+  return seg->term_handle(t);
+}
+}  // namespace
+
 Searcher::Searcher(std::vector<std::shared_ptr<SegmentReader>> segments)
     : segments_(std::move(segments)) {}
 Searcher::~Searcher() { delete[] fast_weights_.load(std::memory_order_relaxed); }
@@ -265,6 +291,12 @@ Weight Searcher::weight(const Query &query) const {
       w.terms = {(uint32_t)TQ_TERM_ALL};
       w.weights = {b0};
       return w;
+    case Query::TermSet:  // AutomatonWeight::scorer: ConstScorer(BitSetDocSet, boost) — weights[i] = the boost as it is
+      w.mode = TQ_MODE_OR;
+      w.sets.push_back(std::make_shared<WeightTermSet>(query.set_terms));
+      w.terms = {kTermSetBase};
+      w.weights = {b0};
+      return w;
     case Query::Term:
       // TermWeight::for_each_pruning == one-scorer block-WAND == every doc of the list
       w.mode = TQ_MODE_OR;
@@ -379,7 +411,7 @@ Weight Searcher::weight(const Query &query) const {
         if (c.second.kind == Query::Phrase) {
           any_phrase = tree = true;
           flat = false;
-        } else if (c.second.kind == Query::All) {  // (a clause of its own, like a term: TQ_TERM_ALL)
+        } else if (c.second.kind == Query::All || c.second.kind == Query::TermSet) {  // (a clause of its own, like a term)
         } else if (c.second.kind != Query::Term) {
           if (!is_query_of_terms(c.second))
             throw TantivyError(TantivyError::Unsupported,
@@ -444,8 +476,13 @@ Weight Searcher::weight(const Query &query) const {
             w.atom_of.push_back(member);
           }
         };
-        if (c.second.kind == Query::All) {  // weights[i] = the boost, which is the score every doc gets
-          w.terms.push_back((uint32_t)TQ_TERM_ALL);
+        if (c.second.kind == Query::All || c.second.kind == Query::TermSet) {  // weights[i] = the boost, which is the score every doc gets
+          if (c.second.kind == Query::TermSet) {
+            w.terms.push_back(kTermSetBase + (uint32_t)w.sets.size());
+            w.sets.push_back(std::make_shared<WeightTermSet>(c.second.set_terms));
+          } else {
+            w.terms.push_back((uint32_t)TQ_TERM_ALL);
+          }
           w.weights.push_back(bc);
           if (w.mode == TQ_MODE_BOOL) {
             w.occurs.push_back(oc);
@@ -496,7 +533,8 @@ namespace {
 struct SegmentBatch {
   std::vector<tq_query> qs;
   std::vector<tq_term_handle> handles;
-  SegmentBatch(SegmentReader &seg, const std::vector<Weight> &weights, uint32_t k) {
+  SegmentBatch(const std::shared_ptr<SegmentReader> &seg_p, const std::vector<Weight> &weights, uint32_t k) {
+    SegmentReader &seg = *seg_p;
     const size_t n = weights.size();
     qs.resize(n);
     size_t total_terms = 0;
@@ -505,13 +543,15 @@ struct SegmentBatch {
     if (n > 1) {  // the batch's new terms are prepared together before any handle is asked for
       std::vector<uint32_t> all;
       all.reserve(total_terms);
-      for (auto &w : weights) all.insert(all.end(), w.terms.begin(), w.terms.end());
+      for (auto &w : weights)
+        for (uint32_t t : w.terms)
+          if (t < kTermSetBase) all.push_back(t);  // (a set prepares its members itself; TQ_TERM_ALL names no list)
       seg.prepare_terms(all.data(), all.size());
     }
     for (size_t i = 0; i < n; ++i) {
       const Weight &w = weights[i];
       const size_t at = handles.size();
-      for (uint32_t t : w.terms) handles.push_back(seg.term_handle(t));
+      for (uint32_t t : w.terms) handles.push_back(resolve_handle(seg_p, w, t));
       tq_query &q = qs[i];
       q.n_terms = (uint32_t)w.terms.size();
       q.terms = handles.data() + at;  // stable: reserved up front
@@ -547,7 +587,7 @@ void Searcher::collect_segment_batch(size_t segment_ord, const std::vector<Weigh
                                      std::vector<uint32_t> &docs, std::vector<uint32_t> &counts) {
   SegmentReader &seg = *segments_[segment_ord];
   const size_t n = weights.size();
-  SegmentBatch b(seg, weights, k);
+  SegmentBatch b(segments_[segment_ord], weights, k);
   scores.assign(n * k, 0.0f);
   docs.assign(n * k, TERMINATED);
   counts.assign(n, 0);
@@ -562,7 +602,7 @@ std::vector<uint64_t> Searcher::count_batch(const std::vector<Weight> &weights) 
   std::vector<uint64_t> total(weights.size(), 0);
   std::vector<uint32_t> per(weights.size());
   for (auto &seg : segments_) {
-    SegmentBatch b(*seg, weights, 1);
+    SegmentBatch b(seg, weights, 1);
     const int rc = tq_count_batch(seg->raw(), b.qs.data(), (uint32_t)weights.size(), per.data());
     if (rc != TQ_OK) throw_tq(rc);
     for (size_t i = 0; i < per.size(); ++i) total[i] += per[i];
@@ -576,7 +616,7 @@ std::vector<std::vector<DocAddress>> Searcher::docset_batch(const std::vector<We
   std::vector<uint64_t> starts(n + 1);
   std::vector<uint32_t> docs;
   for (auto &seg : segments_) {  // (segments_ is in segment_ord order: the rows stay sorted)
-    SegmentBatch b(*seg, weights, 1);
+    SegmentBatch b(seg, weights, 1);
     int rc = tq_docset_batch(seg->raw(), b.qs.data(), (uint32_t)n, docs.data(), docs.size(), starts.data());
     if (rc == TQ_ERR_INVALID && starts[n] > docs.size()) {  // too small: the call reported the size
       docs.resize(starts[n]);
@@ -598,7 +638,7 @@ std::vector<std::vector<std::pair<DocAddress, Score>>> Searcher::docset_scored_b
   std::vector<uint32_t> docs;
   std::vector<float> scores;
   for (auto &seg : segments_) {  // (segments_ is in segment_ord order: the rows stay sorted)
-    SegmentBatch b(*seg, weights, 1);
+    SegmentBatch b(seg, weights, 1);
     int rc = tq_docset_scored_batch(seg->raw(), b.qs.data(), (uint32_t)n, docs.data(), scores.data(), docs.size(), starts.data());
     if (rc == TQ_ERR_INVALID && starts[n] > docs.size()) {  // too small: the call reported the size
       docs.resize(starts[n]);
@@ -619,7 +659,7 @@ void Searcher::collect_segment_batch_device(size_t segment_ord, const std::vecto
                                             uint32_t k, float *d_scores, uint32_t *d_docs,
                                             uint32_t *d_counts, void *hip_stream) {
   SegmentReader &seg = *segments_[segment_ord];
-  SegmentBatch b(seg, weights, k);
+  SegmentBatch b(segments_[segment_ord], weights, k);
   const tq_search_opts opts{-1, bound_slack_ppm(seg)};
   const int rc = tq_search_batch_device_opts(seg.raw(), b.qs.data(), (uint32_t)weights.size(), k,
                                              d_scores, d_docs, d_counts, &opts, hip_stream);
@@ -674,7 +714,7 @@ Fruit Searcher::search(const Query &query, const TopDocs &collector) {
   std::vector<tq_term_handle> handles(w.terms.size());
   for (size_t s = 0; s < S; ++s) {
     SegmentReader &seg = *segments_[s];
-    for (size_t i = 0; i < w.terms.size(); ++i) handles[i] = seg.term_handle(w.terms[i]);
+    for (size_t i = 0; i < w.terms.size(); ++i) handles[i] = resolve_handle(segments_[s], w, w.terms[i]);
     tq_query q{};
     q.n_terms = (uint32_t)w.terms.size();
     q.terms = handles.data();

@@ -99,9 +99,11 @@ enum class Occur { Should, Must, MustNot };  // src/query/occur.rs
 // TantivyError::Unsupported so that the caller keeps tantivy's own CPU scorer for it
 // (the `SpecializedScorer::Other` branch, boolean_weight.rs:595-597).
 struct Query {
-  enum Kind { Term, Boolean, Phrase, All } kind;
+  enum Kind { Term, Boolean, Phrase, All, TermSet } kind;
   // Term
   uint32_t term = 0;
+  // TermSet: the term ids of a TermSetQuery (or the terms a fuzzy / regex automaton matched)
+  std::vector<uint32_t> set_terms;
   // Boolean: clauses of (Occur, sub query)
   std::vector<std::pair<Occur, Query>> clauses;
   size_t minimum_number_should_match = 0;  // boolean_query.rs:146-150
@@ -122,6 +124,15 @@ struct Query {
   static Query all() {
     Query q;
     q.kind = All;
+    return q;
+  }
+  // TermSetQuery (src/query/set_query.rs) and every other AutomatonWeight query (automaton_weight.rs:87-111): the docs of
+  // the terms OR-ed into a bitset under ConstScorer(boost) — every doc of the set scores the boost.  At the top level or
+  // as a direct clause of a BooleanQuery (tq_term_set_prepare per segment, weights = boost); deeper: Unsupported
+  static Query term_set(std::vector<uint32_t> term_ids) {
+    Query q;
+    q.kind = TermSet;
+    q.set_terms = std::move(term_ids);
     return q;
   }
   static Query boolean(std::vector<std::pair<Occur, Query>> clauses) {
@@ -268,8 +279,29 @@ class InlineVec {
   size_t n_ = 0, cap_ = N;
 };
 
+// A term set of a Weight (Query::term_set): prepared per segment where the Weight resolves its term handles
+// (tq_term_set_prepare over the members' handles), released when the last copy of the Weight goes away
+// (tq_term_set_release on every segment that is still open: a closed segment has freed its sets itself).
+class WeightTermSet {
+ public:
+  explicit WeightTermSet(std::vector<uint32_t> term_ids) : term_ids_(std::move(term_ids)) {}
+  ~WeightTermSet();
+  WeightTermSet(const WeightTermSet &) = delete;
+  WeightTermSet &operator=(const WeightTermSet &) = delete;
+  tq_term_handle handle(const std::shared_ptr<SegmentReader> &seg);
+  const std::vector<uint32_t> &term_ids() const { return term_ids_; }
+
+ private:
+  std::vector<uint32_t> term_ids_;
+  std::mutex m_;
+  std::vector<std::pair<std::weak_ptr<SegmentReader>, tq_term_handle>> prepared_;
+};
+// Weight::terms[i] == kTermSetBase + j: entry i is the Weight's term set j (no term id reaches that range)
+constexpr uint32_t kTermSetBase = 0xFFFFFF00u;
+
 struct Weight {
   uint8_t mode = TQ_MODE_AND;
+  std::vector<std::shared_ptr<WeightTermSet>> sets;  // Query::term_set clauses, named in `terms` by kTermSetBase + index
   InlineVec<uint32_t, 4> terms;          // term ids in query order
   InlineVec<Score, 4> weights;           // per term (AND/OR) or one (phrase)
   std::vector<uint32_t> phrase_offsets;  // phrase
