@@ -307,6 +307,16 @@ int tq_search_batch_device_opts(tq_segment *seg, const tq_query *queries, uint32
                                 uint32_t out_stride, float *d_out_scores, uint32_t *d_out_docs,
                                 uint32_t *d_out_counts, const tq_search_opts *opts,
                                 void *hip_stream);
+/* tq_search_batch_device_opts for an index of ONE segment: the rows are merge_top_k's already (it orders one segment's
+ * hits by score desc, doc asc), so the batch's merge kernels write its column of segment ordinals as well —
+ * d_out_segment_ords[q][i] = segment_ord for i < d_out_counts[q], 0xFFFFFFFF in the padding — and the caller needs no
+ * tq_merge_topk_device launch and no intermediate slab.  With out_stride = k of every query the four arrays are, bit for
+ * bit, what tq_merge_topk_device(offset 0, limit k) makes of tq_search_batch_device_opts' (DESIGN.md §5 has the one
+ * caveat: a row holding both +0.0 and -0.0 scores).  Outputs: device memory, or pinned host memory mapped into the device. */
+int tq_search_batch_device_rows(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                                uint32_t out_stride, float *d_out_scores, uint32_t *d_out_segment_ords,
+                                uint32_t *d_out_docs, uint32_t *d_out_counts, uint32_t segment_ord,
+                                const tq_search_opts *opts, void *hip_stream);
 
 /* ---- concurrent single-query entry (tantivy's own call pattern) ----
  * replaces: Collector::collect_segment(&dyn Weight, segment_ord, &SegmentReader) as
@@ -682,6 +692,13 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous
  *        batches, shared against per-query: 8 queries 0.23 ms against 0.26; 16: 0.25 against 0.37; 64: 0.34
  *        against 0.44; 256: 0.64 against 0.69 — the batches concurrent single-query callers coalesce into),
+ *        "ashare_inline_warm" (0 / 1 / 2, default 1; any other value: TQ_ERR_INVALID): the shared intersections' warm-up
+ *        tasks (the first 2 permille of every leader's blocks, which leave the other tasks a threshold to start from)
+ *        0 = in a dispatch of their own before the main one, 2 = in front of ONE dispatch, followed by the main tasks
+ *        of leaders that have no warm-up task — as many as the resident wavefronts that find no warm-up task —, then by
+ *        all the others in doc-slice order, 1 = as 2 where the intersections are the batch's only launch group and have
+ *        that many independent tasks, else as 0 (a small batch keeps its barrier; next to another group's kernels the
+ *        chip is not the launch's own).  Results do not depend on it: thresholds are advisory,
  *        "submit_window_us" (default 100): tq_submit / tq_search_one — how long the leader of a batch
  *        holds it open for the callers of the previous batch to come back with their next query
  *        (0 = launch with whatever is pending),

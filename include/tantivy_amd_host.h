@@ -127,6 +127,21 @@ int tqh_collect_segment_prepared(tqh_searcher *s, uint32_t segment_ord, uint32_t
 int tqh_collect_segment_prepared_device(tqh_searcher *s, uint32_t segment_ord, uint32_t k,
                                         float *d_scores, uint32_t *d_docs, uint32_t *d_counts,
                                         void *hip_stream);
+/* Searcher::search of the prepared batch with TopDocs::with_limit(k) on the device as ONE call (src/core/searcher.rs:
+ * 180-238: collect_segment on every segment, then merge_fruits): everything is enqueued on hip_stream, the host never
+ * waits.  out_* ([n][k] x 3, [n]): device memory, or pinned host memory mapped into the device.  Rows as
+ * tqh_search_prepared(offset 0, limit k) leaves them.
+ *   one segment       its merge kernels write the four arrays themselves (tq_search_batch_device_rows): no merge_top_k
+ *                     launch, the slabs are not touched and may be NULL
+ *   several segments  segment s collects into part s of the slabs (d_slab_scores / d_slab_docs: [S][n][k],
+ *                     d_slab_counts: [S][n], device memory on the segments' one device), then ONE tq_merge_topk_device
+ *                     launch; HIP events around it feed tqh_exchange_ms */
+int tqh_search_prepared_device(tqh_searcher *s, uint32_t k, float *out_scores, uint32_t *out_segment_ords,
+                               uint32_t *out_docs, uint32_t *out_counts, float *d_slab_scores,
+                               uint32_t *d_slab_docs, uint32_t *d_slab_counts, void *hip_stream);
+/* *ms = mean GPU time of the merge_top_k launches of the last (<= 16) tqh_search_prepared_device calls since the
+ * previous tqh_exchange_ms (waits for them to finish); 0.0 when none ran, as with one segment. */
+int tqh_exchange_ms(tqh_searcher *s, float *ms);
 /* Bm25Weight::for_terms(...).boost_by(boost): weight + 256-entry tf cache. */
 int tqh_bm25_for_terms(const uint64_t *term_doc_freqs, uint32_t n_terms, uint64_t total_num_docs,
                        uint64_t total_num_tokens, float boost, float *weight_out,

@@ -120,7 +120,7 @@ EXPORTS = [
     "tq_init", "tq_shutdown", "tq_last_error", "tq_segment_upload", "tq_segment_upload_device",
     "tq_segment_free",
     "tq_term_prepare", "tq_term_prepare_batch", "tq_search_batch", "tq_search_batch_device", "tq_search_batch_opts",
-    "tq_search_batch_device_opts", "tq_merge_topk",
+    "tq_search_batch_device_opts", "tq_search_batch_device_rows", "tq_merge_topk",
     "tq_merge_topk_device", "tq_copy_to_host_async", "tq_decode_postings", "tq_decode_position_deltas",
     "tq_last_batch_stats", "tq_segment_get_stats", "tq_segment_reserve_columns", "tq_set_option", "tq_segment_set_alive_bitset", "tq_count_batch",
     "tq_last_batch_match_counts", "tq_last_batch_query_kernels", "tq_encoder_create", "tq_encoder_free", "tq_encode_postings",
@@ -129,7 +129,7 @@ EXPORTS = [
     "tq_comm_info", "tq_allgather_topk",
     "tqh_last_error", "tqh_searcher_new", "tqh_searcher_free", "tqh_searcher_add_segment",
     "tqh_prepare_batch", "tqh_prepare_batch_next", "tqh_commit_next", "tqh_search_prepared", "tqh_collect_segment_prepared",
-    "tqh_collect_segment_prepared_device", "tqh_searcher_add_remote_stats",
+    "tqh_collect_segment_prepared_device", "tqh_search_prepared_device", "tqh_exchange_ms", "tqh_searcher_add_remote_stats",
     "tqh_bm25_for_terms", "tqh_segment_raw", "tqh_term_handle", "tqh_term_dictionary_values",
     "tqh_term_info_store_open", "tqh_term_info_store_free", "tqh_term_info_store_num_terms",
     "tqh_term_info_store_get", "tqh_term_info_store_write", "tqh_searcher_add_segment_with_store",
@@ -170,6 +170,8 @@ def lib():
                                        u32p, C.POINTER(TqSearchOpts)]
     L.tq_search_batch_device_opts.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, vp,
                                               vp, vp, C.POINTER(TqSearchOpts), vp]
+    L.tq_search_batch_device_rows.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, vp, vp,
+                                              vp, vp, C.c_uint32, C.POINTER(TqSearchOpts), vp]
     L.tq_merge_topk.argtypes = [f32p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_uint32, f32p, u32p, u32p, u32p]
     L.tq_copy_to_host_async.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp]
@@ -231,6 +233,8 @@ def lib():
     L.tq_wait.argtypes = [vp]
     L.tqh_collect_segment_prepared.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, u32p, u32p]
     L.tqh_collect_segment_prepared_device.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.tqh_search_prepared_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tqh_exchange_ms.argtypes = [vp, f32p]
     L.tqh_searcher_add_remote_stats.argtypes = [vp, C.c_uint64, C.c_uint64, u32p, u32p, C.c_uint32]
     L.tqh_bm25_for_terms.argtypes = [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.c_uint64,
                                      C.c_float, f32p, f32p]
@@ -711,6 +715,22 @@ class DeviceIndex:
         _check(lib().tqh_collect_segment_prepared_device(
             self._s, int(segment_ord), int(k), d_scores.data_ptr(), d_docs.data_ptr(),
             d_counts.data_ptr(), C.c_void_p(stream) if stream else None), host=True)
+
+    def search_prepared_device(self, k, out, slabs=None, stream=None):
+        """Searcher::search of the prepared batch, limit k, as one native call that only enqueues work on `stream`
+        (tqh_search_prepared_device).  out = (scores float32 [n,k], segment ordinals, docs int32 [n,k], counts int32 [n]):
+        torch tensors on the segments' GPU or in pinned host memory; slabs = ([S*n,k] float32, [S*n,k] int32, [S*n] int32)
+        device tensors, needed with several segments."""
+        sl = [t.data_ptr() for t in slabs] if slabs is not None else [None, None, None]
+        _check(lib().tqh_search_prepared_device(
+            self._s, int(k), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+            sl[0], sl[1], sl[2], C.c_void_p(stream) if stream else None), host=True)
+
+    def exchange_ms(self):
+        """Mean GPU time of the merge_top_k launches of the last (<= 16) search_prepared_device calls; 0.0 with one segment."""
+        ms = C.c_float(0.0)
+        _check(lib().tqh_exchange_ms(self._s, C.byref(ms)), host=True)
+        return float(ms.value)
 
     @property
     def ctx(self):

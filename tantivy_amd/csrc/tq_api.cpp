@@ -496,6 +496,8 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.docset_trees = (int)value;
   else if (!strcmp(name, "docset_score_trees") && (value == 0 || value == 1))
     s->opt.docset_score_trees = (int)value;
+  else if (!strcmp(name, "ashare_inline_warm") && value >= 0 && value <= 2)
+    s->opt.ashare_inline_warm = (int)value;
   else if (!strcmp(name, "ashare_min_batch") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.ashare_min_batch = (int)value;
   else if (!strcmp(name, "xunion_min_queries") && value >= 1 && value <= 0x7FFFFFFF)

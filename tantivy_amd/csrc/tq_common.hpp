@@ -472,6 +472,34 @@ __device__ __forceinline__ void flush_partial(const TopK<KPL> &tk, uint64_t *par
   }
 }
 
+// The output epilogue of merge_kernel and merge_lists_kernel: a query's sorted top-k -> row out_q of the caller's
+// arrays, padded with (0.0, TQD_TERMINATED) up to out_stride, and its count of real hits.  With
+// TqkMergeParams::out_segment_ords the row also gets merge_top_k's column for an index of ONE segment: the segment's
+// ordinal below the count, 0xFFFFFFFF in the padding (what merge_segments_kernel writes for its one slab).
+template <int KPL>
+__device__ __forceinline__ void write_topk_rows(const TqkMergeParams &p, const TopK<KPL> &tk, uint32_t k, uint32_t out_q,
+                                                int lane) {
+  const uint64_t row = (uint64_t)out_q * p.out_stride;
+  uint32_t count = 0;
+#pragma unroll
+  for (int r = 0; r < KPL; ++r) {
+    const uint32_t rank = (uint32_t)r * 64u + (uint32_t)lane;
+    const bool real = rank < k && tk.v[r] != 0ull;
+    count += (uint32_t)__popcll(__ballot(real));
+    if (rank < p.out_stride) {
+      p.out_scores[row + rank] = real ? key_score(tk.v[r]) : 0.0f;
+      p.out_docs[row + rank] = real ? key_doc(tk.v[r]) : TQD_TERMINATED;
+      if (p.out_segment_ords) p.out_segment_ords[row + rank] = real ? p.segment_ord : 0xFFFFFFFFu;
+    }
+  }
+  for (uint32_t rank = (uint32_t)(KPL * 64) + (uint32_t)lane; rank < p.out_stride; rank += 64u) {
+    p.out_scores[row + rank] = 0.0f;
+    p.out_docs[row + rank] = TQD_TERMINATED;
+    if (p.out_segment_ords) p.out_segment_ords[row + rank] = 0xFFFFFFFFu;
+  }
+  if (lane == 0) p.out_counts[out_q] = count;
+}
+
 __device__ __forceinline__ uint32_t sortable(float x) {
   uint32_t fb = __float_as_uint(x);
   return fb ^ ((uint32_t)((int32_t)fb >> 31) | 0x80000000u);

@@ -203,6 +203,8 @@ struct Options {
   int docset_temp_lists = 0;     // doc sets: lists without a bitmap scattered per launch (0 = what TQ_COUNT_TEMP_MB holds, at most 4096)
   int docset_trees = 0;          // doc sets: phrases and nested boolean queries through tq_docset_tree.hip (0 = refused, as before)
   int docset_score_trees = 0;    // scored doc sets: the same shapes, scored by tq_docset_tree_score.hip (0 = refused, as before)
+  int ashare_inline_warm = 1;   // intersections: 0 = warm-up and main tasks as two dispatches, 1 = ONE dispatch where they are the batch's only
+                                // group and tasks of leaders without warm-up tasks fill the grid (build_ashare_plan), 2 = always one dispatch
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
   // tq_submit / tq_search_one: how long the leader of a batch waits for the callers of the previous
   // batch to come back with their next query (0 = launch with whatever is pending)
@@ -631,7 +633,12 @@ struct PlanScratch {
       size_t task0;
     };
     std::vector<ARun> aruns;
-    uint32_t a_warm_tasks = 0;  // tasks [0, a_warm_tasks) are the warm-up launch
+    uint32_t a_warm_tasks = 0;  // tasks [0, a_warm_tasks) are the warm-up launch (band 1)
+    // one dispatch for the whole launch (option "ashare_inline_warm"): the main tasks come in two bands — [a_warm_tasks,
+    // a_dep_tasks) tasks of leaders WITHOUT warm-up tasks from the first doc slices, as many as the resident wavefronts
+    // need, [a_dep_tasks, end) all the others — each in doc-slice order; false: one band, a_dep_tasks = a_warm_tasks
+    bool a_inline = false;
+    uint32_t a_dep_tasks = 0;
     bool over_budget = false;   // the last plan failed because its result lists exceed TQ_AS_LIST_MB at the longest tasks
     bool any_rdir = false;      // (boolean leads) some list of alists is probed through its range directory
   };
@@ -966,7 +973,8 @@ void docset_tree_view(const tq_query &q, TreeView &v, bool scored = false);  // 
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);
-int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean = false);
+// resident: the wavefronts the launch keeps on the chip (its grid before the cap by the task count); 0 = not known
+int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean = false, uint32_t resident = 0);
 int build_dense_plan(tq_segment *s, Group &g, PlanScratch &ps, uint32_t cus);
 int plan_bool_query(tq_segment *s, const tq_query &q, uint32_t qi, TqdQuery &dq, uint64_t &qbytes,
                     uint32_t &n_tiles, uint32_t &tile_cost, uint32_t &n_thr_rows, bool exhaustive);
@@ -982,7 +990,7 @@ int build_tree_query_probe_tables(tq_segment *s, const tq_query &q, bool *built,
 int fail_tree_tables(const tq_segment *s, uint32_t qi);  // "use_dense" off, or the tables outside one 32 GB span: TQ_ERR_UNSUPPORTED
 int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *d_out_scores, uint32_t *d_out_docs, uint32_t *d_out_counts, void *hip_stream,
-                      const CallOpts &co);
+                      const CallOpts &co, uint32_t *d_out_segment_ords = nullptr, uint32_t segment_ord = 0);
 int search_batch_host(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *out_scores, uint32_t *out_docs, uint32_t *out_counts, const CallOpts &co);
 // The same in two halves (the submit queue: the next coalesced batch is planned and enqueued while this one runs):

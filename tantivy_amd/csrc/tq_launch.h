@@ -154,6 +154,10 @@ struct TqkMergeParams {
   // (s + 1) * per), per = tqk_merge_slice_lists(n_parts, pre_slices) — into the slice's FIRST list, in place; the
   // final launch then reads one list per slice.  Queries with fewer than TQK_MERGE_PRE_MIN lists are left alone.
   uint32_t pre_slices;
+  // an index of one segment: the rows are merge_top_k's already, this is its column of segment ordinals ([query][out_stride],
+  // write_topk_rows in tq_common.hpp); null = no such column
+  uint32_t *out_segment_ords;
+  uint32_t segment_ord;
 };
 constexpr uint32_t TQK_MERGE_PRE_MIN = 96;
 inline __host__ __device__ uint32_t tqk_merge_slice_lists(uint32_t n_parts, uint32_t pre_slices) {

@@ -68,23 +68,7 @@ __global__ __launch_bounds__(64) void merge_kernel(TqkMergeParams p) {
     flush_partial<KPL>(tk, const_cast<uint64_t *>(p.partials), part_start, lane);
     return;
   }
-  const uint32_t out_q = p.out_index ? p.out_index[q] : q;
-  uint32_t count = 0;
-#pragma unroll
-  for (int r = 0; r < KPL; ++r) {
-    const uint32_t rank = (uint32_t)r * 64u + (uint32_t)lane;
-    const bool real = rank < k && tk.v[r] != 0ull;
-    count += (uint32_t)__popcll(__ballot(real));
-    if (rank < p.out_stride) {
-      p.out_scores[(uint64_t)out_q * p.out_stride + rank] = real ? key_score(tk.v[r]) : 0.0f;
-      p.out_docs[(uint64_t)out_q * p.out_stride + rank] = real ? key_doc(tk.v[r]) : TQD_TERMINATED;
-    }
-  }
-  for (uint32_t rank = (uint32_t)(KPL * 64) + (uint32_t)lane; rank < p.out_stride; rank += 64u) {
-    p.out_scores[(uint64_t)out_q * p.out_stride + rank] = 0.0f;
-    p.out_docs[(uint64_t)out_q * p.out_stride + rank] = TQD_TERMINATED;
-  }
-  if (lane == 0) p.out_counts[out_q] = count;
+  write_topk_rows<KPL>(p, tk, k, p.out_index ? p.out_index[q] : q, lane);
 }
 
 // =================================================================== batch-start zeroing

@@ -252,7 +252,7 @@ retry_tasks:
 // group gets one task per run of blocks of the leader.  Tasks are launched in doc order (all
 // leaders' runs of the first 1/4096 of the doc-id space, then the next, ...): the chip works on one
 // part of the doc matrix at a time, and every query's threshold rises as its leader is walked.
-int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean) {
+int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean, uint32_t resident) {
   PlanScratch::ASharePlan &A = ps.ap[boolean ? 1 : 0];
   // (block, lead) pairs per task of the intersections: 0 = sized per batch so that the launch has about
   // kTargetTasks tasks (three per resident wavefront), between 64 and 512 pairs — with identical queries evaluated
@@ -697,10 +697,35 @@ int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean) {
   }
   if (n_tasks > 0x7FFFFFFFull) return fail(TQ_ERR_UNSUPPORTED, "batch too large (tasks)");
   tasks.resize(n_tasks);
+  // One dispatch instead of two (intersections, option "ashare_inline_warm"): the warm-up tasks stay in front (band 1);
+  // behind them come main tasks of leaders that HAVE no warm-up task — nothing of theirs is warmed up, they depend on
+  // nothing — from the first doc slices on, as many as the resident wavefronts that find no warm-up task (band 2); then
+  // everything else in one sweep over the doc slices (band 3).  Nothing waits on the device: a dependent task that
+  // starts before its leader's warm-up tasks have ended finds lower thresholds, and thresholds only ever hold scores of k
+  // real matches (tq_ashare.hip).  Mode 1 wants every resident wavefront to find a warm-up or an independent task first:
+  // a batch with fewer independent tasks than that keeps the two dispatches, stream order as its barrier.
+  uint64_t band2_want = 0;
+  {
+    static const uint32_t kInlineEnv = tune_u32("TQ_AS_INLINE_WARM", 0xFFFFFFFFu);  // (A/B runs: overrides the option)
+    const uint32_t mode = boolean ? 0u : kInlineEnv != 0xFFFFFFFFu ? kInlineEnv : (uint32_t)s->opt.ashare_inline_warm;
+    uint64_t n_warm = 0, n_indep = 0;
+    for (const PlanScratch::ASharePlan::ARun &R : runs) {
+      const uint64_t warm = (uint64_t)((R.nb_warm + kWarmBlocks - 1) / kWarmBlocks) * R.n_groups;
+      n_warm += warm;
+      if (!R.nb_warm) n_indep += (uint64_t)R.n_runs * R.n_groups;
+    }
+    const uint64_t grid = std::min<uint64_t>(n_tasks, resident);
+    band2_want = grid - std::min(grid, n_warm);
+    A.a_inline = n_warm != 0 && (mode == 2u || (mode == 1u && resident != 0 && n_indep >= band2_want));
+    static const bool kBand2All = tune_u32("TQ_AS_BAND2_ALL", 0) != 0;  // (experiment: every independent task before any other)
+    if (kBand2All) band2_want = ~0ull;
+  }
+  const bool bands = A.a_inline;
   // slabs of runs of about equal task counts: each counts its tasks by doc slice; the (slice, slab) prefix
   // sums give every slab its places in the launch order (a stable counting sort: slice 0 = the warm-up
-  // launch, then the main launch's tasks by doc slice); a second walk over the runs writes the tasks there
-  constexpr uint32_t kSl = 4098;
+  // tasks, then the main tasks by doc slice — 4 096 slices; with `bands`, 2 048 slices with separate counters for the
+  // leaders without warm-up tasks and for the others); a second walk over the runs writes the tasks there
+  constexpr uint32_t kSl = 4098, kBand3 = 2049;
   const uint32_t t_slabs = n_tasks >= 16384 ? std::min<uint32_t>(plan_threads(), (uint32_t)runs.size()) : 1u;
   std::vector<uint32_t> &hist = A.atask_hist;
   hist.assign((size_t)t_slabs * kSl, 0u);
@@ -718,7 +743,8 @@ int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean) {
     for (uint32_t j0 = 0; j0 < R.n_blocks;) {
       const bool warm = j0 < R.nb_warm;
       const uint32_t nb = warm ? std::min<uint32_t>(kWarmBlocks, R.nb_warm - j0) : std::min<uint32_t>(R.bpt, R.n_blocks - j0);
-      emit(j0, nb, warm ? 0u : 1u + std::min<uint32_t>(4095u, (uint32_t)((j0 * slice_mul) >> 32)));
+      const uint32_t slice = std::min<uint32_t>(4095u, (uint32_t)((j0 * slice_mul) >> 32));
+      emit(j0, nb, warm ? 0u : !bands ? 1u + slice : (R.nb_warm ? kBand3 : 1u) + (slice >> 1));
       j0 += nb;
     }
   };
@@ -735,13 +761,26 @@ int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean) {
   });
   {
     uint32_t run = 0;
-    for (uint32_t sl = 0; sl < kSl; ++sl)
+    auto place = [&](uint32_t sl) {  // the tasks counted under key sl come next in the launch order
       for (uint32_t sb = 0; sb < t_slabs; ++sb) {
         const uint32_t n = hist[(size_t)sb * kSl + sl];
         hist[(size_t)sb * kSl + sl] = run;  // becomes the slab's write position in this slice
         run += n;
-        if (sl == 0 && sb + 1 == t_slabs) A.a_warm_tasks = run;
       }
+    };
+    place(0);
+    A.a_warm_tasks = A.a_dep_tasks = run;
+    if (!bands) {
+      for (uint32_t sl = 1; sl < kSl; ++sl) place(sl);
+    } else {
+      uint32_t c = 1;  // band 2: the independent tasks of slices [1, c)
+      while (c < kBand3 && run - A.a_warm_tasks < band2_want) place(c++);
+      A.a_dep_tasks = run;
+      for (uint32_t sl = 0; sl + 1u < kBand3; ++sl) {  // band 3: one sweep, both kinds
+        if (1u + sl >= c) place(1u + sl);
+        place(kBand3 + sl);
+      }
+    }
   }
   parallel_slabs(t_slabs, [&](uint32_t sb) {
     uint32_t *h = hist.data() + (size_t)sb * kSl;

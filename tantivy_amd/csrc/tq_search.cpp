@@ -34,6 +34,8 @@ struct Batch {
   uint32_t *out_docs, *out_counts;
   void *hip_stream;
   CallOpts co;
+  uint32_t *out_segment_ords;  // tq_search_batch_device_rows: the rows' column of segment ordinals, or null
+  uint32_t segment_ord;
   bool replan = false;  // plan_batch: a shared launch is over its list budget, co now keeps that family off
   hipStream_t st = nullptr;
   bool exhaustive = false, or_windows = false;
@@ -872,10 +874,19 @@ int route_queries(Batch &b) {
   return TQ_OK;
 }
 
+// The wavefronts a shared-intersection launch keeps resident: its grid before the cap by the task count.
+uint32_t ashare_resident(int cus) {
+  static const uint32_t kAGridMul = tune_u32("TQ_AS_GRID_MUL", 0);
+  return (uint32_t)std::max(1, cus) * (kAGridMul ? kAGridMul : tqk_ashare_waves_per_cu());
+}
+
 // Tiles -> chunks / tasks -> partial or result lists per group, in one buffer; `replan` if a shared launch is over budget.
 int plan_group_tasks(Batch &b) {
   PlanScratch &ps = *b.ps;
   (void)hipDeviceGetAttribute(&b.cus, hipDeviceAttributeMultiprocessorCount, b.s->device);
+  // (the intersections' one-dispatch rule counts on the launch's resident wavefronts: next to another group's kernels —
+  // launch_groups runs them side by side — they are not its own, and the mixed stream measured 8 % slower with one dispatch)
+  const bool alone = std::count_if(b.groups, b.groups + kNGroups, [](const Group &g) { return !g.queries.empty(); }) == 1;
   for (int gi = 0; gi < kNGroups; ++gi) {
     Group &g = b.groups[gi];
     if (g.queries.empty()) continue;
@@ -893,7 +904,7 @@ int plan_group_tasks(Batch &b) {
       continue;
     }
     const int rc = gi == kGUShare   ? build_share_plan(b.s, g, ps)
-                   : gi == kGAShare ? build_ashare_plan(b.s, g, ps, false)
+                   : gi == kGAShare ? build_ashare_plan(b.s, g, ps, false, alone ? ashare_resident(b.cus) : 0u)
                    : gi == kGBShare ? build_ashare_plan(b.s, g, ps, true)
                    : gi == kGXUnion ? build_dense_plan(b.s, g, ps, (uint32_t)std::max(1, b.cus))
                                     : build_group_chunks(g, b.or_windows && gi != kGBool, ps, gi == kGBool);
@@ -1155,7 +1166,8 @@ void common_params(P &p, const Batch &b, const Group &g) {
   p.bound_slack = b.co.bound_slack;
 }
 
-// A shared-intersection launch: the warm-up tasks, then the rest (stream order = the barrier between them).
+// A shared-intersection launch: the warm-up tasks, then the rest (stream order = the barrier between them) — or, where
+// build_ashare_plan put the independent main tasks behind the warm-up tasks (ASharePlan::a_inline), all of them at once.
 int launch_ashare(const Batch &b, int gi, hipStream_t gst) {
   const Group &g = b.groups[gi];
   const int ai = gi == kGBShare ? 1 : 0;
@@ -1186,7 +1198,7 @@ int launch_ashare(const Batch &b, int gi, hipStream_t gst) {
   static const uint32_t kBoundMode = tune_u32("TQ_AS_BOUND", 3);
   ap.bound_mode = kBoundMode;
   ap.n_queues = 1;
-  const uint32_t bounds[3] = {0u, b.ps->ap[ai].a_warm_tasks, g.n_chunks};
+  const uint32_t bounds[3] = {0u, b.ps->ap[ai].a_inline ? g.n_chunks : b.ps->ap[ai].a_warm_tasks, g.n_chunks};
   for (int ph = 0; ph < 2; ++ph) {
     ap.task_begin = bounds[ph];
     ap.n_tasks = bounds[ph + 1];
@@ -1370,6 +1382,8 @@ int launch_merges(const Batch &b) {
     m.out_scores = b.out_scores;
     m.out_docs = b.out_docs;
     m.out_counts = b.out_counts;
+    m.out_segment_ords = b.out_segment_ords;
+    m.segment_ord = b.segment_ord;
     m.n_queries = (uint32_t)g.queries.size();
     m.out_stride = b.out_stride;
     if (!kGroupTraits[gi].result_lists) {
@@ -1538,7 +1552,8 @@ size_t host_rows_layout(uint32_t n_queries, uint32_t out_stride, size_t &o_docs,
 
 int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries,
                       uint32_t out_stride, float *d_out_scores, uint32_t *d_out_docs,
-                      uint32_t *d_out_counts, void *hip_stream, const CallOpts &co) {
+                      uint32_t *d_out_counts, void *hip_stream, const CallOpts &co, uint32_t *d_out_segment_ords,
+                      uint32_t segment_ord) {
   if (!s || (!queries && n_queries) || !d_out_scores || !d_out_docs || !d_out_counts)
     return fail(TQ_ERR_INVALID, "tq_search_batch: null argument");
   if (n_queries == 0) return TQ_OK;
@@ -1546,14 +1561,14 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
   int rc = strip_all_clauses(s, queries, n_queries, strip);
   if (rc != TQ_OK) return rc;
   if (!strip.eff.empty()) queries = strip.eff.data();
-  Batch b{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, co};
+  Batch b{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, co, d_out_segment_ords, segment_ord};
   b.n_all_queries = strip.n_all_based;
   b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
   rc = plan_batch(b);
   // a shared launch's result lists over the budget even with the longest tasks: the same batch again, that family
   // through the per-query kernels
   while (rc != TQ_OK && b.replan) {
-    b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co};
+    b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co, d_out_segment_ords, segment_ord};
     b.n_all_queries = strip.n_all_based;
     b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
     rc = plan_batch(b);
@@ -1670,6 +1685,26 @@ int tq_search_batch_device_opts(tq_segment *s, const tq_query *queries, uint32_t
     return fail(TQ_ERR_HIP, "tq_search_batch_device: %s", e.what());
   } catch (...) {
     return fail(TQ_ERR_HIP, "tq_search_batch_device: unknown exception");
+  }
+}
+
+int tq_search_batch_device_rows(tq_segment *s, const tq_query *queries, uint32_t n_queries,
+                                uint32_t out_stride, float *d_out_scores, uint32_t *d_out_segment_ords,
+                                uint32_t *d_out_docs, uint32_t *d_out_counts, uint32_t segment_ord,
+                                const tq_search_opts *opts, void *hip_stream) {
+  if (!s) return fail(TQ_ERR_INVALID, "tq_search_batch: null segment");
+  if (!d_out_segment_ords) return fail(TQ_ERR_INVALID, "tq_search_batch_device_rows: null argument");
+  try {
+    TQ_SEGMENT_LOCK(s);
+    CallOpts co;
+    const int rc = resolve_opts(s, opts, co);
+    if (rc != TQ_OK) return rc;
+    return search_batch_impl(s, queries, n_queries, out_stride, d_out_scores, d_out_docs,
+                             d_out_counts, hip_stream, co, d_out_segment_ords, segment_ord);
+  } catch (const std::exception &e) {
+    return fail(TQ_ERR_HIP, "tq_search_batch_device_rows: %s", e.what());
+  } catch (...) {
+    return fail(TQ_ERR_HIP, "tq_search_batch_device_rows: unknown exception");
   }
 }
 

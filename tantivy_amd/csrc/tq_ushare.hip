@@ -873,46 +873,84 @@ ushare_kernel(TqkShareParams p) {
 
 // One wavefront per query: the query's result list (list_count entries) -> sorted top-k.
 // QT: the group's query record — TqdQuery, or the shared intersections' TqdAQuery (k, chunk_first, part_start).
+// A workgroup holds kMergeWaves queries.  Rows of up to kMergeStageRow slots (k <= 64) leave through LDS: where the
+// workgroup's queries own CONSECUTIVE output rows (a batch of one launch group: out_index is the identity) the rows
+// go out as one contiguous run per array, full 64-byte lines — the rows of a host-output batch and of
+// tq_search_batch_device_rows are written over PCIe into pinned host memory, where 10 000 x 4 stores of 40 bytes each
+// cost 0.05 ms more than the same rows as whole lines.  Otherwise every wavefront writes its own row (write_topk_rows).
+constexpr uint32_t kMergeWaves = 16, kMergeStageRow = 64;
 template <int KPL, typename QT>
-__global__ __launch_bounds__(64) void merge_lists_kernel(TqkMergeParams p, const uint32_t *list_count) {
+__global__ __launch_bounds__(64 * kMergeWaves) void merge_lists_kernel(TqkMergeParams p, const uint32_t *list_count) {
+  __shared__ uint32_t s_rows[3][kMergeWaves * kMergeStageRow];  // scores | docs | segment ordinals, rows packed at out_stride
+  __shared__ uint32_t s_out_q[kMergeWaves], s_count[kMergeWaves];
   const int lane = (int)__lane_id();
-  const uint32_t q = blockIdx.x;
-  if (q >= p.n_queries) return;
-  const QT *Q = uni_ptr(reinterpret_cast<const QT *>(p.queries) + q);
-  const uint32_t k = uni(Q->k);
-  // (chunk_first: the query that owns the list — q itself, or the identical query of the batch that was
-  // evaluated in its place, build_ashare_plan)
-  const uint32_t n = uni(list_count[uni(Q->chunk_first)]);
-  const uint64_t *src = p.partials + (size_t)uni(Q->part_start);
-  TopK<KPL> tk;
-  tk.reset(k);
-  for (uint32_t i0 = 0; i0 < n; i0 += 256u) {  // four loads in flight per step
-    uint64_t keys[4];
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const uint32_t q0 = blockIdx.x * kMergeWaves, q = q0 + wave;
+  const bool staged = p.out_stride <= kMergeStageRow;  // (uniform over the launch)
+  if (q < p.n_queries) {
+    const QT *Q = uni_ptr(reinterpret_cast<const QT *>(p.queries) + q);
+    const uint32_t k = uni(Q->k);
+    // (chunk_first: the query that owns the list — q itself, or the identical query of the batch that was
+    // evaluated in its place, build_ashare_plan)
+    const uint32_t n = uni(list_count[uni(Q->chunk_first)]);
+    const uint64_t *src = p.partials + (size_t)uni(Q->part_start);
+    TopK<KPL> tk;
+    tk.reset(k);
+    for (uint32_t i0 = 0; i0 < n; i0 += 256u) {  // four loads in flight per step
+      uint64_t keys[4];
 #pragma unroll
-    for (uint32_t u = 0; u < 4u; ++u) {
-      const uint32_t i = i0 + 64u * u + (uint32_t)lane;
-      keys[u] = i < n ? src[i] : 0ull;
+      for (uint32_t u = 0; u < 4u; ++u) {
+        const uint32_t i = i0 + 64u * u + (uint32_t)lane;
+        keys[u] = i < n ? src[i] : 0ull;
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 4u; ++u) tk.offer(keys[u] != 0ull, keys[u], lane);
     }
-#pragma unroll
-    for (uint32_t u = 0; u < 4u; ++u) tk.offer(keys[u] != 0ull, keys[u], lane);
-  }
-  const uint32_t out_q = p.out_index ? p.out_index[q] : q;
-  uint32_t count = 0;
-#pragma unroll
-  for (int r = 0; r < KPL; ++r) {
-    const uint32_t rank = (uint32_t)r * 64u + (uint32_t)lane;
-    const bool real = rank < k && tk.v[r] != 0ull;
-    count += (uint32_t)__popcll(__ballot(real));
-    if (rank < p.out_stride) {
-      p.out_scores[(uint64_t)out_q * p.out_stride + rank] = real ? key_score(tk.v[r]) : 0.0f;
-      p.out_docs[(uint64_t)out_q * p.out_stride + rank] = real ? key_doc(tk.v[r]) : TQD_TERMINATED;
+    const uint32_t out_q = p.out_index ? p.out_index[q] : q;
+    if (!staged) {
+      write_topk_rows<KPL>(p, tk, k, out_q, lane);
+    } else {  // (k <= out_stride <= 64: the row is v[0] of lanes [0, out_stride))
+      const bool real = (uint32_t)lane < k && tk.v[0] != 0ull;
+      const uint32_t count = (uint32_t)__popcll(__ballot(real));
+      if ((uint32_t)lane < p.out_stride) {
+        const uint32_t at = wave * p.out_stride + (uint32_t)lane;
+        s_rows[0][at] = real ? __float_as_uint(key_score(tk.v[0])) : __float_as_uint(0.0f);
+        s_rows[1][at] = real ? key_doc(tk.v[0]) : TQD_TERMINATED;
+        s_rows[2][at] = real ? p.segment_ord : 0xFFFFFFFFu;
+      }
+      if (lane == 0) {
+        s_out_q[wave] = out_q;
+        s_count[wave] = count;
+      }
     }
   }
-  for (uint32_t rank = (uint32_t)(KPL * 64) + (uint32_t)lane; rank < p.out_stride; rank += 64u) {
-    p.out_scores[(uint64_t)out_q * p.out_stride + rank] = 0.0f;
-    p.out_docs[(uint64_t)out_q * p.out_stride + rank] = TQD_TERMINATED;
+  if (!staged) return;
+  __syncthreads();
+  const uint32_t n_live = p.n_queries - q0 < kMergeWaves ? p.n_queries - q0 : kMergeWaves;
+  const uint32_t base = s_out_q[0];
+  const bool in_run = (uint32_t)lane >= n_live || s_out_q[(uint32_t)lane < n_live ? lane : 0] == base + (uint32_t)lane;
+  const bool contiguous = __ballot(in_run) == ~0ull;
+  uint32_t *o_scores = reinterpret_cast<uint32_t *>(p.out_scores);
+  if (contiguous) {
+    const uint32_t i = threadIdx.x;  // (n_live * out_stride <= 1 024 = the workgroup)
+    if (i < n_live * p.out_stride) {
+      const uint64_t o = (uint64_t)base * p.out_stride + i;
+      o_scores[o] = s_rows[0][i];
+      p.out_docs[o] = s_rows[1][i];
+      if (p.out_segment_ords) p.out_segment_ords[o] = s_rows[2][i];
+    }
+    if (i < n_live) p.out_counts[base + i] = s_count[i];
+  } else if (q < p.n_queries) {
+    const uint32_t out_q = s_out_q[wave];
+    if ((uint32_t)lane < p.out_stride) {
+      const uint32_t at = wave * p.out_stride + (uint32_t)lane;
+      const uint64_t o = (uint64_t)out_q * p.out_stride + (uint32_t)lane;
+      o_scores[o] = s_rows[0][at];
+      p.out_docs[o] = s_rows[1][at];
+      if (p.out_segment_ords) p.out_segment_ords[o] = s_rows[2][at];
+    }
+    if (lane == 0) p.out_counts[out_q] = s_count[wave];
   }
-  if (lane == 0) p.out_counts[out_q] = count;
 }
 
 }  // namespace
@@ -933,7 +971,7 @@ hipError_t tqk_launch_share(const TqkShareParams &p, int kpl, hipStream_t st) {
 hipError_t tqk_launch_merge_lists(const TqkMergeParams &m, const uint32_t *list_count, int kpl, bool compact,
                                   hipStream_t st) {
   if (m.n_queries == 0) return hipSuccess;
-  const dim3 grid(m.n_queries), block(64);
+  const dim3 grid((m.n_queries + kMergeWaves - 1u) / kMergeWaves), block(64u * kMergeWaves);
   if (compact) {
     switch (kpl) {
       case 1: merge_lists_kernel<1, TqdAQuery><<<grid, block, 0, st>>>(m, list_count); break;

@@ -133,7 +133,9 @@ class ShardRunner:
     order) resident on `device`, the global statistics of the others added as remote statistics.
     enqueue() = for every local segment collect_segment (tq_search_batch_device) into its slab,
     one all-gather of the slabs, merge_top_k on the device, asynchronous copies to pinned host
-    memory — all on one HIP stream, nothing waits for the GPU."""
+    memory — all on one HIP stream, nothing waits for the GPU.  With one rank and no forced exchange
+    the whole step is ONE native call (tqh_search_prepared_device: Searcher::search on the device);
+    an index of one segment then has its rows written once, by the segment's own merge kernels."""
 
     def __init__(self, segments, device, rank=0, world=1, remote_stats=(), comm=None,
                  torch_group=None, force_exchange=False):
@@ -157,6 +159,7 @@ class ShardRunner:
         self._ev_at = 0
         self._trace = bool(os.environ.get("TQ_RUNNER_TRACE"))
         self.n = self.k = 0
+        self._native_args = None  # set by prepare(): the arguments of the one-call step
         self._ex_events = []  # (start, end) torch events around exchange + merge, last 16 steps
         self._agree("local segments per rank", self.n_local)
 
@@ -236,6 +239,13 @@ class ShardRunner:
         self._zero_copy = os.environ.get("TQ_RUNNER_D2H_COPY", "0") != "1"
         self.host = list(views(self._host_all))
         self.merged = tuple(self.host) if self._zero_copy else views(self._merged_all)
+        # one rank, no forced exchange: the step is one native call; its arguments are built here, once per shape
+        self._native_args = None
+        # (TQ_RUNNER_ONE_CALL=0: the step as separate calls — collects, events, merge_top_k — for A/B runs)
+        if W == 1 and not self.force_exchange and os.environ.get("TQ_RUNNER_ONE_CALL", "1") != "0":
+            slabs = [t.data_ptr() for t in self.local] if S > 1 else [None, None, None]
+            self._native_args = (self.dev._s, int(k)) + tuple(t.data_ptr() for t in self.merged) + tuple(slabs) + \
+                (C.c_void_p(self.stream),)
 
     def prepare_next(self, queries, k, marshalled):
         """Query::weight of the NEXT batch on a helper thread while this thread enqueues the current one (same number
@@ -248,6 +258,16 @@ class ShardRunner:
         return self.dev.commit_next()
 
     def enqueue(self):
+        if self._native_args is not None:
+            t0 = time.perf_counter() if self._trace else 0.0
+            B._check(B.lib().tqh_search_prepared_device(*self._native_args), host=True)
+            if not self._zero_copy:
+                B._check(B.lib().tq_copy_to_host_async(
+                    self.dev.ctx, int(self.device), self._host_all.data_ptr(), self._merged_all.data_ptr(),
+                    self._merged_all.numel() * 4, C.c_void_p(self.stream)))
+            if self._trace and time.perf_counter() - t0 > 0.003:
+                print("[runner] native step %.2f ms" % ((time.perf_counter() - t0) * 1e3), file=sys.stderr)
+            return
         torch = self.torch
         n, k, S, W = self.n, self.k, self.n_local, self.world
         sc, dc, ct = self.local
@@ -309,7 +329,11 @@ class ShardRunner:
         return out
 
     def exchange_ms(self):
-        """Mean GPU time of [all-gather + merge_top_k] over the last (<= 16) finished steps."""
+        """Mean GPU time of [all-gather + merge_top_k] over the last (<= 16) finished steps; 0.0 when neither ran
+        (one rank holding the index's one segment)."""
+        if self._native_args is not None:
+            self.stream_obj.synchronize()
+            return self.dev.exchange_ms()
         if not self._ex_events:
             return 0.0
         self.stream_obj.synchronize()

@@ -14,6 +14,8 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "searcher.hpp"
 #include "term_info_store.hpp"
 
@@ -47,6 +49,18 @@ struct tqh_searcher {
   std::unique_ptr<Searcher> searcher;
   std::vector<Weight> prepared;  // weights of the last tqh_prepare_batch
   std::vector<Weight> prepared_next;  // ... of the last tqh_prepare_batch_next: the batch AFTER the one being executed
+  // tqh_search_prepared_device with several segments: HIP events around its merge_top_k launch, the last 16 steps
+  // (created with the first such step, on the segments' device)
+  int device = 0;          // the device of the segments; one_device: they all share it
+  bool one_device = true;
+  static constexpr uint32_t kExRing = 16;
+  hipEvent_t ex_ev[kExRing][2] = {};
+  uint32_t ex_at = 0, ex_n = 0;
+  ~tqh_searcher() {
+    for (auto &pair : ex_ev)
+      for (hipEvent_t e : pair)
+        if (e) (void)hipEventDestroy(e);
+  }
 };
 
 extern "C" {
@@ -136,6 +150,8 @@ int tqh_searcher_add_segment(tqh_searcher *s, int device, uint32_t max_doc, uint
       for (uint32_t i = 0; i < n_terms; ++i) by_df.emplace_back(terms[i].doc_freq, terms[i].postings_start);
       reserve_densest_columns(*seg, by_df);
     }
+    s->one_device = s->segments.empty() || (s->one_device && s->device == device);
+    s->device = device;
     s->segments.push_back(seg);
     s->searcher.reset(new Searcher(s->segments));
   });
@@ -156,6 +172,8 @@ int tqh_searcher_add_segment_with_store(tqh_searcher *s, int device, uint32_t ma
                                                fieldnorm, fn_len);
     seg->set_term_info_store(st);
     reserve_densest_columns(*seg, *st);
+    s->one_device = s->segments.empty() || (s->one_device && s->device == device);
+    s->device = device;
     s->segments.push_back(seg);
     s->searcher.reset(new Searcher(s->segments));
   });
@@ -177,6 +195,8 @@ int tqh_searcher_add_segment_device_with_store(tqh_searcher *s, int device, uint
                                                total_num_tokens);
     seg->set_term_info_store(st);
     reserve_densest_columns(*seg, *st);
+    s->one_device = s->segments.empty() || (s->one_device && s->device == device);
+    s->device = device;
     s->segments.push_back(seg);
     s->searcher.reset(new Searcher(s->segments));
   });
@@ -499,6 +519,65 @@ int tqh_collect_segment_prepared_device(tqh_searcher *s, uint32_t segment_ord, u
       throw TantivyError(TantivyError::InvalidArgument, "bad segment");
     s->searcher->collect_segment_batch_device(segment_ord, s->prepared, k, d_scores, d_docs,
                                               d_counts, hip_stream);
+  });
+}
+
+// Searcher::search of the prepared batch with TopDocs::with_limit(k) on the device, as ONE call that never waits for the
+// GPU (searcher.rs:180-238: collect_segment per segment, then merge_fruits): everything is enqueued on hip_stream.
+// Outputs [n][k] / [n]: device memory, or pinned host memory mapped into the device.
+// One segment: its merge kernels write the four arrays themselves (tq_search_batch_device_rows), the slabs are not
+// touched and may be null.  Several: every segment collects into its [n][k] part of the slabs ([S][n][k] x 2, [S][n],
+// device memory), one tq_merge_topk_device launch follows, HIP events around it (tqh_exchange_ms).
+int tqh_search_prepared_device(tqh_searcher *s, uint32_t k, float *out_scores, uint32_t *out_segment_ords,
+                               uint32_t *out_docs, uint32_t *out_counts, float *d_slab_scores,
+                               uint32_t *d_slab_docs, uint32_t *d_slab_counts, void *hip_stream) {
+  return guard([&] {
+    if (!s || !s->searcher || s->segments.empty()) throw TantivyError(TantivyError::InvalidArgument, "no segments");
+    if (!out_scores || !out_segment_ords || !out_docs || !out_counts || !k)
+      throw TantivyError(TantivyError::InvalidArgument, "null argument");
+    const size_t S = s->segments.size(), n = s->prepared.size();
+    if (n == 0) return;
+    if (S == 1) {
+      s->searcher->collect_segment_batch_device(0, s->prepared, k, out_scores, out_docs, out_counts, hip_stream,
+                                                out_segment_ords);
+      return;
+    }
+    if (!d_slab_scores || !d_slab_docs || !d_slab_counts)
+      throw TantivyError(TantivyError::InvalidArgument, "several segments need the slabs");
+    if (!s->one_device) throw TantivyError(TantivyError::Unsupported, "tqh_search_prepared_device: the segments sit on several devices");
+    for (size_t sg = 0; sg < S; ++sg)
+      s->searcher->collect_segment_batch_device(sg, s->prepared, k, d_slab_scores + sg * n * k, d_slab_docs + sg * n * k,
+                                                d_slab_counts + sg * n, hip_stream);
+    auto hip = [](hipError_t e) {
+      if (e != hipSuccess) throw TantivyError(TantivyError::SystemError, hipGetErrorString(e));
+    };
+    hipEvent_t *ev = s->ex_ev[s->ex_at % tqh_searcher::kExRing];  // (the collects left the segments' device current)
+    for (int i = 0; i < 2; ++i)
+      if (!ev[i]) hip(hipEventCreate(&ev[i]));
+    hip(hipEventRecord(ev[0], (hipStream_t)hip_stream));
+    const int rc = tq_merge_topk_device(s->ctx, s->device, d_slab_scores, d_slab_docs, d_slab_counts, nullptr, (uint32_t)S,
+                                        (uint32_t)n, k, 0, k, out_scores, out_segment_ords, out_docs, out_counts, hip_stream);
+    if (rc != TQ_OK) throw TantivyError(TantivyError::SystemError, tq_last_error());
+    hip(hipEventRecord(ev[1], (hipStream_t)hip_stream));
+    ++s->ex_at;
+    s->ex_n = std::min(s->ex_n + 1u, tqh_searcher::kExRing);
+  });
+}
+// Mean GPU time of the merge_top_k launches of the last (<= 16) tqh_search_prepared_device calls since the last
+// tqh_exchange_ms (waits for them); 0.0 when none ran — one segment merges nothing.
+int tqh_exchange_ms(tqh_searcher *s, float *ms) {
+  return guard([&] {
+    if (!s || !ms) throw TantivyError(TantivyError::InvalidArgument, "null argument");
+    double sum = 0.0;
+    for (uint32_t i = 0; i < s->ex_n; ++i) {
+      hipEvent_t *ev = s->ex_ev[(s->ex_at - 1u - i) % tqh_searcher::kExRing];
+      float one = 0.0f;
+      if (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&one, ev[0], ev[1]) != hipSuccess)
+        throw TantivyError(TantivyError::SystemError, "tqh_exchange_ms: the events of a merge launch cannot be read");
+      sum += one;
+    }
+    *ms = s->ex_n ? (float)(sum / s->ex_n) : 0.0f;
+    s->ex_n = 0;
   });
 }
 

@@ -98,6 +98,12 @@ tq_term_handle SegmentReader::term_handle(uint32_t term_id) {
   return handle;
 }
 
+bool SegmentReader::handle_known(uint32_t term_id) const {
+  if (term_id >= kFastHandles) return false;
+  std::atomic<tq_term_handle> *fast = fast_handles_.load(std::memory_order_acquire);
+  return fast && fast[term_id].load(std::memory_order_acquire) != kHandleUnknown;
+}
+
 void SegmentReader::prepare_terms(const uint32_t *term_ids, size_t n) {
   // the ones without a handle yet, each once
   std::vector<uint32_t> fresh;
@@ -173,10 +179,6 @@ tq_term_handle resolve_handle(const std::shared_ptr<SegmentReader> &seg, const W
   return seg->term_handle(t);
 }
 }  // namespace
-
-Searcher::Searcher(std::vector<std::shared_ptr<SegmentReader>> segments)
-    : segments_(std::move(segments)) {}
-Searcher::~Searcher() { delete[] fast_weights_.load(std::memory_order_relaxed); }
 
 void Searcher::add_remote_statistics(
     uint64_t max_doc, uint64_t total_num_tokens,
@@ -533,20 +535,23 @@ namespace {
 struct SegmentBatch {
   std::vector<tq_query> qs;
   std::vector<tq_term_handle> handles;
-  SegmentBatch(const std::shared_ptr<SegmentReader> &seg_p, const std::vector<Weight> &weights, uint32_t k) {
+  SegmentBatch() = default;
+  SegmentBatch(const std::shared_ptr<SegmentReader> &seg_p, const std::vector<Weight> &weights, uint32_t k) { fill(seg_p, weights, k); }
+  // (every field of every record is written: an object that is filled again keeps its memory, nothing of its contents)
+  void fill(const std::shared_ptr<SegmentReader> &seg_p, const std::vector<Weight> &weights, uint32_t k) {
     SegmentReader &seg = *seg_p;
     const size_t n = weights.size();
     qs.resize(n);
     size_t total_terms = 0;
     for (auto &w : weights) total_terms += w.terms.size();
+    handles.clear();
     handles.reserve(total_terms);
     if (n > 1) {  // the batch's new terms are prepared together before any handle is asked for
-      std::vector<uint32_t> all;
-      all.reserve(total_terms);
+      std::vector<uint32_t> fresh;  // (a replayed or a warm batch has none: no list of 20 000 terms is built to find that out)
       for (auto &w : weights)
         for (uint32_t t : w.terms)
-          if (t < kTermSetBase) all.push_back(t);  // (a set prepares its members itself; TQ_TERM_ALL names no list)
-      seg.prepare_terms(all.data(), all.size());
+          if (t < kTermSetBase && !seg.handle_known(t)) fresh.push_back(t);  // (a set prepares its members itself; TQ_TERM_ALL names no list)
+      if (!fresh.empty()) seg.prepare_terms(fresh.data(), fresh.size());
     }
     for (size_t i = 0; i < n; ++i) {
       const Weight &w = weights[i];
@@ -570,6 +575,17 @@ struct SegmentBatch {
   }
 };
 }  // namespace
+
+// The records of collect_segment_batch_device's last batch: built anew by every call, in the same memory (a batch of
+// 10 000 queries is a megabyte of tq_query records: a fresh vector was an mmap, 250 page faults and a munmap per step)
+struct Searcher::DeviceBatch {
+  std::mutex m;
+  SegmentBatch b;
+};
+
+Searcher::Searcher(std::vector<std::shared_ptr<SegmentReader>> segments)
+    : segments_(std::move(segments)), device_batch_(new DeviceBatch()) {}
+Searcher::~Searcher() { delete[] fast_weights_.load(std::memory_order_relaxed); }
 
 uint32_t Searcher::bound_slack_ppm(const SegmentReader &seg) const {
   const double global = (double)total_num_tokens() / (double)total_num_docs();
@@ -657,12 +673,17 @@ std::vector<std::vector<std::pair<DocAddress, Score>>> Searcher::docset_scored_b
 
 void Searcher::collect_segment_batch_device(size_t segment_ord, const std::vector<Weight> &weights,
                                             uint32_t k, float *d_scores, uint32_t *d_docs,
-                                            uint32_t *d_counts, void *hip_stream) {
+                                            uint32_t *d_counts, void *hip_stream, uint32_t *d_segment_ords) {
   SegmentReader &seg = *segments_[segment_ord];
-  SegmentBatch b(segments_[segment_ord], weights, k);
+  std::lock_guard<std::mutex> lk(device_batch_->m);  // (the call below only enqueues; calls on one segment are serial anyway)
+  SegmentBatch &b = device_batch_->b;
+  b.fill(segments_[segment_ord], weights, k);
   const tq_search_opts opts{-1, bound_slack_ppm(seg)};
-  const int rc = tq_search_batch_device_opts(seg.raw(), b.qs.data(), (uint32_t)weights.size(), k,
-                                             d_scores, d_docs, d_counts, &opts, hip_stream);
+  const int rc = d_segment_ords
+                     ? tq_search_batch_device_rows(seg.raw(), b.qs.data(), (uint32_t)weights.size(), k, d_scores,
+                                                   d_segment_ords, d_docs, d_counts, (uint32_t)segment_ord, &opts, hip_stream)
+                     : tq_search_batch_device_opts(seg.raw(), b.qs.data(), (uint32_t)weights.size(), k,
+                                                   d_scores, d_docs, d_counts, &opts, hip_stream);
   if (rc != TQ_OK) throw_tq(rc);
 }
 

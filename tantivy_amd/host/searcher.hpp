@@ -71,6 +71,8 @@ class SegmentReader {
   // the terms of a batch that no query has named yet, prepared TOGETHER (tq_term_prepare_batch: one staged upload,
   // one signature launch) — term_handle then finds every one of them
   void prepare_terms(const uint32_t *term_ids, size_t n);
+  // term_handle(term_id) would answer from the lock-free table: the term was prepared, or found absent, before
+  bool handle_known(uint32_t term_id) const;
   uint32_t max_doc() const { return max_doc_; }
   uint32_t segment_ord() const { return segment_ord_; }
   uint64_t total_num_tokens() const { return total_num_tokens_; }  // inverted_index_reader.rs:72-73
@@ -374,10 +376,12 @@ class Searcher {
                              std::vector<float> &scores, std::vector<uint32_t> &docs,
                              std::vector<uint32_t> &counts);
   // same, results left in device memory (enqueued on hip_stream, no host sync): feeds the
-  // cross-rank all-gather of the one-segment-per-GPU deployment
+  // cross-rank all-gather of the one-segment-per-GPU deployment.
+  // d_segment_ords (an index of this ONE segment, rows of stride k): the rows are merge_fruits' already and get its
+  // column of segment ordinals (tq_search_batch_device_rows) — no merge launch follows
   void collect_segment_batch_device(size_t segment_ord, const std::vector<Weight> &weights,
                                     uint32_t k, float *d_scores, uint32_t *d_docs,
-                                    uint32_t *d_counts, void *hip_stream);
+                                    uint32_t *d_counts, void *hip_stream, uint32_t *d_segment_ords = nullptr);
 
  private:
   // block-max metadata was selected under the segment's own average fieldnorm; with global
@@ -385,6 +389,8 @@ class Searcher {
   // passed with every call (tq_search_opts)
   uint32_t bound_slack_ppm(const SegmentReader &seg) const;
   std::vector<std::shared_ptr<SegmentReader>> segments_;
+  struct DeviceBatch;  // collect_segment_batch_device's tq_query records (searcher.cpp)
+  std::unique_ptr<DeviceBatch> device_batch_;
   mutable std::mutex cache_m_;
   mutable std::shared_ptr<Bm25Weight> shared_cache_;  // one tf cache per field (avg fieldnorm)
   // idf * (1 + K1) of small term ids as float bits (0xFFFFFFFF = not computed yet), read without a lock; dropped
