@@ -183,6 +183,67 @@ int tq_segment_upload_device(tq_ctx *ctx, int device, uint32_t max_doc, const ui
                              tq_segment **out);
 void tq_segment_free(tq_segment *seg);
 
+/* ---- multi-field segments ----
+ * replaces: one SegmentReader::inverted_index(field) + fieldnorms_readers().get_field(field) per indexed Field of a
+ * query (src/index/segment_reader.rs:221-283, src/query/term_query/term_weight.rs:196-219): F >= 1 fields over ONE
+ * doc-id space, queries whose terms come from any of them — what QueryParser makes of `hello world` over the default
+ * fields [title, body]: (title:hello body:hello) (title:world body:world).  Every term scores with its OWN field's
+ * fieldnorm and its own field's Bm25Weight cache.
+ * fields[f] = the sub-files of field f, with the meaning of tq_segment_upload's arguments (fieldnorm NULL: that
+ * field reads FieldNormReader::constant(max_doc, 1)); all fields share one record_option (the skip-entry size depends
+ * on it; per-field options are not taken).  1 <= n_fields <= TQ_MAX_FIELDS, else TQ_ERR_INVALID; n_fields == 1 is
+ * tq_segment_upload.  There is no device-resident variant.
+ * Layout: the fields' .idx sub-files are laid end to end (each with its 8-byte header and its padding) in one device
+ * buffer, the .pos sub-files in another; a term's offsets are shifted by its field's base when it is prepared, and
+ * every decode path reads the shifted offsets unchanged.  Field 0's fieldnorms lie where a single-field segment's do;
+ * fields 1.. add max_doc bytes each (tq_fields_stats.extra_fieldnorm_bytes).
+ * FIELD 0 IS THE PRIMARY FIELD: the doc matrix's fieldnorm byte, the lists' range maxima / list maxima / leader
+ * norms, the segment's own Bm25Weight cache, and with them the shared and the pruned kernels, are field 0's.  A
+ * query that names only field-0 terms runs exactly as on a single-field upload of field 0: same kernels, same rows.
+ * Lists of a field != 0 get bitmaps, tf bytes, position directories, doc-matrix columns / signature bits and range
+ * directories like any list (membership and tf only) and none of the norm-derived tables.
+ * Queries on a segment with F > 1: tq_query.tf_cache points at F x 256 floats, row f = Bm25Weight.cache under field
+ * f's average fieldnorm; weights stay per term (idf from that field's statistics, Bm25Weight::for_terms per
+ * TermQuery).  F == 1: nothing changes.
+ *   tq_count_batch, tq_docset_batch*   bitmap words and positions only: any field mix, "docset_trees" shapes included
+ *   tq_search_batch*, tq_submit / tq_search_one
+ *                             a query naming at least one term of a field != 0 runs as TQ_KERNEL_TREE whatever its mode
+ *                             (tree_fields_kernel, tq_tree_fields.hip: per-LIST norms), occurs on call scratch as for
+ *                             term sets; nothing is pruned, "exhaustive" 0 and 1 give the same rows and
+ *                             tq_last_batch_match_counts is the doc-set size; refusals as for any tree ("use_dense" off,
+ *                             tables outside one 32 GB span, a negative weight: TQ_ERR_UNSUPPORTED).  TQ_MODE_AND / OR /
+ *                             BOOL with clause_of unions, nested shapes, phrase atoms (scored with the norm of their
+ *                             terms' field), term sets beside them; a TQ_MODE_PHRASE query of one field f != 0 runs as
+ *                             a one-atom tree.  A phrase or phrase atom whose terms are of DIFFERENT fields:
+ *                             TQ_ERR_INVALID naming the query (the reference's PhraseQuery panics on it).  A term set
+ *                             with members of different fields is fine: a bitmap and a constant.  TQ_TERM_ALL beside
+ *                             field terms is taken where it is taken today with ONE exception: a Should term of a
+ *                             field != 0 in a query that its All clauses make ALL-BASED (such a query keeps Should and
+ *                             MustNot lists only: its Should terms are what scores) is TQ_ERR_UNSUPPORTED (all_kernel scores under the primary field's norms; MustNot terms of
+ *                             any field are taken: bits only; EMPTY / PLAIN forms run as the stripped query does).
+ *   tq_docset_scored_batch*   flat shapes take any field mix (docset_score_fields_kernel, tq_docset_score_fields.hip: per-list
+ *                             norms, the same sums).  Under "docset_score_trees", a phrase or a nested query that names a
+ *                             term of a field != 0: TQ_ERR_UNSUPPORTED naming the query in this version, nothing launched
+ *                             (the parser's shape is flat and is taken).
+ * tq_segment_reserve_columns names field-0 lists. */
+#define TQ_MAX_FIELDS 8u
+typedef struct tq_field_files {
+  const uint8_t *idx;
+  size_t idx_len;
+  const uint8_t *pos; /* NULL: no positions */
+  size_t pos_len;
+  const uint8_t *fieldnorm; /* NULL: FieldNormReader::constant(max_doc, 1) */
+  size_t fn_len;
+} tq_field_files;
+int tq_segment_upload_fields(tq_ctx *ctx, int device, uint32_t max_doc, uint32_t n_fields,
+                             const tq_field_files *fields, uint8_t record_option, tq_segment **out);
+typedef struct tq_fields_stats {
+  uint32_t n_fields;
+  uint32_t n_field_terms;            /* prepared terms of fields != 0 (0: no entry point looks at a query's fields) */
+  uint64_t extra_fieldnorm_bytes;    /* fieldnorm bytes of fields 1.. (field 0's: tq_segment_stats.fieldnorm_bytes) */
+} tq_fields_stats;
+int tq_segment_get_fields_stats(tq_segment *seg, tq_fields_stats *out);
+
 /* replaces: InvertedIndexReader::read_postings_from_terminfo + BlockSegmentPostings::open +
  * SkipReader::new + PositionReader::open (inverted_index_reader.rs:204-247,
  * block_segment_postings.rs:97-140, skip.rs:131-151, positions/reader.rs:43-56).
@@ -205,6 +266,17 @@ typedef struct tq_term_info {
   uint32_t pad_;
 } tq_term_info;
 int tq_term_prepare_batch(tq_segment *seg, const tq_term_info *infos, uint32_t n, tq_term_handle *out);
+/* The same for a term of field `field` of a multi-field segment (tq_segment_upload_fields): the offsets are relative
+ * to THAT field's sub-file bodies, the library adds the field's base.  tq_term_prepare / tq_term_prepare_batch mean
+ * field 0.  Idempotent per (field, postings_off): the same postings_off in two fields gives two handles.
+ * field >= the segment's field count: TQ_ERR_INVALID.  fields = n bytes, one per info. */
+int tq_term_prepare_field(tq_segment *seg, uint32_t field, uint64_t postings_off, uint32_t postings_len,
+                          uint64_t positions_off, uint32_t positions_len, uint32_t doc_freq,
+                          tq_term_handle *out);
+int tq_term_prepare_batch_fields(tq_segment *seg, const tq_term_info *infos, const uint8_t *fields, uint32_t n,
+                                 tq_term_handle *out);
+/* *field = the field the handle's list belongs to (a term set: 0). */
+int tq_term_field(tq_segment *seg, tq_term_handle term, uint32_t *field);
 /* Optional, before the first tq_term_prepare: names the posting lists (by postings_off) that get
  * the 40 columns of the segment's doc matrix — the caller knows every term's doc_freq from the
  * term dictionary and passes the densest lists.  Without it the columns go to the first 40 dense

@@ -77,11 +77,24 @@ int tqh_searcher_add_segment(tqh_searcher *s, int device, uint32_t max_doc, uint
                              const uint8_t *idx, size_t idx_len, const uint8_t *pos,
                              size_t pos_len, const uint8_t *fieldnorm, size_t fn_len,
                              const tqh_term_info *terms, uint32_t n_terms);
+/* SegmentReader for n_fields fields of one segment over one doc-id space (tq_segment_upload_fields in tantivy_amd.h:
+ * fields[f] = field f's sub-files, one record_option for all; field 0 is the primary field).  term_fields[i] = the
+ * field of terms[i] (NULL: all of field 0); term ids share ONE uint32_t space over the fields, a term id belongs to one
+ * field.  Queries name term ids as on a single-field segment: every term scores with its own field's fieldnorms and
+ * the Bm25Weight cache under its own field's average fieldnorm (idf from its own doc_freq), a query that names a term
+ * of a field != 0 runs as TQ_KERNEL_TREE, and a phrase over terms of different fields is TQ_ERR_INVALID (the
+ * reference's PhraseQuery panics on it). */
+int tqh_searcher_add_segment_fields(tqh_searcher *s, int device, uint32_t max_doc, uint8_t record_option,
+                                    uint32_t n_fields, const tq_field_files *fields, const tqh_term_info *terms,
+                                    const uint8_t *term_fields, uint32_t n_terms);
 /* Bm25StatisticsProvider input for segments held by other ranks (src/query/bm25.rs:11-50):
  * their max_doc, total_num_tokens and per-term doc_freq are added to the local sums. */
 int tqh_searcher_add_remote_stats(tqh_searcher *s, uint64_t max_doc, uint64_t total_num_tokens,
                                   const uint32_t *term_ids, const uint32_t *doc_freqs,
                                   uint32_t n_terms);
+/* ... of multi-field segments: tokens[f] = their total_num_tokens of field f (the call above means field 0). */
+int tqh_searcher_add_remote_stats_fields(tqh_searcher *s, uint64_t max_doc, const uint64_t *tokens, uint32_t n_fields,
+                                         const uint32_t *term_ids, const uint32_t *doc_freqs, uint32_t n_terms);
 /* Query::weight for every query of a batch (global BM25 statistics + executor choice). */
 int tqh_prepare_batch(tqh_searcher *s, const tqh_query *queries, uint32_t n);
 /* Query::weight of the NEXT batch while the current one executes on another thread (a second slot; thread-safe next to
@@ -142,7 +155,10 @@ int tqh_search_prepared_device(tqh_searcher *s, uint32_t k, float *out_scores, u
 /* *ms = mean GPU time of the merge_top_k launches of the last (<= 16) tqh_search_prepared_device calls since the
  * previous tqh_exchange_ms (waits for them to finish); 0.0 when none ran, as with one segment. */
 int tqh_exchange_ms(tqh_searcher *s, float *ms);
-/* Bm25Weight::for_terms(...).boost_by(boost): weight + 256-entry tf cache. */
+/* Bm25Weight::for_terms(...).boost_by(boost): weight + 256-entry tf cache — of ONE field: the statistics passed in are
+ * that field's (total_num_tokens of the field).  It knows no Searcher.  A caller that builds raw tq_query records
+ * against a multi-field segment calls it once per field with that field's token count and lays the F caches end to
+ * end (tq_query.tf_cache = F x 256 floats, row f = field f); one 256-float cache there is too short. */
 int tqh_bm25_for_terms(const uint64_t *term_doc_freqs, uint32_t n_terms, uint64_t total_num_docs,
                        uint64_t total_num_tokens, float boost, float *weight_out,
                        float *cache_out);

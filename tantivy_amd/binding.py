@@ -91,6 +91,18 @@ class TqTermInfo(C.Structure):  # tq_term_info: the fields of a TermInfo as tq_t
                 ("positions_len", C.c_uint32), ("doc_freq", C.c_uint32), ("pad_", C.c_uint32)]
 
 
+class TqFieldFiles(C.Structure):  # tq_field_files: one field's sub-files of a multi-field segment
+    _fields_ = [("idx", C.c_void_p), ("idx_len", C.c_size_t), ("pos", C.c_void_p), ("pos_len", C.c_size_t),
+                ("fieldnorm", C.c_void_p), ("fn_len", C.c_size_t)]
+
+
+class TqFieldsStats(C.Structure):  # tq_fields_stats
+    _fields_ = [("n_fields", C.c_uint32), ("n_field_terms", C.c_uint32), ("extra_fieldnorm_bytes", C.c_uint64)]
+
+
+MAX_FIELDS = 8  # TQ_MAX_FIELDS
+
+
 class TqhTermInfo(C.Structure):
     _fields_ = [("term_id", C.c_uint32), ("doc_freq", C.c_uint32), ("postings_start", C.c_uint64),
                 ("postings_end", C.c_uint64), ("positions_start", C.c_uint64),
@@ -138,6 +150,8 @@ EXPORTS = [
     "tq_docset_scored_batch", "tq_docset_scored_batch_device", "tqh_docset_scored_prepared",
     "tq_all_query_form",
     "tq_term_set_prepare", "tq_term_set_info", "tq_term_set_release",
+    "tq_segment_upload_fields", "tq_segment_get_fields_stats", "tq_term_prepare_field", "tq_term_prepare_batch_fields",
+    "tq_term_field", "tqh_searcher_add_segment_fields", "tqh_searcher_add_remote_stats_fields",
 ]
 
 
@@ -198,6 +212,14 @@ def lib():
     L.tq_term_set_prepare.argtypes = [vp, u32p, C.c_uint32, u32p]
     L.tq_term_set_info.argtypes = [vp, C.c_uint32, u32p, C.POINTER(C.c_uint64)]
     L.tq_term_set_release.argtypes = [vp, C.c_uint32]
+    L.tq_segment_upload_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TqFieldFiles), C.c_uint8, C.POINTER(vp)]
+    L.tq_segment_get_fields_stats.argtypes = [vp, C.POINTER(TqFieldsStats)]
+    L.tq_term_prepare_field.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
+    L.tq_term_prepare_batch_fields.argtypes = [vp, C.POINTER(TqTermInfo), u8p, C.c_uint32, u32p]
+    L.tq_term_field.argtypes = [vp, C.c_uint32, u32p]
+    L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
+                                                  C.POINTER(TqhTermInfo), u8p, C.c_uint32]
+    L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
     u64p = C.POINTER(C.c_uint64)
     L.tq_encoder_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.tq_encoder_free.argtypes = [vp]
@@ -279,7 +301,8 @@ def _u32(a):
 
 
 def bm25_for_terms(doc_freqs, total_num_docs, total_num_tokens, boost=1.0):
-    """Product-side Bm25Weight::for_terms: returns (weight, cache[256])."""
+    """Product-side Bm25Weight::for_terms: returns (weight, cache[256]) of ONE field's statistics; the tf_cache of a
+    multi-field segment is np.stack of one such cache per field (total_num_tokens = that field's)."""
     dfs = (C.c_uint64 * len(doc_freqs))(*[int(d) for d in doc_freqs])
     w = C.c_float()
     cache = np.zeros(256, np.float32)
@@ -487,6 +510,54 @@ class DeviceIndex:
             pos.size if pos is not None else 0, fn.ctypes.data if fn is not None else None,
             fn.size if fn is not None else 0, tis, n), host=True)
         self.n_segments += 1
+
+    def add_segment_fields(self, fields, device=0):
+        """One segment of several fields over one doc-id space (tq_segment_upload_fields).  fields: a list of objects
+        shaped like add_segment's segment objects (idx with its header, pos, fieldnorm or None, terms), one per field,
+        sharing max_doc and record_option; fields[0] is the primary field.  TERM IDS ARE ASSIGNED FIELD BY FIELD IN
+        ORDER: field 0's terms get 0 .. len(fields[0].terms) - 1, field 1's the next len(fields[1].terms), and so on
+        (field_term_base(fields, f) + the term's index in fields[f].terms).  Queries name these ids as on a single-field
+        segment; every term scores under its own field's fieldnorms and average fieldnorm.  -> the term-id base of
+        every field."""
+        L = lib()
+        if not 1 <= len(fields) <= MAX_FIELDS:
+            raise TantivyAmdError(1, "add_segment_fields: %d fields, 1..%d are taken" % (len(fields), MAX_FIELDS))
+        if any(f.max_doc != fields[0].max_doc or f.record_option != fields[0].record_option for f in fields):
+            raise TantivyAmdError(1, "add_segment_fields: the fields of a segment share max_doc and record_option")
+        ff = (TqFieldFiles * len(fields))()
+        keep, tis_list, tfs, bases = [], [], [], []
+        for f, seg in enumerate(fields):
+            idx = np.ascontiguousarray(seg.idx[: seg.idx_len] if hasattr(seg, "idx_len") else seg.idx, dtype=np.uint8)
+            pos_len = getattr(seg, "pos_len", len(seg.pos) if seg.pos is not None else 0)
+            pos = np.ascontiguousarray(seg.pos[:pos_len], dtype=np.uint8) if pos_len else None
+            fn = None if seg.fieldnorm is None else np.ascontiguousarray(seg.fieldnorm, dtype=np.uint8)
+            keep += [idx, pos, fn]
+            ff[f] = TqFieldFiles(idx.ctypes.data, idx.size, pos.ctypes.data if pos is not None else None,
+                                 pos.size if pos is not None else 0, fn.ctypes.data if fn is not None else None,
+                                 fn.size if fn is not None else 0)
+            bases.append(len(tis_list))
+            for t in seg.terms:
+                if isinstance(t, (tuple, list)):
+                    df, ps, pe, qs, qe = t
+                else:
+                    df, ps, pe, qs, qe = (t.doc_freq, t.postings_start, t.postings_end, t.positions_start, t.positions_end)
+                tis_list.append(TqhTermInfo(len(tis_list), int(df), int(ps), int(pe), int(qs), int(qe)))
+                tfs.append(f)
+        n = len(tis_list)
+        tis = (TqhTermInfo * max(1, n))(*tis_list)
+        tfa = (C.c_uint8 * max(1, n))(*tfs)
+        _check(L.tqh_searcher_add_segment_fields(self._s, int(device), int(fields[0].max_doc), int(fields[0].record_option),
+                                                 len(fields), ff, tis, tfa, n), host=True)
+        self.n_segments += 1
+        return bases
+
+    def add_remote_stats_fields(self, max_doc, total_num_tokens_per_field, doc_freqs):
+        """add_remote_stats for multi-field segments: one token count per field; doc_freqs indexed by term id."""
+        toks = (C.c_uint64 * len(total_num_tokens_per_field))(*[int(t) for t in total_num_tokens_per_field])
+        ids = np.arange(len(doc_freqs), dtype=np.uint32)
+        dfs = np.ascontiguousarray(doc_freqs, dtype=np.uint32)
+        _check(lib().tqh_searcher_add_remote_stats_fields(self._s, int(max_doc), toks, len(total_num_tokens_per_field),
+                                                          _u32(ids), _u32(dfs), len(dfs)), host=True)
 
     def add_segment_device(self, max_doc, record_option, d_idx, d_pos, d_fieldnorm,
                            total_num_tokens, term_info_store, device=0):
@@ -798,6 +869,19 @@ class DeviceIndex:
             return TERM_ALL
         return lib().tqh_term_handle(self._s, segment_ord, int(term_id))
 
+    def term_field(self, handle, segment_ord=0):
+        """tq_term_field: the field of a multi-field segment the HANDLE's list belongs to (0: the primary field)."""
+        f = C.c_uint32()
+        _check(lib().tq_term_field(self.segment_raw(segment_ord), int(handle), C.byref(f)))
+        return int(f.value)
+
+    def fields_stats(self, segment_ord=0):
+        """tq_segment_get_fields_stats -> {n_fields, n_field_terms, extra_fieldnorm_bytes}."""
+        st = TqFieldsStats()
+        _check(lib().tq_segment_get_fields_stats(self.segment_raw(segment_ord), C.byref(st)))
+        return {"n_fields": int(st.n_fields), "n_field_terms": int(st.n_field_terms),
+                "extra_fieldnorm_bytes": int(st.extra_fieldnorm_bytes)}
+
     def term_set_prepare(self, term_ids, segment_ord=0):
         """tq_term_set_prepare on one segment: the OR of the docs of the terms `term_ids` (ids of the term dictionary, or
         RawHandles / TERM_ABSENT as they are) as a const-scoring list -> RawHandle, which every raw_* helper takes in its
@@ -949,7 +1033,7 @@ class DeviceIndex:
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =
-        np.float32[256] (or None), or a list of one per query (the same object = the same pointer; None: left NULL).
+        np.float32[256] (a multi-field segment: np.float32[F, 256], row f = field f's cache; or None), or a list of one per query (the same object = the same pointer; None: left NULL).
         -> (array, keep-alive list)"""
         qs, keep = self._raw_flat_queries(queries, segment_ord)
         per_query = None

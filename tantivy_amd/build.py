@@ -14,6 +14,7 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_ashare.hip"),
     os.path.join(HERE, "csrc", "tq_count.hip"),
     os.path.join(HERE, "csrc", "tq_tree.hip"),
+    os.path.join(HERE, "csrc", "tq_tree_fields.hip"),
     os.path.join(HERE, "csrc", "tq_all.hip"),
     os.path.join(HERE, "csrc", "tq_all.cpp"),
     os.path.join(HERE, "csrc", "tq_count.cpp"),
@@ -22,6 +23,7 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_docset.hip"),
     os.path.join(HERE, "csrc", "tq_docset.cpp"),
     os.path.join(HERE, "csrc", "tq_docset_score.hip"),
+    os.path.join(HERE, "csrc", "tq_docset_score_fields.hip"),
     os.path.join(HERE, "csrc", "tq_docset_tree.hip"),
     os.path.join(HERE, "csrc", "tq_docset_tree_score.hip"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
@@ -31,6 +33,7 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_prepare.hip"),
     os.path.join(HERE, "csrc", "tq_api.cpp"),
     os.path.join(HERE, "csrc", "tq_terms.cpp"),
+    os.path.join(HERE, "csrc", "tq_fields.cpp"),
     os.path.join(HERE, "csrc", "tq_term_walk.cpp"),
     os.path.join(HERE, "csrc", "tq_term_arena.cpp"),
     os.path.join(HERE, "csrc", "tq_term_tables.cpp"),
@@ -49,6 +52,7 @@ HEADERS = [
     os.path.join(HERE, "csrc", "tq_common.hpp"),
     os.path.join(HERE, "csrc", "tq_device.h"),
     os.path.join(HERE, "csrc", "tq_launch.h"),
+    os.path.join(HERE, "csrc", "tq_fields.h"),
     os.path.join(HERE, "csrc", "tq_prepare.h"),
     os.path.join(HERE, "csrc", "tq_internal.hpp"),
     os.path.join(HERE, "host", "searcher.hpp"),
@@ -78,7 +82,7 @@ def csrc_hash():
 
 # which translation unit a scan kernel of a rocprofv3 trace comes from
 KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip", "union_kernel": "tq_union.hip",
-                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "docset_tree_score_kernel": "tq_docset_tree_score.hip", "tree_kernel": "tq_tree.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
+                "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "docset_tree_score_kernel": "tq_docset_tree_score.hip", "tree_kernel": "tq_tree.hip", "tree_fields_kernel": "tq_tree_fields.hip", "docset_score_fields_kernel": "tq_docset_score_fields.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
                 "phrase_sweep_kernel": "tq_phrase.hip", "phrase_kernel": "tq_phrase.hip"}
 
 

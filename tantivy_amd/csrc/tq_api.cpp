@@ -185,6 +185,60 @@ int tq_segment_upload_device(tq_ctx *ctx, int device, uint32_t max_doc, const ui
                                fn_len, record_option, true, out);
 }
 
+// F fields over one doc-id space: the sub-files laid end to end (each keeps its header and gets its own padding, the
+// next one starts 16-byte aligned), uploaded as ONE .idx and ONE .pos buffer; the per-field bases shift a term's offsets
+// when it is prepared (tq_fields.cpp), so every decode path works on the concatenation unchanged.
+int tq_segment_upload_fields(tq_ctx *ctx, int device, uint32_t max_doc, uint32_t n_fields, const tq_field_files *fields,
+                             uint8_t record_option, tq_segment **out) {
+  if (!ctx || !out || !fields) return fail(TQ_ERR_INVALID, "tq_segment_upload_fields: null argument");
+  if (n_fields == 0 || n_fields > TQ_MAX_FIELDS)
+    return fail(TQ_ERR_INVALID, "tq_segment_upload_fields: n_fields %u not in 1..%u", n_fields, TQ_MAX_FIELDS);
+  if (n_fields == 1)
+    return tq_segment_upload(ctx, device, max_doc, fields[0].idx, fields[0].idx_len, fields[0].pos, fields[0].pos_len,
+                             fields[0].fieldnorm, fields[0].fn_len, record_option, out);
+  uint64_t idx_base[TQ_MAX_FIELDS], pos_base[TQ_MAX_FIELDS], pos_len[TQ_MAX_FIELDS];
+  size_t idx_total = 0, pos_total = 0;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    const tq_field_files &ff = fields[f];
+    if (!ff.idx) return fail(TQ_ERR_INVALID, "tq_segment_upload_fields: field %u: null idx", f);
+    if (ff.idx_len < 8) return fail(TQ_ERR_FORMAT, "field %u: idx sub-file shorter than its 8-byte header", f);
+    if (ff.fieldnorm && ff.fn_len < max_doc)
+      return fail(TQ_ERR_FORMAT, "field %u: fieldnorm file has %zu bytes for max_doc %u", f, ff.fn_len, max_doc);
+    pos_len[f] = ff.pos && ff.pos_len ? ff.pos_len : 0;
+    idx_base[f] = idx_total;
+    pos_base[f] = pos_total;
+    // (the last field's padding is the buffer's own)
+    idx_total += f + 1 < n_fields ? (ff.idx_len + PAD + 15) & ~(size_t)15 : ff.idx_len;
+    pos_total += f + 1 < n_fields && pos_len[f] ? (pos_len[f] + PAD + 15) & ~(size_t)15 : pos_len[f];
+  }
+  std::vector<uint8_t> idx(idx_total, 0), pos(pos_total, 0);
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    memcpy(idx.data() + idx_base[f], fields[f].idx, fields[f].idx_len);
+    if (pos_len[f]) memcpy(pos.data() + pos_base[f], fields[f].pos, pos_len[f]);
+  }
+  tq_segment *s = nullptr;
+  int rc = segment_upload_common(ctx, device, max_doc, idx.data(), idx_total, pos_total ? pos.data() : nullptr, pos_total,
+                                 fields[0].fieldnorm, fields[0].fn_len, record_option, false, &s);
+  if (rc != TQ_OK) return rc;
+  s->n_fields = n_fields;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    s->field_idx_base[f] = idx_base[f];
+    s->field_idx_len[f] = fields[f].idx_len;
+    s->field_pos_base[f] = pos_base[f];
+    s->field_pos_len[f] = pos_len[f];
+    if (f == 0 || !fields[f].fieldnorm) continue;
+    hipError_t e = hipMalloc((void **)&s->d_fn_field[f], (size_t)max_doc + PAD);
+    if (e == hipSuccess) e = hipMemset(s->d_fn_field[f] + max_doc, 0, PAD);
+    if (e == hipSuccess) e = hipMemcpy(s->d_fn_field[f], fields[f].fieldnorm, max_doc, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      tq_segment_free(s);
+      return fail(TQ_ERR_HIP, "field %u fieldnorms: %s", f, hipGetErrorString(e));
+    }
+  }
+  *out = s;
+  return TQ_OK;
+}
+
 void tq_segment_free(tq_segment *s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
@@ -198,6 +252,8 @@ void tq_segment_free(tq_segment *s) {
   if (s->d_idx) (void)hipFree(s->d_idx);
   if (s->d_pos) (void)hipFree(s->d_pos);
   if (s->d_fn) (void)hipFree(s->d_fn);
+  for (uint8_t *fn : s->d_fn_field)
+    if (fn) (void)hipFree(fn);
   if (s->d_alive) (void)hipFree(s->d_alive);
   if (s->d_docmat) (void)hipFree(s->d_docmat);
   if (s->d_doccls) (void)hipFree(s->d_doccls);

@@ -210,6 +210,13 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
     if (has && set_q.empty()) set_q.assign(n_queries, 0);
     if (has) set_q[qi] = 1;
   }
+  // Multi-field segments (tq_fields.cpp): a phrase over terms of different fields is refused here, under the caller's
+  // index (the scan below sees a sub-batch); looked for only while the segment holds a term of a field != 0.
+  for (uint32_t qi = 0; s->n_field_terms && qi < n_queries; ++qi)
+    if (query_names_field(s, given[qi])) {
+      const int frc = check_field_query(s, given[qi], qi, "tq_count_batch");
+      if (frc != TQ_OK) return frc;
+    }
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     if (!done.empty() && done[qi]) continue;
     TqkCountQuery cq;

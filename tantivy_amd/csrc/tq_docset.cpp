@@ -108,6 +108,7 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
         sq.aux[n] = th.rdir_ent;
         sq.shift[n] = th.rdir_shift;
       }
+      sq.shift[n] |= (uint32_t)th.field << 8;  // (multi-field segments: the list's field, read by docset_score_fields_kernel alone)
       sq.access |= kind << (2u * n);
       if (i + 1 == c.n) sq.clause_end |= 1u << n;
       ++n;
@@ -181,6 +182,16 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   std::vector<TqkDocsetQuery> dqs(n_queries);
   std::vector<TqkScoreQuery> sqs(scored ? n_queries : 0u);
   std::vector<const float *> caches;  // the batch's Bm25Weight caches in order of first use (pointer identity, as in search)
+  // (a multi-field segment: tf_cache is one row per field, the rows go up together and the index names row 0)
+  const uint32_t cache_rows = s->n_fields;
+  auto cache_index = [&](const float *tc) {
+    for (size_t ci = caches.size(); ci >= cache_rows; ci -= cache_rows)  // (last first: neighbours share one)
+      if (caches[ci - cache_rows] == tc) return (uint32_t)(ci - cache_rows);
+    for (uint32_t f = 0; f < cache_rows; ++f) caches.push_back(tc + (size_t)f * 256u);
+    return (uint32_t)(caches.size() - cache_rows);
+  };
+  const bool fields = s->n_field_terms != 0;  // (0: no query is looked at for fields)
+  bool score_fields = false;                  // some scoring list of the batch belongs to a non-primary field
   uint64_t algo_bytes = 0;
   std::vector<uint32_t> tree_q;     // the queries that take the tree path (option "docset_trees"), ascending
   std::vector<TqdTreeQuery> tqs;    // ... and their records, in the same order
@@ -194,8 +205,15 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       const int src = check_set_query(s, q, qi, fn, &names_set);
       if (src != TQ_OK) return src;
     }
+    const bool names_field = fields && query_names_field(s, q);
+    if (names_field) {  // a phrase over two fields: refused whatever the tree options say
+      const int frc = check_field_query(s, q, qi, fn);
+      if (frc != TQ_OK) return frc;
+    }
     const int rc = docset_expression(s, q, dqs[qi], &why, scored ? &fc : nullptr);
     if (rc == FLAT_UNSUPPORTED && trees_on && !query_has_all(q) && (q.mode == TQ_MODE_PHRASE || bool_query_is_tree(q))) {
+      if (scored && names_field)  // (docset_tree_score_kernel scores under the primary field's norms)
+        return fail(TQ_ERR_UNSUPPORTED, "%s: query %u: scored doc sets of phrases and nested queries that name a non-primary field stay on the CPU in this version", fn, qi);
       if (scored) {  // the rule of the flat queries; plan_tree_query reads every term's weight
         if (!q.weights || !q.tf_cache) return fail(TQ_ERR_INVALID, "%s: query %u: null weights / tf_cache", fn, qi);
         for (uint32_t i = 0; i < (q.mode == TQ_MODE_PHRASE ? std::min(q.n_terms, 1u) : q.n_terms); ++i)
@@ -219,15 +237,8 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       return fail(TQ_ERR_UNSUPPORTED, "%s: query %u has a boosted match-all clause beside another scoring clause or a second match-all clause: its scores stay on the CPU",
                   fn, qi);
     if (has_list || fc.all_based) score_expression(s, q, fc, sqs[qi]);
-    if (sqs[qi].n_lists) {
-      uint32_t ci = (uint32_t)caches.size();
-      while (ci > 0 && caches[ci - 1] != q.tf_cache) --ci;  // (last first: neighbours share one)
-      if (ci == 0) {
-        caches.push_back(q.tf_cache);
-        ci = (uint32_t)caches.size();
-      }
-      sqs[qi].cache_idx = ci - 1u;
-    }
+    if (sqs[qi].n_lists) sqs[qi].cache_idx = cache_index(q.tf_cache);
+    for (uint32_t m = 0; names_field && m < sqs[qi].n_lists; ++m) score_fields = score_fields || (sqs[qi].shift[m] >> 8) != 0u;
     algo_bytes += (uint64_t)sqs[qi].n_lists * n_words * 8u;
   }
   if (!tree_q.empty()) {
@@ -257,14 +268,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       algo_bytes += ((uint64_t)tqs[i].n_terms + 2u) * n_words * 4u;
       if (!scored) continue;
       if (tqs[i].n_terms) {  // its cache in the blob the flat queries use: one index space for both scoring kernels
-        const float *tc = queries[tree_q[i]].tf_cache;
-        uint32_t ci = (uint32_t)caches.size();
-        while (ci > 0 && caches[ci - 1] != tc) --ci;
-        if (ci == 0) {
-          caches.push_back(tc);
-          ci = (uint32_t)caches.size();
-        }
-        tqs[i].cache_idx = ci - 1u;
+        tqs[i].cache_idx = cache_index(queries[tree_q[i]].tf_cache);
       }
       // the scoring pass: one bitmap word per 32 docs for every list that scores (under no MustNot on either level)
       uint32_t n_scoring = 0;
@@ -470,7 +474,15 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
           sp.tile_counts = p.tile_counts + (size_t)(r0 - sb.q0) * n_tiles;
           sp.tile_offs = p.tile_offs + (size_t)(r0 - sb.q0) * n_tiles;
           sp.n_queries = r1 - r0;
-          e = tqk_launch_docset_score(sp, st);
+          if (score_fields) {  // per-list norms (tq_fields.cpp)
+            TqkScoreFieldsParams fp{};
+            fp.base = sp;
+            fp.fn[0] = s->d_fn;
+            for (uint32_t f = 1; f < TQK_MAX_FIELDS; ++f) fp.fn[f] = s->d_fn_field[f];
+            e = tqk_launch_docset_score_fields(fp, st);
+          } else {
+            e = tqk_launch_docset_score(sp, st);
+          }
         }
         r0 = r1 + 1u;
       }

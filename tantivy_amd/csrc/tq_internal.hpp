@@ -143,6 +143,7 @@ struct TermHost {
   // its weight as given.  kSetReleased: the tombstone tq_term_set_release leaves (a later set may take the slot)
   enum : uint8_t { kNoSet = 0, kSet = 1, kSetReleased = 2 };
   uint8_t set_kind = kNoSet;
+  uint8_t field = 0;  // the field of a multi-field segment the list belongs to (tq_term_prepare_field); 0: the primary field
 };
 
 inline uint32_t rd32(const uint8_t *p) {
@@ -267,6 +268,16 @@ struct tq_segment {
   size_t idx_len = 0, pos_len = 0;    // sizes of the sub-files in HBM
   TqpInfo *d_tp_info = nullptr;       // device-side prepare: result slots (info + positions result)
   uint8_t *d_idx = nullptr, *d_pos = nullptr, *d_fn = nullptr, *d_alive = nullptr;
+  // Multi-field segments (tq_segment_upload_fields): the fields' sub-files lie end to end in d_idx / d_pos (h_idx /
+  // h_pos), field f's .idx sub-file (header included) at field_idx_base[f], its .pos sub-file at field_pos_base[f]; a
+  // term's offsets are shifted by them when it is prepared (term_by_off is keyed by the shifted offset: one key per
+  // (field, postings_off)).  d_fn is field 0's fieldnorms, d_fn_field[f] those of field f >= 1 (null: constant id).
+  uint32_t n_fields = 1;
+  uint64_t field_idx_base[TQ_MAX_FIELDS] = {}, field_idx_len[TQ_MAX_FIELDS] = {};
+  uint64_t field_pos_base[TQ_MAX_FIELDS] = {}, field_pos_len[TQ_MAX_FIELDS] = {};
+  uint8_t *d_fn_field[TQ_MAX_FIELDS] = {};
+  uint32_t n_field_terms = 0;  // prepared terms of fields != 0 (0: no entry point looks at a query's handles for fields)
+  uint8_t prep_field = 0;      // the field of the terms being registered (set under the lock by the field entry points)
   float *d_local_cache = nullptr;  // Bm25Weight.cache under the segment's OWN average fieldnorm (256 floats; null:
                                    // the header holds no usable token count): what the range maxima are built under
   uint64_t *d_docmat = nullptr;  // doc-major matrix of the dense lists (TqdSegment::docmat)
@@ -802,6 +813,9 @@ int wait_segment_idle(tq_segment *s);
 // the handle of a new term: its records appended to the host tables (the five facts every preparation path registers)
 uint32_t add_term(tq_segment *s, const TqdTerm &dt, const TermHost &th, uint64_t postings_off);
 int register_term(tq_segment *s, const TqdTerm &dt, const TermHost &th, uint64_t postings_off, tq_term_handle *out);
+int term_prepare_shifted(tq_segment *s, uint64_t postings_off, uint32_t postings_len, uint64_t positions_off,
+                         uint32_t positions_len, uint32_t doc_freq, tq_term_handle *out);
+int term_prepare_batch_shifted(tq_segment *s, const tq_term_info *infos, uint32_t n, tq_term_handle *out, uint8_t field);
 int sync_terms(tq_segment *s, hipStream_t st);
 void mark_term_dirty(tq_segment *s, uint32_t handle);
 // a TermInfo's postings range lies inside the idx sub-file's body (idx_len counts its 8-byte header)
@@ -918,6 +932,26 @@ inline bool is_term_set(const tq_segment *s, uint32_t h) { return h < s->terms.s
 inline const void *expression_bitmap(const tq_segment *s, const TermHost &th) {
   return th.dense_blob && (s->opt.use_dense || th.set_kind == TermHost::kSet) ? th.dense_blob : nullptr;
 }
+// ---- multi-field segments: does the query name a list of a field != 0?  (Asked only while s->n_field_terms != 0.)
+static_assert(TQK_MAX_FIELDS == TQ_MAX_FIELDS, "the multi-field launch parameters hold one fieldnorm pointer per field");
+inline uint32_t term_field_of(const tq_segment *s, uint32_t h) { return h < s->terms.size() ? s->terms[h].field : 0u; }
+inline bool query_names_field(const tq_segment *s, const tq_query &q) {
+  if (!q.terms || q.n_terms > TQ_MAX_TERMS) return false;
+  for (uint32_t i = 0; i < q.n_terms; ++i)
+    if (term_field_of(s, q.terms[i])) return true;
+  return false;
+}
+// The field of the terms registered while the scope — and the segment's lock — is held: add_term tags them with it.
+struct FieldScope {
+  tq_segment *s;
+  uint8_t was;
+  FieldScope(tq_segment *seg, uint8_t field) : s(seg), was(seg->prep_field) { s->prep_field = field; }
+  ~FieldScope() { s->prep_field = was; }
+  FieldScope(const FieldScope &) = delete;
+  FieldScope &operator=(const FieldScope &) = delete;
+};
+// TQ_ERR_INVALID (`fn: query qi: ...`) for a phrase, or a phrase atom, whose present terms are of different fields
+int check_field_query(const tq_segment *s, const tq_query &q, uint32_t qi, const char *fn);
 inline bool query_names_set(const tq_segment *s, const tq_query &q) {
   if (!q.terms || q.n_terms > TQ_MAX_TERMS) return false;
   for (uint32_t i = 0; i < q.n_terms; ++i)

@@ -201,6 +201,7 @@ struct TqdTreeQuery {
                                              // any of them is, scoring the present ones) instead of a conjunction;
                                              // bit 3: a CONST-SCORE leaf (a term set): present where its bit is, scoring
                                              // weight_bits as given — neither rank nor tf is read (tf8_off = dense_off)
+                                             // bits 4..6: the FIELD of the list (multi-field segments; 0 = the primary field)
   uint32_t dir_off[TQK_TREE_MAX_TERMS];      // phrase terms: position directory of the list (TqdTerm::pos_dir layout), 8-byte units
   uint32_t phrase_off[TQK_TREE_MAX_TERMS];   // phrase terms: max_offset - term_offset (phrase_scorer.rs:372-385)
   uint32_t outer[TQK_TREE_MAX_TERMS];        // per clause: its occur in the query
@@ -218,6 +219,17 @@ struct TqkTreeParams {
   uint32_t any_phrase;  // some query of the launch has a phrase atom (selects the kernel instantiation)
 };
 hipError_t tqk_launch_tree(const TqkTreeParams &p, int kpl, hipStream_t st);
+// The same trees over the lists of SEVERAL fields (tq_fields.cpp): tree_fields_kernel, tq_tree_fields.hip.  The field
+// of list t rides in bits 4..6 of TqdTreeQuery::atom_end[t] (the other kernels that read the record test single bits
+// below them); list t of field f scores under caches[(cache_idx + f) * 256 + fn[f][doc]] — fn[f] null: the constant
+// id — so a query's cache is F consecutive rows.  fn[0] = the segment's own fieldnorms.  These launch parameters alone
+// know about fields: TqdSegment stays as it is.
+constexpr uint32_t TQK_MAX_FIELDS = 8;
+struct TqkTreeFieldsParams {
+  TqkTreeParams base;
+  const uint8_t *fn[TQK_MAX_FIELDS];
+};
+hipError_t tqk_launch_tree_fields(const TqkTreeFieldsParams &p, int kpl, hipStream_t st);
 uint32_t tqk_tree_tiles(uint32_t n_words);
 // ---- the exact match bits of such trees for doc sets (tq_docset_tree.hip): query q's alive matching docs as bits
 // [part_start * words_per_list, + n_words) of the doc-set batch's scratch, every word stored once; no scores
@@ -398,6 +410,14 @@ struct TqkScoreParams {
   uint32_t any_blocks;             // some list of the sub-batch is TQK_SCORE_BLOCKS (selects the instantiation with LDS)
 };
 hipError_t tqk_launch_docset_score(const TqkScoreParams &p, hipStream_t st);
+// ... with scoring lists of SEVERAL fields (tq_fields.cpp): docset_score_fields_kernel, tq_docset_score_fields.hip.  The field of
+// list m rides in bits 8..10 of TqkScoreQuery::shift[m] (zero on every list of a launch that takes the kernel above,
+// whose range-directory lookup reads the whole word); norms as in TqkTreeFieldsParams.
+struct TqkScoreFieldsParams {
+  TqkScoreParams base;
+  const uint8_t *fn[TQK_MAX_FIELDS];
+};
+hipError_t tqk_launch_docset_score_fields(const TqkScoreFieldsParams &p, hipStream_t st);
 // ---- ... of phrases and nested boolean queries (tq_docset_tree_score.hip, option "docset_score_trees"): the pass behind the
 // write pass over the sub-batch's TREE queries, whose rows the flat pass leaves alone.  Tree i of the launch is query
 // query_of[i] of the sub-batch: that is where its tile_counts / tile_offs stand.

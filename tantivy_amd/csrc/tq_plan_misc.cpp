@@ -465,7 +465,7 @@ int plan_tree_query(tq_segment *s, const tq_query &q, uint32_t qi, TqdTreeQuery 
         memcpy(&tq.weight_bits[n], &A.w[A.phrase ? 0u : i], sizeof(float));  // (a phrase scores with ONE weight: the sum of its idfs)
         tq.handle[n] = A.handle[i];
         tq.inner[n] = A.inner;
-        tq.atom_end[n] = (i + 1u == A.n ? 1u : 0u) | (A.phrase ? 2u : 0u) | (A.any ? 4u : 0u) | (cset ? 8u : 0u);
+        tq.atom_end[n] = (i + 1u == A.n ? 1u : 0u) | (A.phrase ? 2u : 0u) | (A.any ? 4u : 0u) | (cset ? 8u : 0u) | ((uint32_t)th.field << 4);
         if (A.phrase) {
           const void *dir = own && th.posdir_blob ? th.posdir_blob : th.probe_posdir_blob;
           if (!dir)

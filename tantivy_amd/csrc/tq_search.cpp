@@ -142,9 +142,12 @@ void look_at_queries(Batch &b) {
     if (tc == last_tc && tc) {
       cache_idx = last_idx;
     } else if (tc) {
-      for (; cache_idx < b.caches.size(); ++cache_idx)
+      // (a multi-field segment: tf_cache is one row per field, and the rows go up together — cache_idx names row 0)
+      const uint32_t rows = b.s->n_fields;
+      for (; cache_idx < b.caches.size(); cache_idx += rows)
         if (b.caches[cache_idx] == tc) break;
-      if (cache_idx == b.caches.size()) b.caches.push_back(tc);
+      if (cache_idx == b.caches.size())
+        for (uint32_t f = 0; f < rows; ++f) b.caches.push_back(tc + (size_t)f * 256u);
       last_tc = tc;
       last_idx = cache_idx;
     }
@@ -1255,7 +1258,18 @@ int launch_tree(const Batch &b, hipStream_t gst) {
   tp.table_base = (const uint8_t *)b.s->share_table_lo;
   tp.n_queries = (uint32_t)g.queries.size();
   tp.n_words = (b.s->max_doc + 31u) / 32u;
-  for (const TqdTreeQuery &tq : g.tree) tp.any_phrase |= tq.has_phrase;
+  bool any_field = false;  // some list of the launch belongs to a non-primary field: per-list norms (tq_fields.cpp)
+  for (const TqdTreeQuery &tq : g.tree) {
+    tp.any_phrase |= tq.has_phrase;
+    for (uint32_t t = 0; b.s->n_field_terms && t < tq.n_terms; ++t) any_field = any_field || (tq.atom_end[t] >> 4) != 0u;
+  }
+  if (any_field) {
+    TqkTreeFieldsParams fp{};
+    fp.base = tp;
+    fp.fn[0] = b.s->d_fn;
+    for (uint32_t f = 1; f < TQK_MAX_FIELDS; ++f) fp.fn[f] = b.s->d_fn_field[f];
+    return launched(tqk_launch_tree_fields(fp, g.kpl, gst), "nested boolean (multi-field)");
+  }
   return launched(tqk_launch_tree(tp, g.kpl, gst), "nested boolean");
 }
 
@@ -1487,15 +1501,39 @@ struct AllStrip {
   std::deque<AllView> views;  // (a deque: the views' arrays stay where they are)
   std::deque<std::array<uint8_t, TQ_MAX_TERMS>> set_occurs;  // the occurs of TQ_MODE_AND / TQ_MODE_OR queries that name a set
   std::vector<uint8_t> set_q;  // per query: it names a term set and runs as a tree (empty: no query of the batch does)
+  std::deque<TreeView> field_phrases;  // TQ_MODE_PHRASE queries of a non-primary field as one-atom trees
   uint32_t n_all_based = 0, n_set = 0;
 };
 int strip_all_clauses(const tq_segment *s, const tq_query *queries, uint32_t n_queries, AllStrip &st) {
   const bool sets = s->n_set_slots != 0;
+  // Multi-field segments (tq_fields.cpp; looked for only while the segment holds a prepared term of a field != 0): a
+  // query that names such a term scores per LIST norms — tree_fields_kernel, tq_tree_fields.hip, whatever its mode,
+  // flagged in set_q like a query that names a set (the same route: occurs on call scratch, every list through a
+  // bitmap, nothing pruned).  A TQ_MODE_PHRASE query becomes the tree "one Must clause holding one phrase atom".
+  const bool fields = s->n_field_terms != 0;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     bool names_set = false;
     if (sets) {
       const int src = check_set_query(s, queries[qi], qi, "tq_search_batch", &names_set);
       if (src != TQ_OK) return src;
+    }
+    bool names_field = false;
+    if (fields && query_names_field(s, queries[qi])) {
+      const int frc = check_field_query(s, queries[qi], qi, "tq_search_batch");
+      if (frc != TQ_OK) return frc;
+      names_field = true;
+      if (queries[qi].mode == TQ_MODE_PHRASE) {
+        const tq_query &pq = queries[qi];
+        if (pq.n_terms < 2 || !pq.phrase_offsets || !pq.weights) return fail(TQ_ERR_INVALID, "query %u: a phrase needs >= 2 terms, offsets and a weight", qi);
+        if (st.eff.empty()) st.eff.assign(queries, queries + n_queries);
+        st.field_phrases.emplace_back();
+        docset_tree_view(pq, st.field_phrases.back(), true);
+        st.eff[qi] = st.field_phrases.back().q;
+        if (st.set_q.empty()) st.set_q.assign(n_queries, 0);
+        st.set_q[qi] = 1;
+        ++st.n_set;
+        continue;
+      }
     }
     bool all_based = false;
     if (query_has_all(queries[qi])) {
@@ -1515,15 +1553,19 @@ int strip_all_clauses(const tq_segment *s, const tq_query *queries, uint32_t n_q
         st.eff[qi] = st.views.back().q;
       }
     }
-    if (!names_set) continue;
+    if (!names_set && !names_field) continue;
     const tq_query &q = st.eff.empty() ? queries[qi] : st.eff[qi];  // (what is left of it without its All clauses)
     if (all_based) {
-      for (uint32_t i = 0; i < q.n_terms; ++i)
-        if (is_term_set(s, q.terms[i]) && !(q.mode == TQ_MODE_BOOL && q.occurs && q.occurs[i] == TQ_MUST_NOT))
+      for (uint32_t i = 0; i < q.n_terms; ++i) {
+        const bool must_not = q.mode == TQ_MODE_BOOL && q.occurs && q.occurs[i] == TQ_MUST_NOT;
+        if (is_term_set(s, q.terms[i]) && !must_not)
           return fail(TQ_ERR_UNSUPPORTED, "tq_search_batch: query %u: a term set as a Should clause beside a match-all clause stays on the CPU (its counts and doc sets are taken)", qi);
+        if (names_field && term_field_of(s, q.terms[i]) && !must_not)  // (all_kernel scores under field 0's norms)
+          return fail(TQ_ERR_UNSUPPORTED, "tq_search_batch: query %u: a Should term of field %u (the scoring terms of a query whose match-all clauses make every doc a candidate are its Should terms) stays on the CPU (its counts and doc sets are taken)", qi, term_field_of(s, q.terms[i]));
+      }
       continue;
     }
-    if (!query_names_set(s, q)) continue;  // (the set went with an EMPTY form's clauses)
+    if (!(names_set && query_names_set(s, q)) && !(names_field && query_names_field(s, q))) continue;  // (it went with an EMPTY form's clauses)
     if (st.set_q.empty()) st.set_q.assign(n_queries, 0);
     st.set_q[qi] = 1;
     ++st.n_set;

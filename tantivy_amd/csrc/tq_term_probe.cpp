@@ -163,7 +163,7 @@ int build_probe_tables(tq_segment *s, uint32_t handle, bool *ok, bool must) {
   if (e == hipSuccess) e = enqueue_bitmap(s, dl, t.doc_freq, blob);
   // range maxima of the list (tq_ashare.hip's bound on a probed list), into the slot
   uint8_t *rmb = base + s->probe_bm_bytes + tf_cap + dir_cap;
-  const bool want_rm = !t.rmax_blob && s->d_local_cache;
+  const bool want_rm = !t.rmax_blob && s->d_local_cache && !t.field;  // (norm-derived: field-0 lists only)
   if (e == hipSuccess && want_rm) e = enqueue_rmax(s, dl, t.doc_freq, rmb);
   uint32_t h_bad = 0, lmax = 0;
   if (e == hipSuccess) e = finish_tables(s, dl, &h_bad, want_rm ? &lmax : nullptr);

@@ -50,6 +50,7 @@ void prep_apply_lmax(tq_segment *s, bool wait) {
     for (size_t i = 0; i < hs.size(); ++i) {
       TermHost &t = s->terms[hs[i]];
       const uint32_t lmax = s->prep_lmax_host[bx][i];
+      if (t.field) continue;  // (a non-primary list: the maximum was taken under field 0's norms)
       if (t.rdir_blob && !t.rmax_blob && lmax) t.rmax_list = std::min<uint32_t>(lmax, 255u);
     }
     hs.clear();
@@ -131,7 +132,7 @@ static int build_tf8(tq_segment *s, uint32_t handle, const uint32_t *d_tfs) {
 // scratch.  13 KB per list of a 10M-doc segment (five levels, one byte per 1024 docs at the finest).
 static int build_rmax(tq_segment *s, uint32_t handle, const DecodedList &dl) {
   TermHost &t = s->terms[handle];
-  if (t.rmax_blob || !s->d_local_cache || !t.doc_freq) return TQ_OK;
+  if (t.rmax_blob || !s->d_local_cache || !t.doc_freq || t.field) return TQ_OK;  // (norm-derived: field-0 lists only)
   const uint32_t n_out = tqd_rm_level_off(s->max_doc, TQD_RM_LEVELS);  // every level (tq_device.h)
   void *blob = nullptr;
   const int arc = dense_alloc(s, n_out, &blob);
@@ -185,7 +186,7 @@ int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok) {
 // against the side tables' budget.  Over the budget, or no memory: the list stays without (stage A gathers as before).
 void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st) {
   TermHost &t = s->terms[handle];
-  if (t.lnorm_blob || s->lnorm_off || !t.n_blocks || !t.d_self || !s->dseg.fieldnorm) return;
+  if (t.lnorm_blob || s->lnorm_off || !t.n_blocks || !t.d_self || !s->dseg.fieldnorm || t.field) return;
   const size_t bytes = (size_t)t.n_blocks * 128u;
   if (s->dense_bytes_total + bytes > s->dense_budget()) return;
   void *blob = nullptr;
@@ -267,7 +268,7 @@ int add_to_doc_signatures(tq_segment *s, uint32_t handle) {
       t.rdir_blob = t.rdir_ent = nullptr, t.rdir_shift = 0;  // (not filled: the list does without)
       return fail(TQ_ERR_HIP, "range directory: %s", hipGetErrorString(e));
     }
-    if (s->d_local_cache) {  // the list's largest tf/(tf + norm): td_rmax_scatter_kernel's value, one range
+    if (s->d_local_cache && !t.field) {  // the list's largest tf/(tf + norm): td_rmax_scatter_kernel's value, one range
       uint32_t *acc = dl.dt + t.doc_freq + 8u, lmax = 0;
       e = hipMemsetAsync(acc, 0, sizeof(uint32_t), s->stream);
       if (e == hipSuccess) e = tqp_launch_list_max(dl.dd, dl.dt, t.doc_freq, s->d_fn, s->dseg.const_fieldnorm_id, s->d_local_cache, acc, s->stream);

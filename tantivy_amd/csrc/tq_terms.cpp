@@ -13,6 +13,12 @@ uint32_t add_term(tq_segment *s, const TqdTerm &dt, const TermHost &th, uint64_t
   s->terms.push_back(th);
   s->terms.back().wants_col = !s->cols_reserved || s->reserved_cols.count(postings_off) != 0;
   s->h_dterms.push_back(dt);
+  if (s->prep_field) {  // a list of a non-primary field (tq_term_prepare_field): TqdTermHead::has_freq bits 26..28
+    s->terms.back().field = s->prep_field;
+    s->terms.back().wants_col = !s->cols_reserved;  // (reserved columns name field-0 lists)
+    s->h_dterms.back().has_freq |= (uint32_t)s->prep_field << 26;
+    ++s->n_field_terms;
+  }
   mark_term_dirty(s, handle);
   s->term_by_off.emplace(postings_off, handle);
   return handle;
@@ -205,12 +211,11 @@ int sync_terms(tq_segment *s, hipStream_t st) {
 
 }  // namespace tqi
 
-extern "C" {
-
-int tq_term_prepare(tq_segment *s, uint64_t postings_off, uint32_t postings_len,
+namespace tqi {
+// tq_term_prepare with offsets already shifted by the field's bases (field 0: as given); s->prep_field names the field
+int term_prepare_shifted(tq_segment *s, uint64_t postings_off, uint32_t postings_len,
                     uint64_t positions_off, uint32_t positions_len, uint32_t doc_freq,
                     tq_term_handle *out) {
-  if (!s || !out) return fail(TQ_ERR_INVALID, "tq_term_prepare: null argument");
   TQ_SEGMENT_LOCK(s);
   auto it = s->term_by_off.find(postings_off);
   if (it != s->term_by_off.end()) {
@@ -242,9 +247,16 @@ int tq_term_prepare(tq_segment *s, uint64_t postings_off, uint32_t postings_len,
   }
   return register_term(s, w.dt, w.th, postings_off, out);
 }
+}  // namespace tqi
 
-
-}  // extern "C"
+extern "C" int tq_term_prepare(tq_segment *s, uint64_t postings_off, uint32_t postings_len,
+                               uint64_t positions_off, uint32_t positions_len, uint32_t doc_freq,
+                               tq_term_handle *out) {
+  if (!s || !out) return fail(TQ_ERR_INVALID, "tq_term_prepare: null argument");
+  if (s->n_fields > 1)  // (field 0's ranges, checked against field 0's sub-files)
+    return tq_term_prepare_field(s, 0, postings_off, postings_len, positions_off, positions_len, doc_freq, out);
+  return term_prepare_shifted(s, postings_off, postings_len, positions_off, positions_len, doc_freq, out);
+}
 
 // The new terms of a batch together: every list is walked on the host as tq_term_prepare walks
 // it, the blobs go up from ONE pinned staging buffer with asynchronous copies and one wait, and the signature bits of
@@ -285,7 +297,7 @@ struct PrepareBatch {
 
 int prepare_one(PrepareBatch &b, uint32_t i) {
   const tq_term_info &ti = b.infos[i];
-  return tq_term_prepare(b.s, ti.postings_off, ti.postings_len, ti.positions_off, ti.positions_len, ti.doc_freq, &b.out[i]);
+  return term_prepare_shifted(b.s, ti.postings_off, ti.postings_len, ti.positions_off, ti.positions_len, ti.doc_freq, &b.out[i]);
 }
 
 // under the lock: out[] of the terms the segment knows, the others collected
@@ -489,8 +501,8 @@ void resolve_repeats(PrepareBatch &b) {  // (a term named twice in one call)
 }
 }  // namespace
 
-extern "C" int tq_term_prepare_batch(tq_segment *s, const tq_term_info *infos, uint32_t n, tq_term_handle *out) {
-  if (!s || (!infos && n) || (!out && n)) return fail(TQ_ERR_INVALID, "tq_term_prepare_batch: null argument");
+// (infos: offsets already shifted by the field's bases; the terms registered under the second lock are tagged `field`)
+int tqi::term_prepare_batch_shifted(tq_segment *s, const tq_term_info *infos, uint32_t n, tq_term_handle *out, uint8_t field) {
   PrepareBatch b{s, infos, n, out};
   {
     TQ_SEGMENT_LOCK(s);
@@ -503,6 +515,7 @@ extern "C" int tq_term_prepare_batch(tq_segment *s, const tq_term_info *infos, u
   if (!s->device_prepare()) prewalk(b);
   b.t1 = Clock::now();
   TQ_SEGMENT_LOCK(s);
+  FieldScope field_scope(s, field);  // (add_term tags what is registered while the lock is held)
   b.t2 = b.t3 = b.t4 = Clock::now();
   HIP_TRY(hipSetDevice(s->device));
   if (s->device_prepare()) {  // (no host copy of the index: the device walk, term by term)
@@ -521,4 +534,10 @@ extern "C" int tq_term_prepare_batch(tq_segment *s, const tq_term_info *infos, u
   if (rc != TQ_OK) return rc;
   resolve_repeats(b);
   return TQ_OK;
+}
+
+extern "C" int tq_term_prepare_batch(tq_segment *s, const tq_term_info *infos, uint32_t n, tq_term_handle *out) {
+  if (!s || (!infos && n) || (!out && n)) return fail(TQ_ERR_INVALID, "tq_term_prepare_batch: null argument");
+  if (s->n_fields > 1) return tq_term_prepare_batch_fields(s, infos, nullptr, n, out);
+  return term_prepare_batch_shifted(s, infos, n, out, 0);
 }

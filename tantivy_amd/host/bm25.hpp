@@ -52,6 +52,11 @@ struct Bm25Weight {
   Score weight = 0.0f;
   Score cache[256];
   Score average_fieldnorm = 0.0f;
+  // A Searcher over multi-field segments: F x 256 floats, row f = the cache under field f's average fieldnorm, contiguous
+  // as tq_query.tf_cache wants them (row 0 == cache); empty: single-field, `cache` is the cache.  Lives in the ONE shared
+  // object of a Searcher, so that a Weight is what it was.
+  std::vector<Score> field_rows;
+  const Score *tf_cache() const { return field_rows.empty() ? cache : field_rows.data(); }
 
   // bm25.rs:158-166 (new) + :62-69 (compute_tf_cache)
   static Bm25Weight from_idf(Score idf_value, Score average_fieldnorm) {

@@ -157,6 +157,36 @@ int tqh_searcher_add_segment(tqh_searcher *s, int device, uint32_t max_doc, uint
   });
 }
 
+// A segment of n_fields fields over one doc-id space (tq_segment_upload_fields): fields[f] = field f's sub-files,
+// term_fields[i] = the field of terms[i] (null: all of field 0).  Term ids share one space over the fields.  The doc
+// matrix's columns are reserved for the densest lists of field 0, the primary field.
+int tqh_searcher_add_segment_fields(tqh_searcher *s, int device, uint32_t max_doc, uint8_t record_option,
+                                    uint32_t n_fields, const tq_field_files *fields, const tqh_term_info *terms,
+                                    const uint8_t *term_fields, uint32_t n_terms) {
+  return guard([&] {
+    if (!s || !fields || (!terms && n_terms)) throw TantivyError(TantivyError::InvalidArgument, "null argument");
+    auto seg = std::make_shared<SegmentReader>(s->ctx, device, (uint32_t)s->segments.size(), max_doc, record_option,
+                                               fields, n_fields);
+    std::vector<std::pair<uint32_t, uint64_t>> by_df;
+    for (uint32_t i = 0; i < n_terms; ++i) {
+      TermInfo ti;
+      ti.doc_freq = terms[i].doc_freq;
+      ti.postings_start = terms[i].postings_start;
+      ti.postings_end = terms[i].postings_end;
+      ti.positions_start = terms[i].positions_start;
+      ti.positions_end = terms[i].positions_end;
+      const uint32_t f = term_fields ? term_fields[i] : 0u;
+      seg->add_term(terms[i].term_id, ti, f);
+      if (f == 0) by_df.emplace_back(terms[i].doc_freq, terms[i].postings_start);
+    }
+    reserve_densest_columns(*seg, by_df);
+    s->one_device = s->segments.empty() || (s->one_device && s->device == device);
+    s->device = device;
+    s->segments.push_back(seg);
+    s->searcher.reset(new Searcher(s->segments));
+  });
+}
+
 // A segment whose term ids are the term ordinals of its TermInfoStore (the value half of the
 // field's term dictionary file): no per-term TermInfo crosses the boundary.
 int tqh_searcher_add_segment_with_store(tqh_searcher *s, int device, uint32_t max_doc,
@@ -211,6 +241,17 @@ int tqh_searcher_add_remote_stats(tqh_searcher *s, uint64_t max_doc, uint64_t to
     std::vector<std::pair<uint32_t, uint32_t>> v;
     for (uint32_t i = 0; i < n_terms; ++i) v.emplace_back(term_ids[i], doc_freqs[i]);
     s->searcher->add_remote_statistics(max_doc, total_num_tokens, v);
+  });
+}
+
+// ... of multi-field segments: tokens[f] = the remote segments' token count of field f
+int tqh_searcher_add_remote_stats_fields(tqh_searcher *s, uint64_t max_doc, const uint64_t *tokens, uint32_t n_fields,
+                                         const uint32_t *term_ids, const uint32_t *doc_freqs, uint32_t n_terms) {
+  return guard([&] {
+    if (!s || !s->searcher || !tokens) throw TantivyError(TantivyError::InvalidArgument, "no segments");
+    std::vector<std::pair<uint32_t, uint32_t>> v;
+    for (uint32_t i = 0; i < n_terms; ++i) v.emplace_back(term_ids[i], doc_freqs[i]);
+    s->searcher->add_remote_statistics(max_doc, std::vector<uint64_t>(tokens, tokens + n_fields), v);
   });
 }
 
@@ -581,7 +622,8 @@ int tqh_exchange_ms(tqh_searcher *s, float *ms) {
   });
 }
 
-// Bm25Weight for tests / tools: weight and 256-entry cache from global statistics.
+// Bm25Weight for tests / tools: weight and 256-entry cache from global statistics — of ONE field (a multi-field segment's
+// tf_cache is one such cache per field, laid end to end by the caller: tantivy_amd_host.h).
 int tqh_bm25_for_terms(const uint64_t *term_doc_freqs, uint32_t n_terms, uint64_t total_num_docs,
                        uint64_t total_num_tokens, float boost, float *weight_out,
                        float *cache_out /*256 or null*/) {

@@ -31,14 +31,26 @@ SegmentReader::SegmentReader(tq_ctx *ctx, int device, uint32_t segment_ord, uint
   if (rc != TQ_OK) throw_tq(rc);
   uint64_t t = 0;
   for (int i = 0; i < 8; ++i) t |= (uint64_t)idx[i] << (8 * i);
-  total_num_tokens_ = t;
+  total_num_tokens_[0] = t;
+}
+SegmentReader::SegmentReader(tq_ctx *ctx, int device, uint32_t segment_ord, uint32_t max_doc, uint8_t record_option,
+                             const tq_field_files *fields, uint32_t n_fields)
+    : segment_ord_(segment_ord), max_doc_(max_doc), record_option_(record_option) {
+  const int rc = tq_segment_upload_fields(ctx, device, max_doc, n_fields, fields, record_option, &seg_);
+  if (rc != TQ_OK) throw_tq(rc);
+  n_fields_ = n_fields;
+  for (uint32_t f = 0; f < n_fields; ++f) {
+    uint64_t t = 0;
+    for (int i = 0; i < 8; ++i) t |= (uint64_t)fields[f].idx[i] << (8 * i);
+    total_num_tokens_[f] = t;
+  }
 }
 SegmentReader::SegmentReader(DeviceResident, tq_ctx *ctx, int device, uint32_t segment_ord,
                              uint32_t max_doc, uint8_t record_option, const uint8_t *d_idx,
                              size_t idx_len, const uint8_t *d_pos, size_t pos_len,
                              const uint8_t *d_fieldnorm, size_t fn_len, uint64_t total_num_tokens)
-    : segment_ord_(segment_ord), max_doc_(max_doc), record_option_(record_option),
-      total_num_tokens_(total_num_tokens) {
+    : segment_ord_(segment_ord), max_doc_(max_doc), record_option_(record_option) {
+  total_num_tokens_[0] = total_num_tokens;
   const int rc = tq_segment_upload_device(ctx, device, max_doc, d_idx, idx_len, d_pos, pos_len,
                                           d_fieldnorm, fn_len, record_option, &seg_);
   if (rc != TQ_OK) throw_tq(rc);
@@ -48,7 +60,16 @@ SegmentReader::~SegmentReader() {
   delete[] fast_handles_.load(std::memory_order_relaxed);
 }
 
-void SegmentReader::add_term(uint32_t term_id, const TermInfo &info) { terms_[term_id] = info; }
+void SegmentReader::add_term(uint32_t term_id, const TermInfo &info, uint32_t field) {
+  if (field >= n_fields_) throw TantivyError(TantivyError::InvalidArgument, "add_term: field out of range");
+  terms_[term_id] = info;
+  if (field) term_field_[term_id] = (uint8_t)field;
+}
+uint32_t SegmentReader::term_field(uint32_t term_id) const {
+  if (term_field_.empty()) return 0;
+  auto it = term_field_.find(term_id);
+  return it == term_field_.end() ? 0u : it->second;
+}
 void SegmentReader::set_term_info_store(std::shared_ptr<const TermInfoStore> store) {
   store_ = std::move(store);
 }
@@ -77,12 +98,12 @@ tq_term_handle SegmentReader::term_handle(uint32_t term_id) {
   const TermInfo *ti = get_term_info(term_id);
   tq_term_handle handle = TQ_TERM_ABSENT;
   if (ti) {
-    const int rc = tq_term_prepare(seg_, ti->postings_start,
-                                   (uint32_t)(ti->postings_end - ti->postings_start),
-                                   ti->positions_start,
-                                   (uint32_t)(ti->positions_end - ti->positions_start),
-                                   ti->doc_freq, &handle);
-    if (rc != TQ_OK) throw_tq(rc);  // (tq_term_prepare is idempotent per postings offset: two threads
+    const int rc = tq_term_prepare_field(seg_, term_field(term_id), ti->postings_start,
+                                         (uint32_t)(ti->postings_end - ti->postings_start),
+                                         ti->positions_start,
+                                         (uint32_t)(ti->positions_end - ti->positions_start),
+                                         ti->doc_freq, &handle);
+    if (rc != TQ_OK) throw_tq(rc);  // (idempotent per field and postings offset: two threads
   }                                 // preparing the same term get the same handle)
   std::lock_guard<std::mutex> lk(m_);
   handles_[term_id] = handle;
@@ -125,6 +146,7 @@ void SegmentReader::prepare_terms(const uint32_t *term_ids, size_t n) {
   if (fresh.size() < 2) return;  // (one term: term_handle's own road)
   std::vector<tq_term_info> infos;
   std::vector<uint32_t> ids;
+  std::vector<uint8_t> fields;
   for (uint32_t t : fresh) {
     const TermInfo *ti = get_term_info(t);
     if (!ti) continue;  // (absent: term_handle records TQ_TERM_ABSENT)
@@ -136,10 +158,11 @@ void SegmentReader::prepare_terms(const uint32_t *term_ids, size_t n) {
     x.doc_freq = ti->doc_freq;
     infos.push_back(x);
     ids.push_back(t);
+    fields.push_back((uint8_t)term_field(t));
   }
   if (infos.empty()) return;
   std::vector<tq_term_handle> hs(infos.size(), TQ_TERM_ABSENT);
-  const int rc = tq_term_prepare_batch(seg_, infos.data(), (uint32_t)infos.size(), hs.data());
+  const int rc = tq_term_prepare_batch_fields(seg_, infos.data(), fields.data(), (uint32_t)infos.size(), hs.data());
   if (rc != TQ_OK) throw_tq(rc);
   std::lock_guard<std::mutex> lk(m_);
   std::atomic<tq_term_handle> *fast = fast_handles_.load(std::memory_order_relaxed);
@@ -183,8 +206,15 @@ tq_term_handle resolve_handle(const std::shared_ptr<SegmentReader> &seg, const W
 void Searcher::add_remote_statistics(
     uint64_t max_doc, uint64_t total_num_tokens,
     const std::vector<std::pair<uint32_t, uint32_t>> &term_doc_freqs) {
+  add_remote_statistics(max_doc, std::vector<uint64_t>{total_num_tokens}, term_doc_freqs);
+}
+void Searcher::add_remote_statistics(
+    uint64_t max_doc, const std::vector<uint64_t> &total_num_tokens_per_field,
+    const std::vector<std::pair<uint32_t, uint32_t>> &term_doc_freqs) {
+  if (total_num_tokens_per_field.size() > TQ_MAX_FIELDS)
+    throw TantivyError(TantivyError::InvalidArgument, "add_remote_statistics: more fields than TQ_MAX_FIELDS");
   remote_docs_ += max_doc;
-  remote_tokens_ += total_num_tokens;
+  for (size_t f = 0; f < total_num_tokens_per_field.size(); ++f) remote_tokens_[f] += total_num_tokens_per_field[f];
   for (auto &tf : term_doc_freqs) remote_doc_freq_[tf.first] += tf.second;
   shared_cache_.reset();
   if (std::atomic<uint32_t> *fw = fast_weights_.load(std::memory_order_acquire))  // (the statistics changed)
@@ -219,18 +249,31 @@ Score Searcher::term_weight_cached(uint32_t term, uint64_t nd) const {
   return w;
 }
 
+// One Bm25Weight cache per field (Bm25Weight::for_terms per TermQuery: the average fieldnorm is the term's field's), the
+// F rows contiguous as tq_query.tf_cache wants them, inside the one object every Weight shares until the statistics change.
+std::shared_ptr<Bm25Weight> Searcher::shared_caches(uint64_t nd) const {
+  std::lock_guard<std::mutex> lk(cache_m_);
+  if (!shared_cache_) {
+    const Score avg = (Score)total_num_tokens(0) / (Score)nd;
+    auto bw = std::make_shared<Bm25Weight>(Bm25Weight::from_idf(0.0f, avg));
+    if (n_fields_ > 1) {
+      bw->field_rows.resize((size_t)n_fields_ * 256u);
+      for (uint32_t f = 0; f < n_fields_; ++f) {
+        const Bm25Weight row = Bm25Weight::from_idf(0.0f, (Score)total_num_tokens(f) / (Score)nd);
+        std::memcpy(bw->field_rows.data() + (size_t)f * 256u, row.cache, sizeof row.cache);
+      }
+    }
+    shared_cache_ = bw;
+  }
+  return shared_cache_;
+}
+
 Searcher::FlatContext Searcher::flat_context() const {
   FlatContext fc;
   fc.nd = total_num_docs();
-  const uint64_t nt = total_num_tokens();
   if (fc.nd == 0)
     throw TantivyError(TantivyError::InvalidArgument, "no documents: BM25 statistics undefined");
-  std::lock_guard<std::mutex> lk(cache_m_);
-  if (!shared_cache_) {
-    const Score avg = (Score)nt / (Score)fc.nd;
-    shared_cache_ = std::make_shared<Bm25Weight>(Bm25Weight::from_idf(0.0f, avg));
-  }
-  fc.cache = shared_cache_;
+  fc.cache = shared_caches(fc.nd);
   return fc;
 }
 void Searcher::weight_flat_into(const FlatContext &fc, uint8_t mode, const uint32_t *terms, uint32_t n_terms, Weight &w) const {
@@ -252,10 +295,16 @@ uint64_t Searcher::total_num_docs() const {
   for (auto &s : segments_) n += s->max_doc();
   return n;
 }
-uint64_t Searcher::total_num_tokens() const {
-  uint64_t n = remote_tokens_;
-  for (auto &s : segments_) n += s->total_num_tokens();
+uint64_t Searcher::total_num_tokens(uint32_t field) const {
+  uint64_t n = field < TQ_MAX_FIELDS ? remote_tokens_[field] : 0;
+  for (auto &s : segments_) n += s->total_num_tokens(field);
   return n;
+}
+uint32_t Searcher::term_field(uint32_t term) const {
+  if (n_fields_ == 1) return 0;
+  for (auto &s : segments_)
+    if (const uint32_t f = s->term_field(term)) return f;
+  return 0;
 }
 uint64_t Searcher::doc_freq(uint32_t term) const {
   uint64_t n = 0;
@@ -267,18 +316,18 @@ uint64_t Searcher::doc_freq(uint32_t term) const {
 }
 
 Weight Searcher::weight(const Query &query) const {
-  const uint64_t nd = total_num_docs(), nt = total_num_tokens();
+  const uint64_t nd = total_num_docs();
   if (nd == 0)
     throw TantivyError(TantivyError::InvalidArgument, "no documents: BM25 statistics undefined");
   Weight w;
-  {
-    std::lock_guard<std::mutex> lk(cache_m_);
-    if (!shared_cache_) {
-      const Score avg = (Score)nt / (Score)nd;
-      shared_cache_ = std::make_shared<Bm25Weight>(Bm25Weight::from_idf(0.0f, avg));
-    }
-    w.bm25 = shared_cache_;
-  }
+  w.bm25 = shared_caches(nd);
+  // PhraseQuery::new panics on terms of different fields (phrase_query.rs:66-75)
+  auto check_phrase_fields = [&](const Query &ph) {
+    if (n_fields_ == 1) return;
+    for (auto &ot : ph.phrase_terms)
+      if (term_field(ot.second) != term_field(ph.phrase_terms[0].second))
+        throw TantivyError(TantivyError::InvalidArgument, "All terms in a phrase query must belong to the same field");
+  };
   // Weight::scorer(reader, boost) starts at 1.0; every BoostWeight multiplies its own factor in
   // (boost_query.rs:70-72) and the leaf applies Bm25Weight::boost_by(boost) (bm25.rs:82-92)
   auto boost_by = [](Score weight, Score boost) { return boost == 1.0f ? weight : weight * boost; };
@@ -309,6 +358,7 @@ Weight Searcher::weight(const Query &query) const {
       if (query.phrase_terms.size() < 2)
         throw TantivyError(TantivyError::InvalidArgument,
                            "A phrase query is required to have strictly more than one term.");
+      check_phrase_fields(query);
       w.mode = TQ_MODE_PHRASE;
       Score idf_sum = 0.0f;  // bm25.rs:121-128
       for (auto &ot : query.phrase_terms) {
@@ -463,6 +513,7 @@ Weight Searcher::weight(const Query &query) const {
                                "A phrase query is required to have strictly more than one term.");
           if (ph.phrase_terms.size() > 8)
             throw TantivyError(TantivyError::Unsupported, "a phrase inside a boolean query takes at most 8 terms on the device");
+          check_phrase_fields(ph);
           Score idf_sum = 0.0f;
           for (auto &ot : ph.phrase_terms) idf_sum += idf(doc_freq(ot.second), nd);
           const Score pw = boost_by(idf_sum * (1.0f + K1), boost);
@@ -561,7 +612,7 @@ struct SegmentBatch {
       q.n_terms = (uint32_t)w.terms.size();
       q.terms = handles.data() + at;  // stable: reserved up front
       q.weights = w.weights.data();
-      q.tf_cache = w.bm25->cache;
+      q.tf_cache = w.bm25->tf_cache();
       q.mode = w.mode;
       q.phrase_offsets = w.phrase_offsets.empty() ? nullptr : w.phrase_offsets.data();
       q.k = k;
@@ -584,7 +635,9 @@ struct Searcher::DeviceBatch {
 };
 
 Searcher::Searcher(std::vector<std::shared_ptr<SegmentReader>> segments)
-    : segments_(std::move(segments)), device_batch_(new DeviceBatch()) {}
+    : segments_(std::move(segments)), device_batch_(new DeviceBatch()) {
+  for (auto &s : segments_) n_fields_ = std::max(n_fields_, s->num_fields());
+}
 Searcher::~Searcher() { delete[] fast_weights_.load(std::memory_order_relaxed); }
 
 uint32_t Searcher::bound_slack_ppm(const SegmentReader &seg) const {
@@ -740,7 +793,7 @@ Fruit Searcher::search(const Query &query, const TopDocs &collector) {
     q.n_terms = (uint32_t)w.terms.size();
     q.terms = handles.data();
     q.weights = w.weights.data();
-    q.tf_cache = w.bm25->cache;
+    q.tf_cache = w.bm25->tf_cache();
     q.mode = w.mode;
     q.phrase_offsets = w.phrase_offsets.empty() ? nullptr : w.phrase_offsets.data();
     q.k = k;

@@ -45,10 +45,15 @@ struct DocAddress {
   }
 };
 
-// A device-resident single-field segment (SegmentReader + InvertedIndexReader + FieldNormReader
-// of the reference, for one indexed text field).
+// A device-resident segment (SegmentReader + InvertedIndexReader + FieldNormReader of the reference): one indexed
+// text field, or — the multi-field constructor — F <= TQ_MAX_FIELDS fields over one doc-id space (one
+// InvertedIndexReader and one FieldNormReader per Field).  A term id belongs to ONE field; ids of all fields share one
+// uint32_t space.  Field 0 is the primary field (include/tantivy_amd.h "multi-field segments").
 class SegmentReader {
  public:
+  // F fields: fields[f] = the sub-files of field f (tq_field_files), one record_option for all of them
+  SegmentReader(tq_ctx *ctx, int device, uint32_t segment_ord, uint32_t max_doc, uint8_t record_option,
+                const tq_field_files *fields, uint32_t n_fields);
   SegmentReader(tq_ctx *ctx, int device, uint32_t segment_ord, uint32_t max_doc,
                 uint8_t record_option, const uint8_t *idx, size_t idx_len, const uint8_t *pos,
                 size_t pos_len, const uint8_t *fieldnorm, size_t fn_len);
@@ -62,7 +67,9 @@ class SegmentReader {
   SegmentReader(const SegmentReader &) = delete;
   SegmentReader &operator=(const SegmentReader &) = delete;
 
-  void add_term(uint32_t term_id, const TermInfo &info);  // TermDictionary substitute
+  void add_term(uint32_t term_id, const TermInfo &info, uint32_t field = 0);  // TermDictionary substitute (of `field`)
+  uint32_t term_field(uint32_t term_id) const;  // the field a term id was added under (unknown ids: 0)
+  uint32_t num_fields() const { return n_fields_; }
   // the segment's TermInfoStore: term ids are term ordinals, TermInfos are decoded on first use
   // (TermDictionary::term_info_from_ord, termdict.rs:185-188)
   void set_term_info_store(std::shared_ptr<const class TermInfoStore> store);
@@ -75,7 +82,8 @@ class SegmentReader {
   bool handle_known(uint32_t term_id) const;
   uint32_t max_doc() const { return max_doc_; }
   uint32_t segment_ord() const { return segment_ord_; }
-  uint64_t total_num_tokens() const { return total_num_tokens_; }  // inverted_index_reader.rs:72-73
+  // inverted_index_reader.rs:72-73, of one field (a field the segment does not have: 0)
+  uint64_t total_num_tokens(uint32_t field = 0) const { return field < n_fields_ ? total_num_tokens_[field] : 0; }
   uint8_t record_option() const { return record_option_; }
   tq_segment *raw() const { return seg_; }
 
@@ -83,7 +91,9 @@ class SegmentReader {
   tq_segment *seg_ = nullptr;
   uint32_t segment_ord_, max_doc_;
   uint8_t record_option_;
-  uint64_t total_num_tokens_ = 0;
+  uint32_t n_fields_ = 1;
+  uint64_t total_num_tokens_[TQ_MAX_FIELDS] = {};
+  std::unordered_map<uint32_t, uint8_t> term_field_;  // the term ids of fields != 0 (filled before the first search)
   mutable std::mutex m_;  // term tables: Searcher::search may be called from many threads
   mutable std::unordered_map<uint32_t, TermInfo> terms_;
   std::unordered_map<uint32_t, tq_term_handle> handles_;
@@ -316,7 +326,7 @@ struct Weight {
   std::vector<uint8_t> clause_min_should;  // TQ_MODE_BOOL: the nested queries' minimum_number_should_match by clause
                                            // index (TQ_MAX_TERMS entries), or empty
   uint32_t min_should_match = 0;         // TQ_MODE_BOOL
-  std::shared_ptr<Bm25Weight> bm25;      // holds the shared tf cache
+  std::shared_ptr<Bm25Weight> bm25;      // holds the shared tf cache (multi-field segments: one row per field, Bm25Weight::field_rows)
 };
 
 class Searcher {
@@ -327,7 +337,9 @@ class Searcher {
   Searcher &operator=(const Searcher &) = delete;
   // Bm25StatisticsProvider (bm25.rs:27-50)
   uint64_t total_num_docs() const;
-  uint64_t total_num_tokens() const;
+  uint64_t total_num_tokens(uint32_t field = 0) const;  // of one field, over all segments (+ remote statistics)
+  uint32_t num_fields() const { return n_fields_; }      // the largest field count of the segments
+  uint32_t term_field(uint32_t term) const;              // the field a term id belongs to (0 on single-field indexes)
   uint64_t doc_freq(uint32_t term) const;
   size_t num_segments() const { return segments_.size(); }
   SegmentReader &segment_reader(size_t ord) { return *segments_[ord]; }
@@ -338,6 +350,9 @@ class Searcher {
   // entry, and a concurrent weight() may store an idf computed from the statistics of before the call (tantivy
   // builds a new Searcher per reader reload; so does the host mirror's caller).
   void add_remote_statistics(uint64_t max_doc, uint64_t total_num_tokens,
+                             const std::vector<std::pair<uint32_t, uint32_t>> &term_doc_freqs);
+  // ... of multi-field segments: one token count per field (the signature above means field 0)
+  void add_remote_statistics(uint64_t max_doc, const std::vector<uint64_t> &total_num_tokens_per_field,
                              const std::vector<std::pair<uint32_t, uint32_t>> &term_doc_freqs);
 
   Weight weight(const Query &query) const;
@@ -398,7 +413,10 @@ class Searcher {
   static constexpr uint32_t kFastWeights = 1u << 20;
   mutable std::atomic<std::atomic<uint32_t> *> fast_weights_{nullptr};
   Score term_weight_cached(uint32_t term, uint64_t nd) const;
-  uint64_t remote_docs_ = 0, remote_tokens_ = 0;
+  uint64_t remote_docs_ = 0, remote_tokens_[TQ_MAX_FIELDS] = {};
+  uint32_t n_fields_ = 1;
+  // the cache object every Weight shares: the primary field's Bm25Weight, with (multi-field) one row per field in it
+  std::shared_ptr<Bm25Weight> shared_caches(uint64_t nd) const;
   std::unordered_map<uint32_t, uint64_t> remote_doc_freq_;
 };
 
