@@ -484,6 +484,55 @@ int tq_decode_postings(tq_segment *seg, tq_term_handle term, uint32_t *docs, uin
 int tq_decode_position_deltas(tq_segment *seg, tq_term_handle term, uint32_t *out, uint64_t cap,
                               uint64_t *n_out);
 
+/* ---- derived tables, read back (DIAGNOSTIC: tests of term preparation; no query path uses them) ----
+ * replaces: nothing in the reference — the tables are this library's own (tq_device.h), built when a term is prepared.
+ * tq_term_table_read copies ONE table of a prepared list, or of the segment, to the host as the device holds it: the
+ * segment's stream is waited for, list maxima still on their way from tq_term_prepare_batch are applied, then plain
+ * device-to-host copies — no kernel is launched and no device memory allocated.  *n_bytes = the table's size; a table
+ * the list does not have: *n_bytes = 0 and TQ_OK.  out NULL or cap_bytes 0: the size alone; cap_bytes below the size,
+ * an unknown `which`, a handle that is out of range or a released term set: TQ_ERR_INVALID.  Per-segment tables ignore
+ * `term`.  Layouts: tantivy_amd/csrc/tq_device.h (TqdTermHead / TqdTerm / TqdSegment); TQ_TABLE_RMAX = every level as
+ * laid out by tqd_rm_level_off; TQ_TABLE_RDIR = the directory words (padded to four), then one entry per posting;
+ * TQ_TABLE_FLAT = the doc ids (padded to 16 bytes), then min(tf, 255) per posting; TQ_TABLE_LNORM = 128 bytes per block. */
+enum {
+  TQ_TABLE_REC = 0,        /* (n_blocks + 1) x 4 u32 */
+  TQ_TABLE_COARSE = 1,
+  TQ_TABLE_TAIL_DOCS = 2,
+  TQ_TABLE_TAIL_TFS = 3,
+  TQ_TABLE_POS_BLK = 4,
+  TQ_TABLE_POS_TAIL = 5,
+  TQ_TABLE_DENSE = 6,      /* {doc bits, rank} per 32 docs */
+  TQ_TABLE_BITS = 7,
+  TQ_TABLE_POS_DIR = 8,
+  TQ_TABLE_TF8 = 9,
+  TQ_TABLE_RMAX = 10,
+  TQ_TABLE_RDIR = 11,
+  TQ_TABLE_LNORM = 12,
+  TQ_TABLE_FLAT = 13,
+  TQ_TABLE_PROBE_DENSE = 14,   /* the probe pool's, while the list holds a slot */
+  TQ_TABLE_PROBE_TF8 = 15,
+  TQ_TABLE_PROBE_POS_DIR = 16,
+  TQ_TABLE_DOCMAT = 32,        /* per segment: max_doc u64 */
+  TQ_TABLE_DOCCLS = 33,        /* max_doc u64 */
+  TQ_TABLE_LOCAL_CACHE = 34,   /* 256 floats: Bm25Weight.cache under the segment's own average fieldnorm */
+  TQ_TABLE_MIN_FIELDNORM_ID = 35 /* one u32 */
+};
+typedef struct tq_term_table_info_t {
+  uint32_t n_blocks, n_full, n_tail, coarse_shift;
+  uint64_t payload_base;
+  uint32_t has_freq;      /* TqdTermHead::has_freq: column slot, signature bit, tf-class flag, ... */
+  uint32_t rdir_shift;    /* 0: no range directory */
+  uint32_t rmax_list;     /* 255: none */
+  uint32_t n_pos_blocks, n_pos_tail;
+  uint32_t field;
+  uint64_t n_positions;
+  uint32_t doc_freq;
+  uint32_t probe_slot;    /* 0xFFFFFFFF: the list holds no slot of the probe pool */
+} tq_term_table_info_t;
+int tq_term_table_read(tq_segment *seg, tq_term_handle term, uint32_t which, void *out, uint64_t cap_bytes,
+                       uint64_t *n_bytes);
+int tq_term_table_info(tq_segment *seg, tq_term_handle term, tq_term_table_info_t *info);
+
 /* ---- codec writers (segment finalisation / merges on the device) ----
  * replaces: PostingsSerializer::{new_term, write_doc, close_term} (src/postings/serializer.rs:
  * 342-481; skip entries src/postings/skip.rs:55-88; block-max selection serializer.rs:404-428)

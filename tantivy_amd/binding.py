@@ -152,7 +152,25 @@ EXPORTS = [
     "tq_term_set_prepare", "tq_term_set_info", "tq_term_set_release",
     "tq_segment_upload_fields", "tq_segment_get_fields_stats", "tq_term_prepare_field", "tq_term_prepare_batch_fields",
     "tq_term_field", "tqh_searcher_add_segment_fields", "tqh_searcher_add_remote_stats_fields",
+    "tq_term_table_read", "tq_term_table_info",
 ]
+
+# tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
+TERM_TABLES = {
+    "rec": (0, np.uint32), "coarse": (1, np.uint32), "tail_docs": (2, np.uint32), "tail_tfs": (3, np.uint32),
+    "pos_blk": (4, np.uint64), "pos_tail": (5, np.uint32), "dense": (6, np.uint32), "bits": (7, np.uint32),
+    "pos_dir": (8, np.uint32), "tf8": (9, np.uint8), "rmax": (10, np.uint8), "rdir": (11, np.uint32),
+    "lnorm": (12, np.uint8), "flat": (13, np.uint8), "probe_dense": (14, np.uint32), "probe_tf8": (15, np.uint8),
+    "probe_pos_dir": (16, np.uint32),
+    "docmat": (32, np.uint64), "doccls": (33, np.uint64), "local_cache": (34, np.float32), "min_fieldnorm_id": (35, np.uint32),
+}
+
+
+class TqTermTableInfo(C.Structure):  # tq_term_table_info_t
+    _fields_ = [("n_blocks", C.c_uint32), ("n_full", C.c_uint32), ("n_tail", C.c_uint32), ("coarse_shift", C.c_uint32),
+                ("payload_base", C.c_uint64), ("has_freq", C.c_uint32), ("rdir_shift", C.c_uint32),
+                ("rmax_list", C.c_uint32), ("n_pos_blocks", C.c_uint32), ("n_pos_tail", C.c_uint32), ("field", C.c_uint32),
+                ("n_positions", C.c_uint64), ("doc_freq", C.c_uint32), ("probe_slot", C.c_uint32)]
 
 
 def lib():
@@ -217,6 +235,8 @@ def lib():
     L.tq_term_prepare_field.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
     L.tq_term_prepare_batch_fields.argtypes = [vp, C.POINTER(TqTermInfo), u8p, C.c_uint32, u32p]
     L.tq_term_field.argtypes = [vp, C.c_uint32, u32p]
+    L.tq_term_table_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.tq_term_table_info.argtypes = [vp, C.c_uint32, C.POINTER(TqTermTableInfo)]
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -908,6 +928,25 @@ class DeviceIndex:
         tfs = np.zeros(max(1, doc_freq), np.uint32)
         _check(lib().tq_decode_postings(self.segment_raw(segment_ord), h, _u32(docs), _u32(tfs)))
         return docs[:doc_freq], tfs[:doc_freq]
+
+    def term_table(self, handle, which, segment_ord=0):
+        """tq_term_table_read (diagnostic): one derived table of the HANDLE's list, or of the segment (`handle` ignored),
+        as the device holds it -> numpy array of the table's element type (TERM_TABLES), empty if the list has no such
+        table.  "rec" is (n_blocks + 1, 4), "dense" (words, 2): {doc bits, rank}."""
+        w, dtype = TERM_TABLES[which]
+        seg, n = self.segment_raw(segment_ord), C.c_uint64()
+        _check(lib().tq_term_table_read(seg, int(handle), w, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.uint8)
+        if n.value:
+            _check(lib().tq_term_table_read(seg, int(handle), w, out.ctypes.data, out.size, C.byref(n)))
+        out = out[:out.size - out.size % np.dtype(dtype).itemsize].view(dtype)
+        return out.reshape(-1, 4) if which == "rec" else (out.reshape(-1, 2) if which in ("dense", "probe_dense") else out)
+
+    def term_table_info(self, handle, segment_ord=0):
+        """tq_term_table_info (diagnostic) -> dict of the list's preparation facts (tq_term_table_info_t)."""
+        info = TqTermTableInfo()
+        _check(lib().tq_term_table_info(self.segment_raw(segment_ord), int(handle), C.byref(info)))
+        return {n: int(getattr(info, n)) for n, _ in TqTermTableInfo._fields_}
 
     def decode_position_deltas(self, term_id, cap, segment_ord=0):
         h = self.term_handle(term_id, segment_ord)

@@ -615,6 +615,125 @@ int tq_decode_position_deltas(tq_segment *s, tq_term_handle term, uint32_t *out,
   return TQ_OK;
 }
 
+// ---- derived tables, read back (diagnostic: tests/test_gpu_prepare_tables.py).  Where a table lives and how long it
+// is, from the host's records alone; the copies below are the only device work.
+namespace {
+struct TableSpan {
+  const void *p = nullptr;
+  size_t bytes = 0;
+  bool host = false;  // (a value the host keeps: min_fieldnorm_id)
+};
+bool table_span(tq_segment *s, uint32_t term, uint32_t which, TableSpan &sp) {
+  if (which >= TQ_TABLE_DOCMAT) {
+    const size_t per_doc = (size_t)s->max_doc * sizeof(uint64_t);
+    switch (which) {
+      case TQ_TABLE_DOCMAT: sp = {s->d_docmat, s->d_docmat ? per_doc : 0, false}; return true;
+      case TQ_TABLE_DOCCLS: sp = {s->d_doccls, s->d_doccls ? per_doc : 0, false}; return true;
+      case TQ_TABLE_LOCAL_CACHE: sp = {s->d_local_cache, s->d_local_cache ? 256 * sizeof(float) : 0, false}; return true;
+      case TQ_TABLE_MIN_FIELDNORM_ID: sp = {&s->dseg.min_fieldnorm_id, sizeof(uint32_t), true}; return true;
+      default: return false;
+    }
+  }
+  const TermHost &t = s->terms[term];
+  const TqdTerm &d = s->h_dterms[term];
+  const size_t n_words = bitmap_words(s);
+  const size_t n_dir = ((size_t)t.doc_freq + 3) / 4 + 1;
+  const bool list = t.set_kind == TermHost::kNoSet;  // (a term set has a bitmap and nothing else)
+  uint32_t n_buckets = 0;
+  if (list && t.n_blocks) (void)coarse_shift(s->max_doc, t.n_blocks, &n_buckets);
+  auto span = [&](const void *p, size_t bytes) { sp = {p, p ? bytes : 0, false}; };
+  switch (which) {
+    case TQ_TABLE_REC: span(list ? d.rec : nullptr, 16 * ((size_t)t.n_blocks + 1)); return true;
+    case TQ_TABLE_COARSE: span(list ? d.coarse : nullptr, 4 * ((size_t)n_buckets + 1)); return true;
+    case TQ_TABLE_TAIL_DOCS: span(list && t.n_tail ? d.tail_docs : nullptr, 4 * (size_t)t.n_tail); return true;
+    case TQ_TABLE_TAIL_TFS: span(list && t.n_tail ? d.tail_tfs : nullptr, 4 * (size_t)t.n_tail); return true;
+    case TQ_TABLE_POS_BLK: span(list && d.n_pos_blocks ? d.pos_blk : nullptr, 8 * (size_t)d.n_pos_blocks); return true;
+    case TQ_TABLE_POS_TAIL: span(list && d.n_pos_tail ? d.pos_tail : nullptr, 4 * (size_t)d.n_pos_tail); return true;
+    case TQ_TABLE_DENSE: span(t.dense_blob, n_words * sizeof(uint2)); return true;
+    case TQ_TABLE_BITS: span(list ? d.bits : nullptr, ((n_words + 255) & ~(size_t)255) * sizeof(uint32_t)); return true;
+    case TQ_TABLE_POS_DIR: span(list ? t.posdir_blob : nullptr, n_dir * sizeof(uint32_t)); return true;
+    case TQ_TABLE_TF8: span(list ? t.tf8_blob : nullptr, t.doc_freq); return true;
+    case TQ_TABLE_RMAX: span(list ? t.rmax_blob : nullptr, tqd_rm_level_off(s->max_doc, TQD_RM_LEVELS)); return true;
+    case TQ_TABLE_RDIR: span(list ? t.rdir_blob : nullptr, t.rdir_shift ? rdir_bytes(s, t.doc_freq, t.rdir_shift) : 0); return true;
+    case TQ_TABLE_LNORM: span(list ? t.lnorm_blob : nullptr, (size_t)t.n_blocks * 128u); return true;
+    case TQ_TABLE_FLAT:
+      span(list ? t.flat_blob : nullptr, (((size_t)t.doc_freq * sizeof(uint32_t) + 15) & ~(size_t)15) + t.doc_freq);
+      return true;
+    case TQ_TABLE_PROBE_DENSE: span(t.probe_dense_blob, n_words * sizeof(uint2)); return true;
+    case TQ_TABLE_PROBE_TF8: span(t.probe_tf8_blob, t.doc_freq); return true;
+    case TQ_TABLE_PROBE_POS_DIR: span(t.probe_posdir_blob, n_dir * sizeof(uint32_t)); return true;
+    default: return false;
+  }
+}
+int table_handle_ok(tq_segment *s, tq_term_handle term, const char *who) {
+  if (term >= s->terms.size()) return fail(TQ_ERR_INVALID, "%s: unknown term handle %u", who, term);
+  if (s->terms[term].set_kind == TermHost::kSetReleased) return fail(TQ_ERR_INVALID, "%s: handle %u is a released term set", who, term);
+  return TQ_OK;
+}
+// every producer of a table has finished: the segment's stream (the batch path's copy stream is ordered before it by
+// an event), the batches in flight, and the list maxima a tq_term_prepare_batch call left on their way
+int table_quiesce(tq_segment *s) {
+  HIP_TRY(hipSetDevice(s->device));
+  const int rc = wait_segment_idle(s);
+  if (rc != TQ_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  prep_apply_lmax(s, true);
+  return TQ_OK;
+}
+}  // namespace
+
+int tq_term_table_read(tq_segment *s, tq_term_handle term, uint32_t which, void *out, uint64_t cap_bytes, uint64_t *n_bytes) {
+  if (!s || !n_bytes) return fail(TQ_ERR_INVALID, "tq_term_table_read: null argument");
+  *n_bytes = 0;
+  TQ_SEGMENT_LOCK(s);
+  if (which < TQ_TABLE_DOCMAT) {
+    const int hrc = table_handle_ok(s, term, "tq_term_table_read");
+    if (hrc != TQ_OK) return hrc;
+  }
+  int rc = table_quiesce(s);
+  if (rc != TQ_OK) return rc;
+  TableSpan sp;
+  if (!table_span(s, term, which, sp)) return fail(TQ_ERR_INVALID, "tq_term_table_read: unknown table %u", which);
+  *n_bytes = sp.bytes;
+  if (!sp.bytes || !out || !cap_bytes) return TQ_OK;
+  if (cap_bytes < sp.bytes)
+    return fail(TQ_ERR_INVALID, "tq_term_table_read: table %u holds %zu bytes, room for %llu", which, sp.bytes, (unsigned long long)cap_bytes);
+  if (sp.host) {
+    memcpy(out, sp.p, sp.bytes);
+    return TQ_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(out, sp.p, sp.bytes, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return TQ_OK;
+}
+
+int tq_term_table_info(tq_segment *s, tq_term_handle term, tq_term_table_info_t *info) {
+  if (!s || !info) return fail(TQ_ERR_INVALID, "tq_term_table_info: null argument");
+  TQ_SEGMENT_LOCK(s);
+  int rc = table_handle_ok(s, term, "tq_term_table_info");
+  if (rc != TQ_OK) return rc;
+  rc = table_quiesce(s);
+  if (rc != TQ_OK) return rc;
+  const TermHost &t = s->terms[term];
+  const TqdTerm &d = s->h_dterms[term];
+  *info = tq_term_table_info_t{};
+  info->n_blocks = t.n_blocks;
+  info->n_full = t.n_full;
+  info->n_tail = t.n_tail;
+  info->coarse_shift = d.coarse_shift;
+  info->payload_base = d.payload_base;
+  info->has_freq = d.has_freq;
+  info->rdir_shift = t.rdir_blob ? t.rdir_shift : 0u;
+  info->rmax_list = t.rmax_list;
+  info->n_pos_blocks = d.n_pos_blocks;
+  info->n_pos_tail = d.n_pos_tail;
+  info->field = t.field;
+  info->n_positions = t.n_positions;
+  info->doc_freq = t.doc_freq;
+  info->probe_slot = t.probe_slot < 0 ? 0xFFFFFFFFu : (uint32_t)t.probe_slot;
+  return TQ_OK;
+}
+
 }  // extern "C"
 
 extern "C" {

@@ -889,6 +889,8 @@ hipError_t finish_tables(tq_segment *s, const DecodedList &dl, uint32_t *bad, ui
 inline uint32_t rmax_list_of(uint32_t lmax) { return lmax ? std::min<uint32_t>(lmax, 255u) : 255u; }
 inline uint32_t sig_bit(uint32_t handle) { return (handle * 0x9E3779B1u) >> (32 - 4); }  // 0 .. TQD_SIG_BITS - 1
 uint32_t rdir_plan(tq_segment *s, uint32_t doc_freq);
+size_t rdir_dir_words(const tq_segment *s, uint32_t S);                  // directory slots of a shift, padded to four
+size_t rdir_bytes(const tq_segment *s, uint32_t doc_freq, uint32_t S);  // ... + one entry per posting, in bytes
 int attach_rdir(tq_segment *s, uint32_t handle, uint32_t S, void **tab);  // allocates the list's range directory and names it in its TermHost
 int ensure_docmat(tq_segment *s);
 int add_to_doc_signatures(tq_segment *s, uint32_t handle);
