@@ -58,7 +58,7 @@ enum tq_record_option { TQ_BASIC = 0, TQ_WITH_FREQS = 1, TQ_WITH_FREQS_AND_POSIT
 /* Which executor the reference would pick (src/query/boolean_query/boolean_weight.rs:236-431):
  * AND    = all-Must term clauses   -> block_wand_intersection
  * OR     = all-Should term clauses -> block_wand / BufferedUnionScorer
- * PHRASE = PhraseQuery (slop 0)    -> PhraseScorer */
+ * PHRASE = PhraseQuery             -> PhraseScorer (tq_query.slop 0: the exact phrase; > 0: see "Sloppy phrases") */
 enum tq_mode { TQ_MODE_AND = 0, TQ_MODE_OR = 1, TQ_MODE_PHRASE = 2, TQ_MODE_BOOL = 3 };
 /* TQ_MODE_BOOL = BooleanQuery whose clauses are terms or BooleanQuerys of terms (unions of terms; since round 5
  * also nested intersections / exclusions / minimums: tq_query.nested_occurs), with mixed occurs
@@ -112,6 +112,10 @@ typedef struct tq_query {
                                     one nested all-Should BooleanQuery, `+a +(b OR c)`); NULL =
                                     every term is its own clause */
   uint32_t min_should_match;     /* TQ_MODE_BOOL: BooleanQuery::minimum_number_should_match */
+  uint32_t slop;                 /* TQ_MODE_PHRASE: PhraseQuery::set_slop, 0..TQ_MAX_SLOP (see "Sloppy phrases" below); any
+                                    other mode: must be 0 (TQ_ERR_INVALID naming the query).  The field sits in what was
+                                    padding in front of the next pointer: sizeof(tq_query) and every other offset are
+                                    unchanged, and CALLERS MUST ZERO THE STRUCT (a zeroed query has slop 0) */
   /* TQ_MODE_BOOL, one level of nesting beyond unions of terms (round 5): a clause_of group is a nested
    * BooleanQuery of terms, every term with its own occur INSIDE it — `+a +(+b +c)`, `(+b +c) d`, `+a -(+b +c)`,
    * `+a +(+b c -d)` — and its own minimum_number_should_match.  Both NULL (or every nested occur TQ_SHOULD and every
@@ -133,6 +137,44 @@ typedef struct tq_query {
                                         phrase that is a clause of its own is a clause_of group of one atom.
                                         A UNION one level further down (nested_occurs | TQ_NESTED_ANY, round 6): see above. */
 } tq_query;
+#ifdef __cplusplus
+static_assert(sizeof(void *) != 8 || (sizeof(tq_query) == 104 && offsetof(tq_query, nested_occurs) == 80 &&
+                                      offsetof(tq_query, slop) == offsetof(tq_query, min_should_match) + 4),
+              "tq_query.slop fills the padding behind min_should_match: the layout of the struct is unchanged");
+#endif
+
+/* ---- Sloppy phrases (TQ_MODE_PHRASE with slop > 0) ----
+ * slop 0 is the exact phrase: the kernels and kernel_mask it always had.  slop > 0 runs as TQ_KERNEL_PHRASE_SLOP, a
+ * launch group of its own over the lists' bitmaps (every list through a bitmap + rank directory, its own or the probe
+ * pool's, as for TQ_KERNEL_TREE: "use_dense" off or tables outside one 32 GB span is TQ_ERR_UNSUPPORTED), nothing
+ * pruned: "exhaustive" 0 and 1 give the same rows and tq_last_batch_match_counts is the number of matching docs.
+ * Validation as for any phrase (2..8 terms, phrase_offsets, a field with positions, a finite weight; an absent term is
+ * an empty result).  The device restates the reference's algorithm, which is NOT "an exact phrase with a window":
+ *  - the lists are walked in COST order (doc freq ascending, ties in phrase order), and with slop that order changes
+ *    verdicts and counts;
+ *  - SCORED and UNSCORED verdicts differ for 3 and more terms: tq_search_batch* / tq_submit / tq_search_one count
+ *    matches carrying the slop already spent (doc `a x b x c`, phrase "a b c"~1: no match); tq_count_batch and
+ *    tq_docset_batch* (under "docset_trees" = 1; refused without it as phrases are) test the last term without it
+ *    (the same doc matches) — exactly as the reference's scoring and non-scoring PhraseScorer do;
+ *  - for 3 and more terms the reference carries a list of (position, slop spent) that has no bound.  The device keeps
+ *    TQ_SLOP_CARRY_CAP entries per candidate doc.  A doc whose initial or carried list would exceed that bumps the
+ *    query's OVERFLOW word and its verdict is unspecified: the host-output entry points (tq_search_batch[_opts],
+ *    tq_count_batch, host tq_docset_batch) then return TQ_ERR_UNSUPPORTED naming the first such query ("carried position
+ *    list over TQ_SLOP_CARRY_CAP") — the caller falls back for it; the other queries' rows are written and valid.
+ *    tq_submit / tq_wait / tq_search_one fail the overflowing query's ticket alone.  Callers of the _device variants MUST
+ *    read tq_last_batch_slop_overflows for batches that hold a sloppy phrase of 3 or more terms.  A 2-term phrase never
+ *    overflows.
+ * Refused (TQ_ERR_UNSUPPORTED naming the query, nothing launched, the segment usable): slop > TQ_MAX_SLOP;
+ * tq_docset_scored_batch* with a sloppy phrase (also under "docset_score_trees"); a sloppy phrase over terms of a field
+ * other than 0.  A phrase ATOM inside a TQ_MODE_BOOL query cannot carry a slop: there is one slop per query and only
+ * TQ_MODE_PHRASE reads it.
+ * algorithmic_bytes of such a query is a MODEL, not a measurement: (lists + 1) x bitmap words x 4, (lists + 2) where a
+ * result bitmap is written (once, by the sloppy-phrase kernel itself) and read back (doc sets, counts); positions are not
+ * counted. */
+#define TQ_MAX_SLOP 255u /* the reference keeps the slop spent in a u8: above 255 its cast wraps, and nobody should depend on that */
+/* Entries of a carried list the device keeps per candidate doc (two lists per lane in LDS: 64 lanes x 2 x 32 x (4 + 1)
+ * bytes = 20 KB per workgroup, 8 workgroups per CU of 160 KB; random docs of tf <= 8, 3..8 terms, slop <= 8 reached 27) */
+#define TQ_SLOP_CARRY_CAP 32u
 
 /* The normal form of a query with TQ_TERM_ALL clauses (pure: needs no segment; handles other than TQ_TERM_ALL /
  * TQ_TERM_ABSENT count as present lists).  kind: TQ_ALL_EMPTY = no doc matches; TQ_ALL_PLAIN = the query is its
@@ -589,6 +631,13 @@ int tq_count_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
 /* Number of docs scored per query by the last tq_search_batch* call on this segment (with
  * "exhaustive" = 1 that is the number of matches, which makes (Count, TopDocs) one pass). */
 int tq_last_batch_match_counts(tq_segment *seg, uint32_t *out, uint32_t n_queries);
+/* Per query of the last tq_search_batch* / tq_docset_batch* / tq_count_batch call on this segment: the candidate docs of
+ * a sloppy phrase whose carried position list went over TQ_SLOP_CARRY_CAP (0 for every other query, and for every
+ * query when the batch held no sloppy phrase), under the CALLER's query indices whatever sub-batches the call ran
+ * internally; n_queries at most the queries of that call.  Waits for the batch like tq_last_batch_match_counts.
+ * Non-zero = that query's rows / count are not to be trusted.  After a host-output call returned TQ_ERR_UNSUPPORTED for an
+ * overflow the words stay readable: the error names the first such query, these words every one. */
+int tq_last_batch_slop_overflows(tq_segment *seg, uint32_t *out, uint32_t n_queries);
 
 /* ---- doc sets ----
  * replaces: Weight::for_each_no_score -> SegmentCollector::collect_block with the alive filter of
@@ -724,6 +773,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_ALL 0x8000u          /* all_kernel (ALL-BASED queries: TQ_TERM_ALL clauses, over bitmap words) */
 #define TQ_KERNEL_DOCSET_TREE 0x10000u /* docset_tree_bits_kernel (tq_docset_batch*, option "docset_trees": phrases and nested queries as match bits) */
 #define TQ_KERNEL_DOCSET_TREE_SCORE 0x20000u /* docset_tree_score_kernel (tq_docset_scored_batch*, option "docset_score_trees": the scores of such rows) */
+#define TQ_KERNEL_PHRASE_SLOP 0x40000u /* phrase_slop_kernel / phrase_slop_bits_kernel (TQ_MODE_PHRASE with slop > 0, over bitmap words) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py

@@ -25,7 +25,9 @@ typedef struct tqh_term_info {
 /* mode: the values of enum tq_mode (tantivy_amd.h) —
  *       TQ_MODE_AND (0) = BooleanQuery of Must term clauses, TQ_MODE_OR (1) = BooleanQuery of
  *       Should term clauses, TQ_MODE_PHRASE (2) = PhraseQuery (offsets 0..n unless phrase_offsets
- *       given), TQ_MODE_BOOL (3) = BooleanQuery with per-term occurs (0 Should, 1 Must,
+ *       given; `slop` as PhraseQuery::set_slop: scoring calls count matches, Count and doc sets test
+ *       existence, and the two verdicts differ as in the reference — tantivy_amd.h "Sloppy phrases",
+ *       the overflow contract included), TQ_MODE_BOOL (3) = BooleanQuery with per-term occurs (0 Should, 1 Must,
  *       2 MustNot); terms sharing a clause_of value form one nested query: a union of its terms
  *       (`+a +(b OR c)`) or, with nested_occurs, a BooleanQuery with an occur per term
  *       (`+a +(+b -c)`: clause_of {0,1,1}, occurs {1,1,1}, nested_occurs {255,1,2}; 255 / NULL =
@@ -49,6 +51,8 @@ typedef struct tqh_query {
   const uint8_t *occurs;
   const uint8_t *clause_of;
   uint32_t min_should_match;
+  uint32_t slop; /* TQ_MODE_PHRASE: PhraseQuery::set_slop (tantivy_amd.h "Sloppy phrases"); any other mode: 0.  Sits in what
+                    was padding: sizeof(tqh_query) is unchanged, and callers must zero the struct */
   const float *boosts; /* per term: the TermQuery is wrapped in BoostQuery(boost) (boost_query.rs);
                           PHRASE: boosts[0] wraps the PhraseQuery; NULL = 1 */
   const uint8_t *nested_occurs; /* TQ_MODE_BOOL: occur of a term inside its clause_of group (read for

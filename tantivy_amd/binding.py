@@ -30,6 +30,7 @@ class TqQuery(C.Structure):
                 ("mode", C.c_uint8), ("phrase_offsets", C.POINTER(C.c_uint32)),
                 ("k", C.c_uint32), ("occurs", C.POINTER(C.c_uint8)),
                 ("clause_of", C.POINTER(C.c_uint8)), ("min_should_match", C.c_uint32),
+                ("slop", C.c_uint32),  # TQ_MODE_PHRASE: PhraseQuery::set_slop (fills what was padding: the size is unchanged)
                 ("nested_occurs", C.POINTER(C.c_uint8)), ("clause_min_should", C.POINTER(C.c_uint8)),
                 ("atom_of", C.POINTER(C.c_uint8))]
 
@@ -59,11 +60,13 @@ KERNEL_DOCSET_SCORE = 0x4000
 KERNEL_ALL = 0x8000
 KERNEL_DOCSET_TREE = 0x10000
 KERNEL_DOCSET_TREE_SCORE = 0x20000
+KERNEL_PHRASE_SLOP = 0x40000
+MAX_SLOP, SLOP_CARRY_CAP = 255, 32  # TQ_MAX_SLOP, TQ_SLOP_CARRY_CAP (include/tantivy_amd.h "Sloppy phrases")
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
-                0x20000: "docset_tree_score"}
+                0x20000: "docset_tree_score", 0x40000: "phrase_slop"}
 
 
 def kernel_names(mask):
@@ -112,7 +115,7 @@ class TqhTermInfo(C.Structure):
 class TqhQuery(C.Structure):
     _fields_ = [("mode", C.c_uint8), ("n_terms", C.c_uint32), ("terms", C.POINTER(C.c_uint32)),
                 ("phrase_offsets", C.POINTER(C.c_uint32)), ("occurs", C.POINTER(C.c_uint8)),
-                ("clause_of", C.POINTER(C.c_uint8)), ("min_should_match", C.c_uint32),
+                ("clause_of", C.POINTER(C.c_uint8)), ("min_should_match", C.c_uint32), ("slop", C.c_uint32),
                 ("boosts", C.POINTER(C.c_float)), ("nested_occurs", C.POINTER(C.c_uint8)),
                 ("clause_min_should", C.POINTER(C.c_uint8)), ("atom_of", C.POINTER(C.c_uint8)),
                 ("set_terms", C.POINTER(C.c_uint32)), ("set_starts", C.POINTER(C.c_uint32))]
@@ -135,7 +138,7 @@ EXPORTS = [
     "tq_search_batch_device_opts", "tq_search_batch_device_rows", "tq_merge_topk",
     "tq_merge_topk_device", "tq_copy_to_host_async", "tq_decode_postings", "tq_decode_position_deltas",
     "tq_last_batch_stats", "tq_segment_get_stats", "tq_segment_reserve_columns", "tq_set_option", "tq_segment_set_alive_bitset", "tq_count_batch",
-    "tq_last_batch_match_counts", "tq_last_batch_query_kernels", "tq_encoder_create", "tq_encoder_free", "tq_encode_postings",
+    "tq_last_batch_match_counts", "tq_last_batch_slop_overflows", "tq_last_batch_query_kernels", "tq_encoder_create", "tq_encoder_free", "tq_encode_postings",
     "tq_encode_positions", "tq_encode_postings_device", "tq_encode_positions_device",
     "tq_encoder_last_kernel_ms", "tq_comm_unique_id", "tq_comm_init", "tq_comm_free",
     "tq_comm_info", "tq_allgather_topk",
@@ -219,6 +222,7 @@ def lib():
     L.tq_segment_set_alive_bitset.argtypes = [vp, vp, C.c_size_t]
     L.tq_count_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p]
     L.tq_last_batch_match_counts.argtypes = [vp, u32p, C.c_uint32]
+    L.tq_last_batch_slop_overflows.argtypes = [vp, u32p, C.c_uint32]
     L.tq_docset_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_docset_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, vp, C.c_uint64, vp, vp]
     L.tqh_docset_prepared.argtypes = [vp, u32p, u32p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -620,7 +624,8 @@ class DeviceIndex:
 
     # ---- host-mirror path (Query::weight + Searcher::search)
     def _host_queries(self, queries):
-        """-> (tqh_query array, keep-alive list).  queries: list of (mode, [term ids]), (MODE_PHRASE, [term ids], [offsets]) or
+        """-> (tqh_query array, keep-alive list).  queries: list of (mode, [term ids]), (MODE_PHRASE, [term ids], [offsets]
+        [, slop]) — PhraseQuery::set_slop, include/tantivy_amd.h "Sloppy phrases" — or
         (MODE_BOOL, [term ids], [occurs][, clause_of | None[, min_should_match]]) with occurs in
         {SHOULD, MUST, MUST_NOT}; terms sharing a clause_of value form one nested union.  A trailing
         dict {"boosts": [...]} wraps every term query in BoostQuery(boost); {"nested_occurs": [...]}
@@ -691,6 +696,8 @@ class DeviceIndex:
                 oa = (C.c_uint32 * len(terms))(*[int(o) for o in q[2]])
                 keep.append(oa)
                 qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
+            if mode == MODE_PHRASE and len(q) > 3:  # (MODE_PHRASE, [ids], [offsets] | None, slop)
+                qs[i].slop = int(q[3])
         return qs, keep
 
     def prepare(self, queries):
@@ -970,6 +977,13 @@ class DeviceIndex:
         _check(lib().tq_last_batch_match_counts(self.segment_raw(segment_ord), _u32(out), n))
         return out[:n]
 
+    def last_batch_slop_overflows(self, n, segment_ord=0):
+        """Per query of the last batch: candidate docs of a sloppy phrase whose carried position list went over
+        SLOP_CARRY_CAP (tq_last_batch_slop_overflows; non-zero = that query's rows are not valid)."""
+        out = np.zeros(max(1, n), np.uint32)
+        _check(lib().tq_last_batch_slop_overflows(self.segment_raw(segment_ord), _u32(out), n))
+        return out[:n]
+
     def last_batch_query_kernels(self, n, segment_ord=0):
         """TQ_KERNEL_* bit of every query of the last batch (option "record_query_kernels" set before it)."""
         out = np.zeros(max(1, n), np.uint32)
@@ -1050,6 +1064,8 @@ class DeviceIndex:
                 oa = (C.c_uint32 * len(terms))(*(q[2] if len(q) > 2 and q[2] is not None else range(len(terms))))
                 keep.append(oa)
                 qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
+                if len(q) > 3:  # (MODE_PHRASE, [ids], [offsets] | None, slop)
+                    qs[i].slop = int(q[3])
         return qs, keep
 
     def raw_docset(self, queries, cap, segment_ord=0, guard=0, fill=0xDEADBEEF):
@@ -1117,11 +1133,12 @@ class DeviceIndex:
                                                    d_scores.data_ptr(), int(cap), d_starts.data_ptr(),
                                                    C.c_void_p(stream) if stream else None)
 
-    def raw_search_trees(self, queries, weights, cache, k, opts=None, segment_ord=0):
+    def raw_search_trees(self, queries, weights, cache, k, opts=None, segment_ord=0, return_rc=False):
         """Direct tq_search_batch_opts over the structs raw_docset_scored sends (_raw_scored_queries: atom_of /
         phrase_offsets / clause_min_should included), every query with top-k size k; weights / cache as
         raw_docset_scored takes them; opts = (exhaustive, bound_slack_ppm) or None
-        -> (scores[n, k], docs[n, k], counts[n])."""
+        -> (scores[n, k], docs[n, k], counts[n]); return_rc: (rc, scores, docs, counts) without raising — a sloppy
+        phrase over the carry cap is TQ_ERR_UNSUPPORTED with the other queries' rows written."""
         n = len(queries)
         qs, keep = self._raw_scored_queries(queries, weights, cache, segment_ord)
         for i in range(n):
@@ -1130,8 +1147,11 @@ class DeviceIndex:
         docs = np.zeros((max(1, n), k), np.uint32)
         counts = np.zeros(max(1, n), np.uint32)
         o = TqSearchOpts(int(opts[0]), int(opts[1])) if opts is not None else None
-        _check(lib().tq_search_batch_opts(self.segment_raw(segment_ord), qs, n, k, _f32(scores), _u32(docs), _u32(counts),
-                                          C.byref(o) if o is not None else None))
+        rc = lib().tq_search_batch_opts(self.segment_raw(segment_ord), qs, n, k, _f32(scores), _u32(docs), _u32(counts),
+                                        C.byref(o) if o is not None else None)
+        if return_rc:
+            return rc, scores[:n], docs[:n], counts[:n]
+        _check(rc)
         return scores[:n], docs[:n], counts[:n]
 
     def raw_count(self, queries, weights, cache, segment_ord=0):
@@ -1155,7 +1175,9 @@ class DeviceIndex:
                                                  else range(len(terms))))
                 keep.append(oa)
                 qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
-            if len(q) > 3 and q[3] is not None:  # TQ_MODE_BOOL, as raw_search takes it: occurs, clause_of, minimum
+            if mode == MODE_PHRASE:  # (MODE_PHRASE, [ids], [offsets] | None, slop)
+                qs[i].slop = int(q[3]) if len(q) > 3 else 0
+            elif len(q) > 3 and q[3] is not None:  # TQ_MODE_BOOL, as raw_search takes it: occurs, clause_of, minimum
                 oc = (C.c_uint8 * len(terms))(*q[3])
                 keep.append(oc)
                 qs[i].occurs = C.cast(oc, C.POINTER(C.c_uint8))
@@ -1204,7 +1226,9 @@ class DeviceIndex:
                 oa = (C.c_uint32 * len(terms))(*q[2])
                 keep.append(oa)
                 qs[i].phrase_offsets = C.cast(oa, C.POINTER(C.c_uint32))
-            if len(q) > 3 and q[3] is not None:  # TQ_MODE_BOOL: enum tq_occur
+            if mode == MODE_PHRASE:  # (MODE_PHRASE, [ids], [offsets] | None, slop)
+                qs[i].slop = int(q[3]) if len(q) > 3 else 0
+            elif len(q) > 3 and q[3] is not None:  # TQ_MODE_BOOL: enum tq_occur
                 oc = (C.c_uint8 * len(terms))(*q[3])
                 keep.append(oc)
                 qs[i].occurs = C.cast(oc, C.POINTER(C.c_uint8))

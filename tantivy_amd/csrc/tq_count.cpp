@@ -173,6 +173,7 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
   std::vector<tq_query> eff;
   std::vector<uint8_t> done;
   const tq_query *const given = queries;
+  s->last_batch_slop = false;  // (set again by the doc-set pass, the last one of this call, if it holds a sloppy phrase)
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     if (!query_has_all(given[qi])) continue;
     if (eff.empty()) {
@@ -200,6 +201,17 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
       all_q.push_back(qi);
   }
   if (!eff.empty()) queries = eff.data();
+  // Sloppy phrases (TQ_MODE_PHRASE with slop > 0, tq_phrase_slop.cpp): Count runs the reference's NON-SCORING PhraseScorer,
+  // whose verdict differs from the scoring one — never the scan; the doc-set count pass over their match bits.
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    if (!given[qi].slop) continue;
+    SlopView sv;
+    const int vrc = slop_view(s, given[qi], qi, "tq_count_batch", sv, false);  // (refusals under the caller's index)
+    if (vrc != TQ_OK) return vrc;
+    if (done.empty()) done.assign(n_queries, 0);
+    done[qi] = 1;
+    all_q.push_back(qi);
+  }
   // Queries that name a term set (tq_termset.cpp) are never scanned — a set has no postings to walk: the bitmap kernel
   // whatever "count_bitmap_ratio" says, or — "at least m of n" — the doc-set count pass.
   std::vector<uint8_t> set_q;
@@ -318,14 +330,27 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
     std::vector<tq_query> qs(n);
     for (uint32_t i = 0; i < n; ++i) qs[i] = given[all_q[i]];
     std::vector<uint64_t> starts((size_t)n + 1u);
-    const int rc = docset_batch(s, qs.data(), n, nullptr, nullptr, 0, starts.data(), false, false, nullptr, true);
+    // (sloppy phrases are named, and their overflow words indexed, by the caller's query: all_q)
+    const int rc = docset_batch(s, qs.data(), n, nullptr, nullptr, 0, starts.data(), false, false, nullptr, true, all_q.data(), n_queries);
+    // a carried list over the cap (the verdict comes behind the count pass: `starts` is filled): the counts of the other
+    // queries are written and valid, the words of this batch stay readable (tq_last_batch_slop_overflows)
+    bool overflowed = false;
+    if (rc == TQ_ERR_UNSUPPORTED && s->last_batch_slop) {
+      const std::string err = g_last_error;
+      std::vector<uint32_t> over(n_queries);
+      HIP_TRY(hipMemcpy(over.data(), s->d_slop_over.p, (size_t)n_queries * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      for (uint32_t w : over) overflowed = overflowed || w != 0u;
+      g_last_error = err;
+    }
+    for (uint32_t i = 0; (rc == TQ_OK || overflowed) && i < n; ++i) out_counts[all_q[i]] = (uint32_t)(starts[i + 1u] - starts[i]);
+    s->slop_over_words = n_queries;
     if (rc != TQ_OK) return rc;
-    for (uint32_t i = 0; i < n; ++i) out_counts[all_q[i]] = (uint32_t)(starts[i + 1u] - starts[i]);
     algo_bytes += s->stats.algorithmic_bytes;
-    mask |= TQ_KERNEL_DOCSET;
+    mask |= TQ_KERNEL_DOCSET | (s->stats.kernel_mask & (TQ_KERNEL_PHRASE_SLOP | TQ_KERNEL_DOCSET_TREE));
   }
   s->stats.kernel_mask = mask;
   s->stats.algorithmic_bytes = algo_bytes;
+  s->slop_over_words = n_queries;  // (the sub-batches above counted their own queries)
   return TQ_OK;
 }
 

@@ -154,6 +154,7 @@ struct SubBatch {  // consecutive whole queries whose lists without a bitmap and
   uint32_t q0 = 0, q1 = 0;
   size_t wg0 = 0, wg1 = 0;  // its part of the scatter work list
   uint32_t t0 = 0, t1 = 0;  // ... and of the tree records (tq_docset_tree.hip)
+  uint32_t s0 = 0, s1 = 0;  // ... and of the sloppy phrases' records (tq_phrase_slop.hip)
   bool any_phrase = false;  // some tree of its queries has a phrase atom
   uint32_t n_temp = 0;
   bool score_blocks = false;  // some scoring list of its queries is reached by the block search
@@ -163,7 +164,12 @@ enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
 }  // namespace
 
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
-                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only) {
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only,
+                 const uint32_t *caller_q, uint32_t n_caller) {
+  // (tq_count_batch hands over a sub-array of its batch: what this call says about a sloppy phrase — refusals, the
+  // overflow words — it says under the CALLER's index)
+  auto named = [&](uint32_t qi) { return caller_q ? caller_q[qi] : qi; };
+  const uint32_t n_over_words = caller_q ? n_caller : n_queries;
   const char *const fn = count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
                                 : (device_out ? "tq_docset_batch_device" : "tq_docset_batch");
   // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
@@ -196,10 +202,30 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   std::vector<uint32_t> tree_q;     // the queries that take the tree path (option "docset_trees"), ascending
   std::vector<TqdTreeQuery> tqs;    // ... and their records, in the same order
   const bool trees_on = count_only ? false : scored ? s->opt.docset_score_trees != 0 : s->opt.docset_trees != 0;
+  // Sloppy phrases (TQ_MODE_PHRASE with slop > 0, tq_phrase_slop.cpp): the existence verdict of the reference's non-scoring
+  // PhraseScorer as match bits in a result slot of their own, like a tree's: phrase_slop_bits_kernel stores every word of
+  // it, once (a query the planner found empty: zeros).  Taken by
+  // the unscored calls under "docset_trees" and by the count pass of tq_count_batch.
+  std::deque<SlopView> slop_views;
+  std::vector<uint32_t> slop_qi;         // the sloppy phrases of the batch, ascending
+  std::vector<TqdSlopQuery> slop_qs;     // ... and their records, in the same order
+  s->last_batch_slop = false;
+  s->slop_over_words = n_over_words;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
     const char *why = "";
     FlatClauses fc;
     const tq_query &q = queries[qi];
+    if (q.slop) {
+      slop_views.emplace_back();
+      const int vrc = slop_view(s, q, named(qi), fn, slop_views.back(), false);
+      if (vrc != TQ_OK) return vrc;
+      if (scored)
+        return fail(TQ_ERR_UNSUPPORTED, "%s: query %u: scored doc sets of sloppy phrases stay on the CPU in this version", fn, named(qi));
+      if (!trees_on && !count_only)
+        return fail(TQ_ERR_UNSUPPORTED, "%s: query %u is a phrase: doc sets of phrases and nested queries stay on the CPU (option \"docset_trees\")", fn, named(qi));
+      slop_qi.push_back(qi);
+      continue;
+    }
     {  // a term set in a phrase, inside a nested query, or released: refused whatever the tree options say
       bool names_set = false;
       const int src = check_set_query(s, q, qi, fn, &names_set);
@@ -241,7 +267,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     for (uint32_t m = 0; names_field && m < sqs[qi].n_lists; ++m) score_fields = score_fields || (sqs[qi].shift[m] >> 8) != 0u;
     algo_bytes += (uint64_t)sqs[qi].n_lists * n_words * 8u;
   }
-  if (!tree_q.empty()) {
+  if (!tree_q.empty() || !slop_qi.empty()) {
     // every list of a tree as a bitmap + tf bytes, a phrase term's position directory: the list's own tables or the probe
     // pool's, built now; a probe batch like a search batch's, so that no list of this call is evicted for another
     probe_begin_batch(s);
@@ -253,10 +279,24 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       const int prc = build_tree_query_probe_tables(s, views.back().q, &built);
       if (prc != TQ_OK) return prc;
     }
+    for (const SlopView &sv : slop_views) {
+      const int prc = build_tree_query_probe_tables(s, sv.v.q, &built);
+      if (prc != TQ_OK) return prc;
+    }
     if (built) s->share_span_terms = ~(size_t)0;
     update_table_span(s);
-    if (!s->share_span_ok || !s->opt.use_dense) return fail_tree_tables(s, tree_q[0]);
+    if (!s->share_span_ok || !s->opt.use_dense)
+      return fail_tree_tables(s, named(std::min(tree_q.empty() ? ~0u : tree_q[0], slop_qi.empty() ? ~0u : slop_qi[0])));
     tqs.resize(tree_q.size());
+    slop_qs.resize(slop_qi.size());
+    for (size_t k = 0; k < slop_qi.size(); ++k) {
+      // (named: the query in refusals, and its overflow word; the lists' bits once + the result word written and read back)
+      const int prc = plan_slop_query(s, slop_views[k].v.q, named(slop_qi[k]), queries[slop_qi[k]].slop, slop_qs[k], algo_bytes, true);
+      if (prc != TQ_OK) return prc;
+      TqkDocsetQuery &dq = dqs[slop_qi[k]];  // to the passes: one Must list that is bits in scratch
+      dq = TqkDocsetQuery{};
+      dq.n_terms = dq.narrow = dq.clause_end = 1u;
+    }
     for (size_t i = 0; i < tree_q.size(); ++i) {
       uint64_t qbytes = 0;
       const int prc = plan_tree_query(s, views[i].q, tree_q[i], tqs[i], qbytes, s->share_table_lo);
@@ -286,10 +326,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   uint32_t max_sub_temp = 0, max_sub_n = 0;
   uint32_t n_slots = 0;  // slots of the sub-batch so far: its lists without a bitmap and its trees' results
   uint32_t n_trees = 0;  // tree queries so far
+  uint32_t n_slops = 0;  // sloppy phrases so far
   auto close_sub = [&](uint32_t q1) {
     cur.q1 = q1;
     cur.wg1 = wgs.size();
     cur.t1 = n_trees;
+    cur.s1 = n_slops;
     cur.n_temp = n_slots;
     for (uint32_t qi = cur.q0; scored && qi < q1; ++qi)
       for (uint32_t m = 0; m < sqs[qi].n_lists; ++m)
@@ -301,6 +343,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     cur.q0 = q1;
     cur.wg0 = wgs.size();
     cur.t0 = n_trees;
+    cur.s0 = n_slops;
     slot.clear();
     n_slots = 0;
   };
@@ -311,6 +354,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       cur.any_phrase = cur.any_phrase || tqs[n_trees].has_phrase;
       tqs[n_trees++].part_start = n_slots;
       dq.dense[0] = (const uint2 *)(uintptr_t)n_slots++;  // (the slot; the pointer below)
+      continue;
+    }
+    if (n_slops < slop_qi.size() && slop_qi[n_slops] == qi) {  // a sloppy phrase: one result slot too
+      if (qi > cur.q0 && (n_slots + 1u > max_temp || qi - cur.q0 >= max_sub_queries)) close_sub(qi);
+      slop_qs[n_slops++].part_start = n_slots;
+      dq.dense[0] = (const uint2 *)(uintptr_t)n_slots++;
       continue;
     }
     uint32_t fresh[TQ_MAX_TERMS], n_fresh = 0;
@@ -342,7 +391,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   }
   s->stats = tq_batch_stats{};
   s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
-                         (scored && !tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u);
+                         (scored && !tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u) | (slop_qs.empty() ? 0u : TQ_KERNEL_PHRASE_SLOP);
   s->stats.algorithmic_bytes = algo_bytes;
   s->stats_pending = false;
   s->last_batch_queries = 0;
@@ -354,7 +403,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     return TQ_OK;
   }
-  if (!wgs.empty() || scored || !tqs.empty()) {  // (the scoring pass reads term records: saturated tfs, the block search; a phrase atom: positions)
+  if (!wgs.empty() || scored || !tqs.empty() || !slop_qs.empty()) {  // (the scoring pass reads term records: saturated tfs, the block search; a phrase atom: positions)
     const int src = sync_terms(s, s->stream);
     if (src != TQ_OK) return src;
   }
@@ -365,8 +414,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   static_assert(sizeof(TqdTreeQuery) % sizeof(uint32_t) == 0, "the map stands right behind the records");
   const size_t tree_map_bytes = scored ? tqs.size() * sizeof(uint32_t) : 0u;
   const size_t max_entries = (size_t)max_sub_n * n_tiles;
-  int rc = s->h_docset.ensure(q_bytes + wg_bytes + sq_bytes + cache_bytes + tree_bytes + tree_map_bytes);
-  if (rc == TQ_OK && tree_bytes) rc = s->d_docset_trees.ensure(tree_bytes + tree_map_bytes);
+  // (the sloppy phrases' records ride behind the tree records and their map, 64-byte aligned, in both buffers)
+  const size_t slop_off = (tree_bytes + tree_map_bytes + 63u) & ~(size_t)63, slop_bytes = slop_qs.size() * sizeof(TqdSlopQuery);
+  const size_t tree_blob_bytes = slop_bytes ? slop_off + slop_bytes : tree_bytes + tree_map_bytes;
+  int rc = s->h_docset.ensure(((q_bytes + wg_bytes + sq_bytes + cache_bytes + 63u) & ~(size_t)63) + tree_blob_bytes + 64u);
+  if (rc == TQ_OK && tree_blob_bytes) rc = s->d_docset_trees.ensure(tree_blob_bytes);
+  if (rc == TQ_OK && slop_bytes) rc = s->d_slop_over.ensure((size_t)n_over_words * sizeof(uint32_t));
   if (rc == TQ_OK && scored) rc = s->d_docset_squeries.ensure(sq_bytes);
   if (rc == TQ_OK && scored) rc = s->d_docset_caches.ensure(std::max<size_t>(cache_bytes, 256u * sizeof(float)));
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
@@ -398,15 +451,20 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     HIP_TRY(hipMemcpyAsync(s->d_docset_squeries.p, h_sq, sq_bytes, hipMemcpyHostToDevice, st));
     if (cache_bytes) HIP_TRY(hipMemcpyAsync(s->d_docset_caches.p, h_sq + sq_bytes, cache_bytes, hipMemcpyHostToDevice, st));
   }
-  if (tree_bytes) {
+  if (tree_blob_bytes) {
     uint8_t *const h_tq = (uint8_t *)s->h_docset.p + q_bytes + wg_bytes + sq_bytes + cache_bytes;
-    memcpy(h_tq, tqs.data(), tree_bytes);
+    if (tree_bytes) memcpy(h_tq, tqs.data(), tree_bytes);
     if (tree_map_bytes) {
       uint32_t *const map = (uint32_t *)(h_tq + tree_bytes);
       for (const SubBatch &sb : subs)
         for (uint32_t t = sb.t0; t < sb.t1; ++t) map[t] = tree_q[t] - sb.q0;
     }
-    HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_bytes + tree_map_bytes, hipMemcpyHostToDevice, st));
+    if (slop_bytes) memcpy(h_tq + slop_off, slop_qs.data(), slop_bytes);
+    HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_blob_bytes, hipMemcpyHostToDevice, st));
+  }
+  if (slop_bytes) {  // the overflow words, one per query of the batch (tq_last_batch_slop_overflows)
+    HIP_TRY(hipMemsetAsync(s->d_slop_over.p, 0, (size_t)n_over_words * sizeof(uint32_t), st));
+    s->last_batch_slop = true;
   }
 
   uint64_t *const d_starts = device_out ? out_starts : (uint64_t *)s->d_docset_starts.p;
@@ -430,6 +488,21 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       tp.any_phrase = sb.any_phrase ? 1u : 0u;
       const hipError_t te = tqk_launch_docset_tree(tp, st);
       if (te != hipSuccess) return fail(TQ_ERR_HIP, "doc-set tree launch: %s", hipGetErrorString(te));
+    }
+    if ((stages & DS_SCATTER) && sb.s1 > sb.s0) {  // its sloppy phrases' match bits: every word of their slots is stored, once
+      TqkPhraseSlopParams pp{};
+      pp.seg = s->dseg;
+      pp.terms = s->d_terms;
+      pp.queries = (const TqdSlopQuery *)((const uint8_t *)s->d_docset_trees.p + slop_off) + sb.s0;
+      pp.table_base = (const uint8_t *)s->share_table_lo;
+      pp.overflow = (uint32_t *)s->d_slop_over.p;
+      pp.bits = (uint32_t *)s->d_count_bits.p;
+      pp.n_queries = sb.s1 - sb.s0;
+      pp.n_words = n_words;
+      pp.words_per_list = words_per_list;
+      for (uint32_t k = sb.s0; k < sb.s1; ++k) (slop_qs[k].n_terms > 2u ? pp.any_carry : pp.any_pair) = 1u;
+      const hipError_t pe = tqk_launch_phrase_slop_bits(pp, st);
+      if (pe != hipSuccess) return fail(TQ_ERR_HIP, "sloppy phrase launch: %s", hipGetErrorString(pe));
     }
     TqkDocsetParams p{};
     p.queries = (const TqkDocsetQuery *)s->d_docset_queries.p + sb.q0;
@@ -537,15 +610,25 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   HIP_TRY(hipStreamSynchronize(st));
   const uint64_t total = out_starts[n_queries];
   s->stats.matches = total;
-  if (count_only) return TQ_OK;  // (tq_count_batch: the row starts are the counts)
+  // host outputs wait for the device anyway: a sloppy phrase whose carried list went over the cap is reported, the rows
+  // of the other queries are written and valid
+  auto slop_verdict = [&]() -> int {
+    if (slop_qs.empty()) return TQ_OK;
+    std::vector<uint32_t> over(n_over_words);
+    HIP_TRY(hipMemcpy(over.data(), s->d_slop_over.p, (size_t)n_over_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return slop_overflow_verdict(fn, over.data(), n_over_words);
+  };
+  if (count_only) return slop_verdict();  // (tq_count_batch: the row starts are the counts)
   s->stats.algorithmic_bytes += (scored ? 9u : 4u) * total;
   if (total > out_cap)
     return fail(TQ_ERR_INVALID, "%s: the batch has %llu docs, out_cap is %llu (out_starts is filled: retry with that many)", fn,
                 (unsigned long long)total, (unsigned long long)out_cap);
-  if (!total) return TQ_OK;
+  if (!total) return slop_verdict();
   rc = s->d_docset_docs.ensure((size_t)total * sizeof(uint32_t));
   if (rc == TQ_OK && scored) rc = s->d_docset_scores.ensure((size_t)total * sizeof(float));
   if (rc != TQ_OK) return rc;
+  if (subs.size() > 1 && !slop_qs.empty())  // (evaluated again: the overflow words count every candidate once)
+    HIP_TRY(hipMemsetAsync(s->d_slop_over.p, 0, (size_t)n_over_words * sizeof(uint32_t), st));
   for (const SubBatch &sb : subs) {
     // one sub-batch: its tables and bits are still there; several: each is evaluated again (the scratch held the last one's)
     rc = enqueue(sb, subs.size() == 1 ? DS_WRITE : (DS_SCATTER | DS_COUNT | DS_WRITE), (uint32_t *)s->d_docset_docs.p,
@@ -557,7 +640,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   HIP_TRY(hipStreamSynchronize(st));
   if (s->d_docset_docs.cap > ((size_t)256 << 20)) s->d_docset_docs.release();  // (a large result is not kept as scratch)
   if (s->d_docset_scores.cap > ((size_t)256 << 20)) s->d_docset_scores.release();
-  return TQ_OK;
+  return slop_verdict();
 }
 
 }  // namespace tqi

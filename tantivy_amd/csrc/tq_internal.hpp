@@ -355,6 +355,12 @@ struct tq_segment {
   bool share_span_ok = true;
   bool lnorm_off = false;  // a leader-norm table came to lie outside that span (build_lnorm): no more of them are built
   uint32_t last_batch_queries = 0;
+  // sloppy phrases (tq_phrase_slop.cpp): per query of the batch, candidate docs whose carried list went over the cap
+  DevBuf d_slop_over;
+  bool last_batch_slop = false;  // the last batch held a sloppy phrase: d_slop_over is its overflow words
+  uint32_t slop_over_words = 0;  // queries of the caller's last search / doc-set / count batch: d_slop_over holds one word
+                                 // for each when last_batch_slop (tq_last_batch_slop_overflows; else every word reads 0)
+  std::vector<uint32_t> slop_over_host;  // ... as search_batch_host left them under CallOpts::defer_slop_verdict
   std::vector<uint32_t> last_query_kernel;  // option "record_query_kernels": TQ_KERNEL_* of every query of the last batch
   PinnedBuf h_stage, h_out;
   // timing: a ring of event quadruples, one per batch, so that pipelined batches (no host sync
@@ -517,6 +523,7 @@ struct Group {
   std::vector<uint32_t> tile_cost;  // per query, cost units per tile
   std::vector<TqdTreeQuery> tree;   // kGTree: the nested boolean queries' descriptors (tq_tree.hip), one per query
   std::vector<TqdAllQuery> all;     // kGAll: the ALL-BASED queries' descriptors (tq_all.hip), one per query
+  std::vector<TqdSlopQuery> slop;   // kGSlop: the sloppy phrases' descriptors (tq_phrase_slop.hip), one per query
   uint32_t total_tiles = 0, n_chunks = 0, max_k = 1;
   uint64_t list_entries = 0;  // term-major / doc-major groups: 8-byte entries of the group's result lists
   int kpl = 1;
@@ -532,6 +539,7 @@ struct Group {
     tile_cost.clear();
     tree.clear();
     all.clear();
+    slop.clear();
     total_tiles = 0;
     n_chunks = 0;
     list_entries = 0;
@@ -578,7 +586,8 @@ enum GroupId : int {
   kGBShare = 9,    // boolean queries through the shared-intersection launch
   kGTree = 10,     // nested boolean queries over bitmaps (tq_tree.hip)
   kGAll = 11,      // ALL-BASED queries (TQ_TERM_ALL clauses) over bitmaps (tq_all.hip)
-  kNGroups = 12
+  kGSlop = 12,     // TQ_MODE_PHRASE with slop > 0 over bitmaps (tq_phrase_slop.hip)
+  kNGroups = 13
 };
 // per group: the TQ_MODE_* of its descriptors; whether it writes result lists (part_start / n_parts count 8-byte
 // entries) rather than per-tile partials; its TQ_KERNEL_* bit (the union group's: group_kernel_bit)
@@ -588,7 +597,7 @@ constexpr GroupTraits kGroupTraits[kNGroups] = {
     {TQ_MODE_AND, false, TQ_KERNEL_AND},       {TQ_MODE_OR, false, TQ_KERNEL_BOOL},  {TQ_MODE_OR, true, TQ_KERNEL_USHARE},
     {TQ_MODE_PHRASE, false, TQ_KERNEL_PHRASE_SWEEP}, {TQ_MODE_OR, true, TQ_KERNEL_XUNION}, {TQ_MODE_AND, true, TQ_KERNEL_ASHARE},
     {TQ_MODE_OR, true, TQ_KERNEL_BSHARE},      {TQ_MODE_OR, false, TQ_KERNEL_TREE},
-    {TQ_MODE_OR, false, TQ_KERNEL_ALL}};
+    {TQ_MODE_OR, false, TQ_KERNEL_ALL},        {TQ_MODE_OR, false, TQ_KERNEL_PHRASE_SLOP}};
 inline uint32_t group_kernel_bit(int gi, bool or_windows) {
   return gi == kGUnion && or_windows ? TQ_KERNEL_OR_WINDOWS : kGroupTraits[gi].kernel;
 }
@@ -805,6 +814,12 @@ struct CallOpts {
   bool exhaustive;
   float bound_slack;
   bool no_ashare = false, no_bshare = false;  // (internal) this call keeps intersections / boolean queries off the shared launch
+  // (internal) pinned host words, one per query: where a batch that holds a sloppy phrase copies its overflow words
+  // behind its last kernel (tq_phrase_slop.cpp); a batch without one leaves them alone (tq_segment::last_batch_slop)
+  uint32_t *h_slop_over = nullptr;
+  // (internal, search_batch_host) a sloppy phrase over the carry cap is not an error of the call: the overflow words are
+  // left in tq_segment::slop_over_host for the caller to judge (tq_submit: only that query's ticket fails)
+  bool defer_slop_verdict = false;
 };
 // ---- tq_api.cpp: the segment's stream
 int order_after_last_batch(tq_segment *s, hipStream_t st);
@@ -995,7 +1010,10 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
 // hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used;
 // count_only (host outputs): the count pass and the row starts alone, no doc is written (tq_count_batch's ALL-BASED queries)
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
-                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false);
+                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false,
+                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0);
+// (caller_q / n_caller — tq_count_batch, which hands over a sub-array of its n_caller queries: query qi of this call is
+// the caller's caller_q[qi]; sloppy phrases are named, and their overflow words indexed, by that)
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
 // Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the
@@ -1006,6 +1024,24 @@ struct TreeView {
   float weights[TQ_MAX_TERMS];
 };
 void docset_tree_view(const tq_query &q, TreeView &v, bool scored = false);  // (q.n_terms <= TQ_MAX_TERMS)
+// ---- tq_phrase_slop.cpp: TQ_MODE_PHRASE with slop > 0
+// A sloppy phrase as the tree planner takes it: the one-atom tree of docset_tree_view with the terms — and their offsets
+// — in COST order (doc freq ascending, ties in phrase order), the order the reference's Intersection walks the lists in.
+struct SlopView {
+  TreeView v;
+  tq_term_handle terms[TQ_MAX_TERMS];
+  uint32_t offsets[TQ_MAX_TERMS];
+};
+// Validates query qi (slop != 0) and builds its view: TQ_ERR_INVALID a slop outside TQ_MODE_PHRASE, a malformed phrase,
+// TQ_TERM_ALL or a term set in it; TQ_ERR_UNSUPPORTED slop > TQ_MAX_SLOP, more than 8 terms, a term of a field != 0.
+// scored: weights[0] is kept (finite), else unit weights.
+int slop_view(const tq_segment *s, const tq_query &q, uint32_t qi, const char *fn, SlopView &out, bool scored);
+// The view's descriptor (plan_tree_query places the lists; n_terms 0: an absent term, nothing matches).  result_bitmap:
+// the launch writes match bits that are read back (doc sets, counts).  qbytes: the HBM MODEL of the header, += .
+int plan_slop_query(tq_segment *s, const tq_query &view, uint32_t qi, uint32_t slop, TqdSlopQuery &sq, uint64_t &qbytes, bool result_bitmap);
+// TQ_ERR_UNSUPPORTED naming the first query with a non-zero overflow word, or TQ_OK
+int slop_overflow_verdict(const char *fn, const uint32_t *over, uint32_t n_queries);
+int slop_overflow_fail(const char *fn, uint32_t qi, uint32_t docs);
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);
 int build_share_plan(tq_segment *s, Group &g, PlanScratch &ps);
@@ -1027,6 +1063,8 @@ int fail_tree_tables(const tq_segment *s, uint32_t qi);  // "use_dense" off, or 
 int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *d_out_scores, uint32_t *d_out_docs, uint32_t *d_out_counts, void *hip_stream,
                       const CallOpts &co, uint32_t *d_out_segment_ords = nullptr, uint32_t segment_ord = 0);
+// (a sloppy phrase over the carry cap: TQ_ERR_UNSUPPORTED naming the first such query, the rows written — or, under
+// CallOpts::defer_slop_verdict, TQ_OK with the overflow words in tq_segment::slop_over_host)
 int search_batch_host(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                       float *out_scores, uint32_t *out_docs, uint32_t *out_counts, const CallOpts &co);
 // The same in two halves (the submit queue: the next coalesced batch is planned and enqueued while this one runs):
@@ -1035,6 +1073,8 @@ int search_batch_host(tq_segment *s, const tq_query *queries, uint32_t n_queries
 // (no lock needed) and leaves the rows readable at out.p, out.p + o_docs, out.p + o_counts.
 struct HostBatchSlot {
   PinnedBuf out;
+  size_t o_slop_over = 0;  // the batch's overflow words behind the rows (read when any_slop)
+  bool any_slop = false;
   hipEvent_t done = nullptr, done_blocking = nullptr;  // the batch's last kernel: waited for spinning / asleep
   bool blocking = false;                               // ... which of the two this batch recorded
   size_t o_docs = 0, o_counts = 0;

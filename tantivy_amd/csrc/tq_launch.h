@@ -244,6 +244,42 @@ struct TqkDocsetTreeParams {
 };
 hipError_t tqk_launch_docset_tree(const TqkDocsetTreeParams &p, hipStream_t st);
 
+// ---- sloppy phrases (tq_phrase_slop.hip): TQ_MODE_PHRASE with slop > 0 over the lists' bitmaps, in the tree route's
+// geometry (tiles of TQK_TREE_TILE_WORDS words, one partial top-k list per (query, tile), tqk_tree_tiles).  Lists in
+// COST order (doc freq ascending, ties in phrase order): the order the reference walks them in.
+constexpr uint32_t TQK_SLOP_MAX_TERMS = TQK_TREE_PHRASE_TERMS;
+constexpr uint32_t TQK_SLOP_CARRY_CAP = 32;  // = TQ_SLOP_CARRY_CAP (tantivy_amd.h; asserted in tq_phrase_slop.cpp)
+struct TqdSlopQuery {                        // 192 bytes
+  uint32_t n_terms;                          // 2..8; 0: the planner found the query empty (an absent term)
+  uint32_t k, cache_idx;
+  uint32_t part_start;                       // first partial top-k list (one per tile); doc sets: the query's result slot
+  uint32_t slop;                             // 1..255
+  uint32_t weight_bits;                      // (float) the phrase's weight: (1 + k1) * boost * sum of idfs
+  uint32_t out_q;                            // query of the BATCH: its overflow word
+  uint32_t pad_;
+  uint32_t dense_off[TQK_SLOP_MAX_TERMS];    // bitmap + rank directory / byte-wide tfs / position directory of the list,
+  uint32_t tf8_off[TQK_SLOP_MAX_TERMS];      // as offsets from TqkPhraseSlopParams::table_base in 8-byte units
+  uint32_t dir_off[TQK_SLOP_MAX_TERMS];
+  uint32_t phrase_off[TQK_SLOP_MAX_TERMS];   // max_offset - term_offset (phrase_scorer.rs:372-385)
+  uint32_t handle[TQK_SLOP_MAX_TERMS];       // term handle (positions; saturated tf bytes read the packed value)
+};
+static_assert(sizeof(TqdSlopQuery) == 192, "TqdSlopQuery is uploaded as raw bytes");
+struct TqkPhraseSlopParams {
+  TqdSegment seg;
+  const TqdTerm *terms;
+  const TqdSlopQuery *queries;
+  const float *caches;          // scoring launch
+  const TqkSinks *sinks;        // scoring launch
+  const uint8_t *table_base;
+  uint32_t *overflow;           // [batch queries] candidate docs whose carried list went over the cap (zeroed by the caller)
+  uint32_t *bits;               // bits launch: the scratch's result bitmaps, words_per_list 32-bit words each
+  uint32_t n_queries, n_words, words_per_list;
+  uint32_t any_pair;            // some query has 2 lists or is empty / some has 3 or more: one launch per instantiation,
+  uint32_t any_carry;           // so that a 2-list query never pays for the carried lists
+};
+hipError_t tqk_launch_phrase_slop(const TqkPhraseSlopParams &p, int kpl, hipStream_t st);
+hipError_t tqk_launch_phrase_slop_bits(const TqkPhraseSlopParams &p, hipStream_t st);
+
 // ---- ALL-BASED queries (tq_all.hip): a flat query whose AllQuery clauses (TQ_TERM_ALL) make every doc a candidate
 // (tq_all.cpp).  Lists: the Should lists in score-sum order (clause by clause, query order), then the MustNot lists.
 constexpr uint32_t TQK_ALL_TILE_WORDS = 2048;  // bitmap words (65 536 docs) per (query, tile) wavefront

@@ -46,6 +46,8 @@ struct Batch {
   uint32_t n_all_queries = 0;  // ALL-BASED queries (TQ_TERM_ALL clauses that make every doc a candidate): counted by strip_all_clauses
   const uint8_t *set_q = nullptr;  // per query: it names a term set (tq_termset.cpp) and is routed to the tree group; null: no
                                    // query of the batch does (flagged and counted by strip_all_clauses)
+  const uint32_t *slop_q = nullptr;  // per query: its slop (a sloppy phrase, replaced by its one-atom tree view in COST order:
+                                     // tq_phrase_slop.cpp) or 0; null: no query of the batch has one
   bool and_probe = false, ashare_on = false, ashare_and = false;
   uint32_t and_tile_cap = TQD_AND_TILE, dense_min_queries = 1;
   uint64_t unique_bytes = 0, dense_ratio = 0;
@@ -546,6 +548,21 @@ int route_tree(const Batch &b, uint32_t qi, Route &r, Group &tree_group) {
   return TQ_OK;
 }
 
+// A TQ_MODE_PHRASE query with slop > 0 (its view: strip_all_clauses): a launch group of its own, tq_phrase_slop.hip.
+int route_slop(const Batch &b, uint32_t qi, Route &r, Group &slop_group) {
+  if (!b.s->share_span_ok || !b.s->opt.use_dense) return fail_tree_tables(b.s, qi);
+  TqdSlopQuery sq;
+  r.qbytes = 0;
+  const int rc = plan_slop_query(b.s, b.queries[qi], qi, b.slop_q[qi], sq, r.qbytes, false);
+  if (rc != TQ_OK) return rc;
+  sq.cache_idx = r.dq.cache_idx;
+  slop_group.slop.push_back(sq);
+  r.dq.n_terms = sq.n_terms;
+  r.n_tiles = 0;
+  r.group = kGSlop;
+  return TQ_OK;
+}
+
 // A query whose AllQuery clauses make every doc a candidate (tq_all.cpp: ALL-BASED; strip_all_clauses has replaced the
 // EMPTY and PLAIN ones by their views): the Should lists in score-sum order, then the MustNot lists, over bitmaps.
 int route_all(const Batch &b, uint32_t qi, Route &r, Group &all_group) {
@@ -746,7 +763,9 @@ int plan_query(const Batch &b, uint32_t qi, Group *groups, RouteTotals &t) {
   r.dq.cache_idx = b.ps->q_cache[qi];
   r.qbytes = 8ull * q.k;
   const bool any_absent = std::find(q.terms, q.terms + q.n_terms, TQ_TERM_ABSENT) != q.terms + q.n_terms;
-  if (b.n_all_queries && query_has_all(q)) {
+  if (b.slop_q && b.slop_q[qi]) {
+    rc = route_slop(b, qi, r, groups[kGSlop]);
+  } else if (b.n_all_queries && query_has_all(q)) {
     rc = route_all(b, qi, r, groups[kGAll]);
   } else if (b.set_q && b.set_q[qi]) {  // (a TQ_MODE_BOOL view, whatever the caller's mode was)
     rc = route_tree(b, qi, r, groups[kGTree]);
@@ -817,6 +836,7 @@ int route_in_slabs(Batch &b, uint32_t q_slabs) {
     for (uint32_t sb = 0; sb < q_slabs; ++sb) g.max_k = std::max(g.max_k, qs[sb].groups[gi].max_k);
     for (uint32_t sb = 0; sb < q_slabs; ++sb) g.tree.insert(g.tree.end(), qs[sb].groups[gi].tree.begin(), qs[sb].groups[gi].tree.end());
     for (uint32_t sb = 0; sb < q_slabs; ++sb) g.all.insert(g.all.end(), qs[sb].groups[gi].all.begin(), qs[sb].groups[gi].all.end());
+    for (uint32_t sb = 0; sb < q_slabs; ++sb) g.slop.insert(g.slop.end(), qs[sb].groups[gi].slop.begin(), qs[sb].groups[gi].slop.end());
   }
   parallel_slabs(q_slabs, [&](uint32_t sb) {
     for (int gi = 0; gi < kNGroups; ++gi) {
@@ -893,7 +913,7 @@ int plan_group_tasks(Batch &b) {
   for (int gi = 0; gi < kNGroups; ++gi) {
     Group &g = b.groups[gi];
     if (g.queries.empty()) continue;
-    if (gi == kGTree) {  // one partial list per (query, tile of bitmap words); no chunk tables
+    if (gi == kGTree || gi == kGSlop) {  // one partial list per (query, tile of bitmap words); no chunk tables
       const uint32_t tiles = tqk_tree_tiles((b.s->max_doc + 31u) / 32u);
       g.kpl = kpl_for(g.max_k);
       for (TqdQuery &dq : g.queries) dq.n_parts = tiles;
@@ -938,6 +958,8 @@ int plan_group_tasks(Batch &b) {
   for (size_t i = 0; i < tree.tree.size(); ++i) tree.tree[i].part_start = tree.queries[i].part_start;
   Group &all = b.groups[kGAll];
   for (size_t i = 0; i < all.all.size(); ++i) all.all[i].part_start = all.queries[i].part_start;
+  Group &slop = b.groups[kGSlop];
+  for (size_t i = 0; i < slop.slop.size(); ++i) slop.slop[i].part_start = slop.queries[i].part_start;
   return TQ_OK;
 }
 
@@ -997,6 +1019,8 @@ int lay_out_stage(Batch &b) {
       g.o_leads = put(64, g.tree.data(), g.tree.size() * sizeof(TqdTreeQuery));
     } else if (gi == kGAll) {  // (o_leads: the ALL-BASED descriptors)
       g.o_leads = put(64, g.all.data(), g.all.size() * sizeof(TqdAllQuery));
+    } else if (gi == kGSlop) {  // (o_leads: the sloppy phrases' descriptors)
+      g.o_leads = put(64, g.slop.data(), g.slop.size() * sizeof(TqdSlopQuery));
     } else if (gi == kGXUnion) {  // (o_leads: the rows, o_tasks: the queries)
       g.o_leads = put(64, ps.xrows.data(), ps.xrows.size() * sizeof(TqkDenseRow));
       g.o_tasks = put(16, ps.xqueries.data(), ps.xqueries.size() * sizeof(TqkDenseQuery));
@@ -1130,6 +1154,13 @@ int zero_batch_buffers(Batch &b) {
   if (rc == TQ_OK) rc = zero_later(b.s->d_qmatches.p, (size_t)b.n_queries * sizeof(uint32_t));
   if (rc != TQ_OK) return rc;
   b.s->last_batch_queries = b.n_queries;
+  b.s->last_batch_slop = !b.groups[kGSlop].queries.empty();
+  b.s->slop_over_words = b.n_queries;
+  if (b.s->last_batch_slop) {  // the sloppy phrases' overflow words, one per query of the batch
+    rc = b.s->d_slop_over.ensure((size_t)b.n_queries * sizeof(uint32_t));
+    if (rc == TQ_OK) rc = zero_later(b.s->d_slop_over.p, (size_t)b.n_queries * sizeof(uint32_t));
+    if (rc != TQ_OK) return rc;
+  }
   if (b.t.n_thr_rows) {
     const size_t thr_bytes = (size_t)b.t.n_thr_rows * TQD_THR_SLOTS * sizeof(uint32_t);
     rc = b.s->d_thr.ensure(thr_bytes);
@@ -1289,6 +1320,23 @@ int launch_all(const Batch &b, hipStream_t gst) {
   return launched(tqk_launch_all(ap, g.kpl, gst), "match-all");
 }
 
+// The sloppy phrases over bitmap words: one launch per instantiation the group needs.
+int launch_slop(const Batch &b, hipStream_t gst) {
+  const Group &g = b.groups[kGSlop];
+  TqkPhraseSlopParams sp{};
+  sp.seg = b.s->dseg;
+  sp.terms = b.s->d_terms;
+  sp.queries = (const TqdSlopQuery *)(b.ds + g.o_leads);
+  sp.caches = (const float *)(b.ds + b.o_caches);
+  sp.sinks = (const TqkSinks *)(b.ds + g.o_sinks);
+  sp.table_base = (const uint8_t *)b.s->share_table_lo;
+  sp.overflow = (uint32_t *)b.s->d_slop_over.p;
+  sp.n_queries = (uint32_t)g.queries.size();
+  sp.n_words = (b.s->max_doc + 31u) / 32u;
+  for (const TqdSlopQuery &sq : g.slop) (sq.n_terms > 2u ? sp.any_carry : sp.any_pair) = 1u;
+  return launched(tqk_launch_phrase_slop(sp, g.kpl, gst), "sloppy phrase");
+}
+
 // The doc-major union launch.
 int launch_xunion(const Batch &b, hipStream_t gst) {
   const PlanScratch &ps = *b.ps;
@@ -1365,13 +1413,14 @@ int launch_groups(Batch &b) {
   for (int gi = 0; main_group < 0 && gi < kNGroups; ++gi)
     if (!groups[gi].queries.empty()) main_group = gi;
   // long serial chains first
-  for (const int gi : {kGAnd, kGBool, kGBShare, kGUShare, kGXUnion, kGTree, kGAll, kGUnion, kGPhrase, kGPhSweep, kGAndDense, kGAShare}) {
+  for (const int gi : {kGAnd, kGBool, kGBShare, kGUShare, kGXUnion, kGTree, kGSlop, kGAll, kGUnion, kGPhrase, kGPhSweep, kGAndDense, kGAShare}) {
     if (groups[gi].queries.empty()) continue;
     const hipStream_t gst = (fork && gi != main_group) ? b.s->side_stream : b.st;
     const int rc = gi == kGAShare || gi == kGBShare ? launch_ashare(b, gi, gst)
                    : gi == kGUShare                ? launch_ushare(b, gst)
                    : gi == kGTree                  ? launch_tree(b, gst)
                    : gi == kGAll                   ? launch_all(b, gst)
+                   : gi == kGSlop                  ? launch_slop(b, gst)
                    : gi == kGXUnion                ? launch_xunion(b, gst)
                                                    : launch_scan(b, gi, gst);
     if (rc != TQ_OK) return rc;
@@ -1414,6 +1463,9 @@ int launch_merges(const Batch &b) {
                             "merge kernel");
     if (rc != TQ_OK) return rc;
   }
+  // a host-output batch with sloppy phrases: their overflow words behind the rows, in stream order (the next batch zeroes them)
+  if (b.s->last_batch_slop && b.co.h_slop_over)
+    HIP_TRY(hipMemcpyAsync(b.co.h_slop_over, b.s->d_slop_over.p, (size_t)b.n_queries * sizeof(uint32_t), hipMemcpyDeviceToHost, b.st));
   return TQ_OK;
 }
 
@@ -1502,6 +1554,8 @@ struct AllStrip {
   std::deque<std::array<uint8_t, TQ_MAX_TERMS>> set_occurs;  // the occurs of TQ_MODE_AND / TQ_MODE_OR queries that name a set
   std::vector<uint8_t> set_q;  // per query: it names a term set and runs as a tree (empty: no query of the batch does)
   std::deque<TreeView> field_phrases;  // TQ_MODE_PHRASE queries of a non-primary field as one-atom trees
+  std::deque<SlopView> slop_views;     // TQ_MODE_PHRASE queries with slop > 0 as one-atom trees in cost order (tq_phrase_slop.cpp)
+  std::vector<uint32_t> slop_q;        // per query: its slop (empty: no query of the batch has one)
   uint32_t n_all_based = 0, n_set = 0;
 };
 int strip_all_clauses(const tq_segment *s, const tq_query *queries, uint32_t n_queries, AllStrip &st) {
@@ -1512,6 +1566,16 @@ int strip_all_clauses(const tq_segment *s, const tq_query *queries, uint32_t n_q
   // bitmap, nothing pruned).  A TQ_MODE_PHRASE query becomes the tree "one Must clause holding one phrase atom".
   const bool fields = s->n_field_terms != 0;
   for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    if (queries[qi].slop) {  // a sloppy phrase: its own launch group (route_slop), planned from its view
+      st.slop_views.emplace_back();
+      const int vrc = slop_view(s, queries[qi], qi, "tq_search_batch", st.slop_views.back(), true);
+      if (vrc != TQ_OK) return vrc;
+      if (st.eff.empty()) st.eff.assign(queries, queries + n_queries);
+      st.eff[qi] = st.slop_views.back().v.q;
+      if (st.slop_q.empty()) st.slop_q.assign(n_queries, 0);
+      st.slop_q[qi] = queries[qi].slop;
+      continue;
+    }
     bool names_set = false;
     if (sets) {
       const int src = check_set_query(s, queries[qi], qi, "tq_search_batch", &names_set);
@@ -1606,6 +1670,7 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
   Batch b{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, co, d_out_segment_ords, segment_ord};
   b.n_all_queries = strip.n_all_based;
   b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
+  b.slop_q = strip.slop_q.empty() ? nullptr : strip.slop_q.data();
   rc = plan_batch(b);
   // a shared launch's result lists over the budget even with the longest tasks: the same batch again, that family
   // through the per-query kernels
@@ -1613,6 +1678,7 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
     b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co, d_out_segment_ords, segment_ord};
     b.n_all_queries = strip.n_all_based;
     b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
+    b.slop_q = strip.slop_q.empty() ? nullptr : strip.slop_q.data();
     rc = plan_batch(b);
   }
   if (rc != TQ_OK) return rc;
@@ -1659,17 +1725,25 @@ int search_batch_host(tq_segment *s, const tq_query *queries, uint32_t n_queries
   // now and then held the calling thread for 7 ms, tantivy_amd/distributed.py).
   const size_t n = (size_t)n_queries * out_stride;
   size_t o_docs, o_counts;
-  int rc = s->h_out.ensure(host_rows_layout(n_queries, out_stride, o_docs, o_counts));
+  const size_t o_over = (host_rows_layout(n_queries, out_stride, o_docs, o_counts) + 255) & ~(size_t)255;  // (the overflow words of sloppy phrases)
+  int rc = s->h_out.ensure(o_over + (size_t)n_queries * sizeof(uint32_t));
   if (rc != TQ_OK) return rc;
   uint8_t *h = (uint8_t *)s->h_out.p;
+  CallOpts co_over = co;
+  co_over.h_slop_over = (uint32_t *)(h + o_over);
   rc = search_batch_impl(s, queries, n_queries, out_stride, (float *)h, (uint32_t *)(h + o_docs),
-                         (uint32_t *)(h + o_counts), nullptr, co);
+                         (uint32_t *)(h + o_counts), nullptr, co_over);
   if (rc != TQ_OK) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   memcpy(out_scores, h, n * sizeof(float));
   memcpy(out_docs, h + o_docs, n * sizeof(uint32_t));
   memcpy(out_counts, h + o_counts, (size_t)n_queries * sizeof(uint32_t));
-  return TQ_OK;
+  if (co.defer_slop_verdict) {
+    if (s->last_batch_slop) s->slop_over_host.assign((const uint32_t *)(h + o_over), (const uint32_t *)(h + o_over) + n_queries);
+    return TQ_OK;
+  }
+  // (the rows above are written and valid for every other query: the caller falls back for the one named)
+  return s->last_batch_slop ? slop_overflow_verdict("tq_search_batch", (const uint32_t *)(h + o_over), n_queries) : TQ_OK;
 }
 int search_batch_host_begin(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t out_stride,
                             const CallOpts &co, HostBatchSlot &slot) {
@@ -1677,14 +1751,18 @@ int search_batch_host_begin(tq_segment *s, const tq_query *queries, uint32_t n_q
   HIP_TRY(hipSetDevice(s->device));
   slot.n = n_queries;
   slot.stride = out_stride;
-  int rc = slot.out.ensure(host_rows_layout(n_queries, out_stride, slot.o_docs, slot.o_counts));
+  slot.o_slop_over = (host_rows_layout(n_queries, out_stride, slot.o_docs, slot.o_counts) + 255) & ~(size_t)255;
+  int rc = slot.out.ensure(slot.o_slop_over + (size_t)n_queries * sizeof(uint32_t));
   if (rc != TQ_OK) return rc;
   if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
   if (!slot.done_blocking) HIP_TRY(hipEventCreateWithFlags(&slot.done_blocking, hipEventDisableTiming | hipEventBlockingSync));
   uint8_t *h = (uint8_t *)slot.out.p;
+  CallOpts co_over = co;
+  co_over.h_slop_over = (uint32_t *)(h + slot.o_slop_over);
   rc = search_batch_impl(s, queries, n_queries, out_stride, (float *)h, (uint32_t *)(h + slot.o_docs),
-                         (uint32_t *)(h + slot.o_counts), nullptr, co);
+                         (uint32_t *)(h + slot.o_counts), nullptr, co_over);
   if (rc != TQ_OK) return rc;
+  slot.any_slop = s->last_batch_slop;
   // A batch of many callers is waited for asleep (an interrupt, some tens of microseconds later than a spinning wait
   // would notice): with hundreds of request threads the host's cores are what runs out first — the GPU box grants 16,
   // and a process above its quota is stopped for the rest of the 100 ms period, all its threads (p99 of 1 024 threads:

@@ -60,7 +60,7 @@ struct SubmitQueue {
   // the leader's scratch (the synchronous road: a batch that has to be bisected)
   std::vector<tq_query> qs;
   std::vector<float> sc;
-  std::vector<uint32_t> dc, ct;
+  std::vector<uint32_t> dc, ct, ov;  // (ov: the overflow words of sloppy phrases, tq_phrase_slop.cpp)
   // Two coalesced batches can be in flight: the leader of batch i hands leadership on as soon as the batch is
   // ENQUEUED, waits for its rows off the lock, and the next leader plans and enqueues batch i + 1 behind it on the
   // segment's stream meanwhile (the library pipelines two batches: two staging buffers).
@@ -110,11 +110,20 @@ void run_ticket_range(SubmitQueue &Q, tq_segment *s, std::vector<tq_ticket *> &b
   int rc;
   {
     TQ_SEGMENT_LOCK(s);
-    rc = search_batch_host(s, Q.qs.data(), n, stride, Q.sc.data(), Q.dc.data(), Q.ct.data(), batch[lo]->co);
+    CallOpts co = batch[lo]->co;
+    co.defer_slop_verdict = true;  // (a sloppy phrase over the carry cap fails its own ticket below, not the batch)
+    rc = search_batch_host(s, Q.qs.data(), n, stride, Q.sc.data(), Q.dc.data(), Q.ct.data(), co);
+    Q.ov.assign(n, 0u);
+    if (rc == TQ_OK && s->last_batch_slop && s->slop_over_host.size() == n) Q.ov = s->slop_over_host;
   }
   if (rc == TQ_OK) {
     for (uint32_t i = 0; i < n; ++i) {
       tq_ticket *t = batch[lo + i];
+      if (Q.ov[i]) {  // a sloppy phrase over the carry cap: this ticket alone fails, its batch mates keep their rows
+        t->rc = slop_overflow_fail("tq_wait", 0u, Q.ov[i]);
+        t->err = g_last_error;
+        continue;
+      }
       const uint32_t k = t->q.k;
       memcpy(t->out_scores, Q.sc.data() + (size_t)i * stride, k * sizeof(float));
       memcpy(t->out_docs, Q.dc.data() + (size_t)i * stride, k * sizeof(uint32_t));
@@ -314,7 +323,15 @@ int ticket_wait(tq_ticket *t, bool parked = false) {
       }
       for (size_t i = 0; i < batch.size(); ++i) {
         tq_ticket *b = batch[i];
-        if (erc == TQ_OK) {
+        const uint32_t over = erc == TQ_OK && S.any_slop ? ((const uint32_t *)((const uint8_t *)S.out.p + S.o_slop_over))[i] : 0u;
+        if (over) {  // a sloppy phrase over the carry cap: this ticket alone fails, its batch mates keep their rows
+          b->rc = TQ_ERR_UNSUPPORTED;
+          try {
+            (void)slop_overflow_fail("tq_wait", 0u, over);
+            b->err = g_last_error;
+          } catch (...) {
+          }
+        } else if (erc == TQ_OK) {
           const uint8_t *h = (const uint8_t *)S.out.p;
           const uint32_t k = b->q.k;
           memcpy(b->out_scores, h + ((size_t)i * S.stride) * sizeof(float), k * sizeof(float));

@@ -81,6 +81,7 @@ struct tqh_query {
   const uint8_t *occurs;           // TQ_MODE_BOOL: 0 Should, 1 Must, 2 MustNot
   const uint8_t *clause_of;        // TQ_MODE_BOOL: terms sharing a value form one nested union; or null
   uint32_t min_should_match;       // TQ_MODE_BOOL
+  uint32_t slop;                   // TQ_MODE_PHRASE: PhraseQuery::set_slop (in what was padding; 0 in every other mode)
   const float *boosts;             // BoostQuery factor per term query (PHRASE: boosts[0] = the phrase's); or null
   const uint8_t *nested_occurs;    // TQ_MODE_BOOL, or null: see tantivy_amd_host.h
   const uint8_t *clause_min_should;  // TQ_MODE_BOOL, or null: minimum_number_should_match of the nested query, by clause_of value
@@ -377,6 +378,7 @@ static Query build_query(const tqh_query &q) {
     for (uint32_t t = 0; t < q.n_terms; ++t)
       pt.emplace_back(q.phrase_offsets ? q.phrase_offsets[t] : t, q.terms[t]);
     query = Query::phrase_with_offsets(std::move(pt));
+    query.set_slop(q.slop);
     // BoostQuery around the PhraseQuery: PhraseWeight applies it with boost_by
     // (phrase_weight.rs:42-69); boosts[0] is the factor of the whole phrase
     if (q.boosts) query.boosted(q.boosts[0]);

@@ -367,6 +367,7 @@ Weight Searcher::weight(const Query &query) const {
         idf_sum += idf(doc_freq(ot.second), nd);
       }
       w.weights = {boost_by(idf_sum * (1.0f + K1), b0)};
+      w.slop = query.slop;
       return w;
     }
     case Query::Boolean: {
@@ -513,6 +514,8 @@ Weight Searcher::weight(const Query &query) const {
                                "A phrase query is required to have strictly more than one term.");
           if (ph.phrase_terms.size() > 8)
             throw TantivyError(TantivyError::Unsupported, "a phrase inside a boolean query takes at most 8 terms on the device");
+          if (ph.slop)  // (one slop per device query, read in TQ_MODE_PHRASE alone)
+            throw TantivyError(TantivyError::Unsupported, "a phrase with a slop inside a boolean query stays on the CPU");
           check_phrase_fields(ph);
           Score idf_sum = 0.0f;
           for (auto &ot : ph.phrase_terms) idf_sum += idf(doc_freq(ot.second), nd);
@@ -619,6 +622,7 @@ struct SegmentBatch {
       q.occurs = w.occurs.empty() ? nullptr : w.occurs.data();
       q.clause_of = w.clause_of.empty() ? nullptr : w.clause_of.data();
       q.min_should_match = w.min_should_match;
+      q.slop = w.slop;
       q.nested_occurs = w.nested_occurs.empty() ? nullptr : w.nested_occurs.data();
       q.clause_min_should = w.clause_min_should.empty() ? nullptr : w.clause_min_should.data();
       q.atom_of = w.atom_of.empty() ? nullptr : w.atom_of.data();
@@ -800,6 +804,7 @@ Fruit Searcher::search(const Query &query, const TopDocs &collector) {
     q.occurs = w.occurs.empty() ? nullptr : w.occurs.data();
     q.clause_of = w.clause_of.empty() ? nullptr : w.clause_of.data();
     q.min_should_match = w.min_should_match;
+    q.slop = w.slop;
     q.nested_occurs = w.nested_occurs.empty() ? nullptr : w.nested_occurs.data();
     q.clause_min_should = w.clause_min_should.empty() ? nullptr : w.clause_min_should.data();
     q.atom_of = w.atom_of.empty() ? nullptr : w.atom_of.data();

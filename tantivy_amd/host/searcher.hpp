@@ -122,8 +122,9 @@ struct Query {
   // BoostQuery::new(this, boost) (boost_query.rs:14-31): BoostWeight::scorer hands
   // `boost * self.boost` down the tree (:70-72) and the leaves apply Bm25Weight::boost_by
   Score boost = 1.0f;
-  // Phrase: (offset, term), slop 0 (phrase_query.rs:28-63)
+  // Phrase: (offset, term) (phrase_query.rs:28-63) and PhraseQuery::set_slop (0 = the exact phrase)
   std::vector<std::pair<uint32_t, uint32_t>> phrase_terms;
+  uint32_t slop = 0;
 
   static Query term_query(uint32_t term) {
     Query q;
@@ -162,12 +163,19 @@ struct Query {
     minimum_number_should_match = n;
     return *this;
   }
-  // PhraseQuery::new(terms): offsets 0..n
-  static Query phrase(const std::vector<uint32_t> &terms) {
+  // PhraseQuery::new(terms): offsets 0..n; slop as PhraseQuery::set_slop
+  static Query phrase(const std::vector<uint32_t> &terms, uint32_t slop = 0) {
     Query q;
     q.kind = Phrase;
     for (uint32_t i = 0; i < terms.size(); ++i) q.phrase_terms.emplace_back(i, terms[i]);
+    q.slop = slop;
     return q;
+  }
+  // PhraseQuery::set_slop.  A top-level phrase only: a phrase that is a clause of a BooleanQuery cannot carry one to the
+  // device (tq_query has one slop, read in TQ_MODE_PHRASE: tantivy_amd.h "Sloppy phrases") — Unsupported there.
+  Query &set_slop(uint32_t s) {
+    slop = s;
+    return *this;
   }
   static Query phrase_with_offsets(std::vector<std::pair<uint32_t, uint32_t>> terms) {
     Query q;
@@ -326,6 +334,7 @@ struct Weight {
   std::vector<uint8_t> clause_min_should;  // TQ_MODE_BOOL: the nested queries' minimum_number_should_match by clause
                                            // index (TQ_MAX_TERMS entries), or empty
   uint32_t min_should_match = 0;         // TQ_MODE_BOOL
+  uint32_t slop = 0;                     // TQ_MODE_PHRASE: PhraseQuery::set_slop
   std::shared_ptr<Bm25Weight> bm25;      // holds the shared tf cache (multi-field segments: one row per field, Bm25Weight::field_rows)
 };
 
