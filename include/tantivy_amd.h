@@ -376,6 +376,80 @@ int tq_term_set_info(tq_segment *seg, tq_term_handle set, uint32_t *n_docs, uint
  * reuse the slot.  tq_segment_free frees the sets still outstanding. */
 int tq_term_set_release(tq_segment *seg, tq_term_handle set);
 
+/* ---- fast-field ranges ----
+ * replaces: FastFieldRangeWeight::scorer for a u64-mapped fast field (src/query/range_query/range_query_fastfield.rs:
+ * 54-239 -> search_on_u64_ff :414-450 -> RangeDocSet over a Column<u64> under ConstScorer(docset, boost),
+ * fast_field_range_doc_set.rs) for one segment: `+body:error +timestamp:[a TO b]`, `price:[10 TO 20]`,
+ * `* -age:{* TO 18}`.
+ * A COLUMN is one serialized u64_based column-values blob, byte for byte as serialize_u64_based_column_values writes it
+ * (columnar/src/column_values/u64_based/mod.rs:79-110): a codec byte (0 Bitpacked, 1 Linear, 2 BlockwiseLinear),
+ * ColumnStats as four VInts — min, gcd, amplitude / gcd, num_rows (stats.rs:30-54; common's VInt, stop bit on the LAST
+ * byte) — and the codec's payload (bitpacked.rs, linear.rs, blockwise_linear.rs, line.rs, bitpacker/src/bitpacker.rs).
+ * The payload stays in HBM as the file holds it, in a 256-byte-aligned buffer of its own with 16 zero bytes behind it;
+ * BlockwiseLinear adds one 32-byte record per block of 512 rows (slope, intercept, data offset, bit width).  Up to
+ * TQ_MAX_COLUMNS columns per segment; their bytes are tq_column_info_t.resident_bytes, not part of tq_segment_stats.
+ *   TQ_CARD_FULL         present_words must be NULL and num_rows == max_doc (else TQ_ERR_FORMAT): a doc's row is the doc
+ *   TQ_CARD_OPTIONAL     present_words = ceil(max_doc / 32) words, bit d of the array set when doc d has a value (the
+ *                        caller reads them off the reference's OptionalIndex); bits at or above max_doc are ignored; their
+ *                        popcount must be num_rows (else TQ_ERR_FORMAT); a doc's row is the number of set bits below it
+ *   TQ_CARD_MULTIVALUED  TQ_ERR_UNSUPPORTED in this version
+ * Malformed bytes — truncated anywhere, an unknown codec byte, gcd 0, min + amplitude past u64, a bit width of 57..63 or
+ * above 64, a payload shorter than ceil(num_rows * num_bits / 8), a BlockwiseLinear footer that does not fit — are
+ * TQ_ERR_FORMAT with a message, never a crash.  tq_column_parse is that check alone, on the host, without a device: it
+ * fills codec, min, max, gcd, num_rows, num_bits (resident_bytes = what an upload would hold, cardinality 0).
+ *
+ * tq_range_prepare turns (column, value range) into a TERM-SET handle (above): a {32 doc bits, docs before the word} table
+ * built by tq_range.hip — a lane per doc reads its row's packed value and compares it with the range divided by the gcd
+ * (transform_range_before_linear_transformation, bitpacked.rs:37-49), a wavefront's ballot is two words of the table,
+ * the term sets' rank stage follows — that tq_term_set_info, tq_term_set_release, tq_term_table_read(TQ_TABLE_DENSE) and
+ * every query entry point treat exactly as a term set, refusals included (phrases, nested structure, a Should set beside
+ * an All clause in top-k).  It scores *out_weight wherever it is present: pass that as the entry's weight.  Releasing the
+ * column does not touch handles already built from it.
+ * The bounds are in the column's u64 space: the caller applies MonotonicallyMappableToU64 first (u64: the value; i64:
+ * (uint64_t)v ^ (1 << 63); f64: bits ^ (bits >> 63 ? ~0 : 1 << 63); bool: 0 / 1; date: its i64 of nanoseconds) and the
+ * JSON numeric coercions of :254-412.  Then search_on_u64_ff + bound_to_value_range + RangeDocSet::new, literally:
+ *   both bounds unbounded     *out = TQ_TERM_ALL, *out_weight = 1.0f (the reference returns AllScorer before it looks at
+ *                             the column, and drops the boost, :57-59); the column is not looked at
+ *   start / end               start = lower, lower + 1 for Excluded (overflow: empty), the column's min when unbounded, then
+ *                             raised to min; end = upper, upper - 1 for Excluded (underflow: empty), max when unbounded,
+ *                             NOT clamped
+ *   empty                     start > end, start > max, end < min or num_rows == 0: a valid handle over a zeroed table (no
+ *                             kernel runs), 0 docs, *out_weight = boost
+ *   full coverage             min >= start && max <= end on a TQ_CARD_FULL column: boost == 1.0f gives *out = TQ_TERM_ALL,
+ *                             *out_weight = 1.0f (an AllScorer: `+range +a` scores bm25(a) alone); any other boost a set
+ *                             of all max_doc docs scoring boost.  An Optional column never takes the shortcut (:443-445)
+ *   otherwise                 the fill; *out_weight = boost
+ * A bound kind above TQ_BOUND_EXCLUDED, a column that is out of range or released (unless both bounds are unbounded):
+ * TQ_ERR_INVALID.  With the option "timing" set the build's figures replace the last batch's, as after
+ * tq_term_set_prepare: kernel_ms = total_ms = from the zeroing to the end of the rank stage, algorithmic_bytes = the
+ * payload's bytes + 16 B per 32 docs (the table written, and read once by the scan) + 8 B per 32 docs of presence table
+ * of an Optional column; an empty range: 0 bytes. */
+#define TQ_MAX_COLUMNS 16u
+enum tq_cardinality { TQ_CARD_FULL = 0, TQ_CARD_OPTIONAL = 1, TQ_CARD_MULTIVALUED = 2 };
+enum tq_column_codec { TQ_CODEC_BITPACKED = 0, TQ_CODEC_LINEAR = 1, TQ_CODEC_BLOCKWISE_LINEAR = 2 };
+enum tq_bound_kind { TQ_BOUND_UNBOUNDED = 0, TQ_BOUND_INCLUDED = 1, TQ_BOUND_EXCLUDED = 2 };
+typedef struct tq_column_info_t {
+  uint64_t min_value, max_value, gcd;
+  uint64_t resident_bytes; /* payload + padding, block records, presence table */
+  uint32_t num_rows;
+  uint32_t num_bits;       /* Bitpacked: bits per value (0..56 or 64); the linear codecs: 0 */
+  uint32_t codec;          /* tq_column_codec */
+  uint32_t cardinality;    /* tq_cardinality */
+} tq_column_info_t;
+int tq_column_parse(const uint8_t *values, size_t values_len, tq_column_info_t *out);
+int tq_column_upload(tq_segment *seg, const uint8_t *values, size_t values_len, uint8_t cardinality,
+                     const uint32_t *present_words, uint32_t *out_column);
+int tq_column_info(tq_segment *seg, uint32_t column, tq_column_info_t *out);
+/* Waits for the segment to be idle, like tq_term_set_release, and frees the column's buffers; the slot is taken by a
+ * later upload.  tq_segment_free frees the columns still held. */
+int tq_column_release(tq_segment *seg, uint32_t column);
+/* Codec access (tests, tooling): out_host[i] = the value of ROW first_row + i, i < n — min + gcd * n for Bitpacked and
+ * BlockwiseLinear, line.eval(row) + diff for Linear — read by the kernels' own three readers.  first_row + n > num_rows:
+ * TQ_ERR_INVALID. */
+int tq_column_decode(tq_segment *seg, uint32_t column, uint32_t first_row, uint32_t n, uint64_t *out_host);
+int tq_range_prepare(tq_segment *seg, uint32_t column, uint8_t lower_kind, uint64_t lower, uint8_t upper_kind, uint64_t upper,
+                     float boost, tq_term_handle *out, float *out_weight);
+
 /* ---- search ----
  * replaces, for each query: TopBySortKeyCollector::collect_segment ->
  * SortBySimilarityScore::collect_segment_top_k -> Weight::for_each_pruning -> {block_wand,

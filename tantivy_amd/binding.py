@@ -12,6 +12,7 @@ if os.environ.get("TQ_LIB_PATH"):  # experiments: a variant build (tools/build_v
 TERMINATED = 0x7FFFFFFF
 TERM_ABSENT = 0xFFFFFFFF
 TERM_ALL = 0xFFFFFFFE  # TQ_TERM_ALL: the clause is an AllQuery; accepted as a term id in every query tuple, its boost in "boosts" / weights
+STAR = TERM_ALL  # what DeviceIndex.range_prepare returns in place of a handle where the range clause is an AllScorer
 ALL_EMPTY, ALL_PLAIN, ALL_BASED = 0, 1, 2  # enum tq_all_kind
 MODE_AND, MODE_OR, MODE_PHRASE, MODE_BOOL, MODE_TERM = 0, 1, 2, 3, 4  # enum tq_mode + TQH_MODE_TERM
 SHOULD, MUST, MUST_NOT = 0, 1, 2  # src/query/occur.rs
@@ -156,6 +157,7 @@ EXPORTS = [
     "tq_segment_upload_fields", "tq_segment_get_fields_stats", "tq_term_prepare_field", "tq_term_prepare_batch_fields",
     "tq_term_field", "tqh_searcher_add_segment_fields", "tqh_searcher_add_remote_stats_fields",
     "tq_term_table_read", "tq_term_table_info",
+    "tq_column_parse", "tq_column_upload", "tq_column_info", "tq_column_release", "tq_column_decode", "tq_range_prepare",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -174,6 +176,30 @@ class TqTermTableInfo(C.Structure):  # tq_term_table_info_t
                 ("payload_base", C.c_uint64), ("has_freq", C.c_uint32), ("rdir_shift", C.c_uint32),
                 ("rmax_list", C.c_uint32), ("n_pos_blocks", C.c_uint32), ("n_pos_tail", C.c_uint32), ("field", C.c_uint32),
                 ("n_positions", C.c_uint64), ("doc_freq", C.c_uint32), ("probe_slot", C.c_uint32)]
+
+
+class TqColumnInfo(C.Structure):  # tq_column_info_t
+    _fields_ = [("min_value", C.c_uint64), ("max_value", C.c_uint64), ("gcd", C.c_uint64), ("resident_bytes", C.c_uint64),
+                ("num_rows", C.c_uint32), ("num_bits", C.c_uint32), ("codec", C.c_uint32), ("cardinality", C.c_uint32)]
+
+
+MAX_COLUMNS = 16  # TQ_MAX_COLUMNS
+CARD_FULL, CARD_OPTIONAL, CARD_MULTIVALUED = 0, 1, 2  # tq_cardinality
+CODEC_BITPACKED, CODEC_LINEAR, CODEC_BLOCKWISE_LINEAR = 0, 1, 2  # tq_column_codec
+BOUND_KINDS = {"in": 1, "ex": 2}  # tq_bound_kind (None: TQ_BOUND_UNBOUNDED)
+
+
+def _column_info_dict(info):
+    return {n: int(getattr(info, n)) for n, _ in TqColumnInfo._fields_}
+
+
+def column_parse(values_bytes):
+    """tq_column_parse: the host-side check of one serialized u64_based column-values blob -> dict of tq_column_info_t
+    (codec, min_value, max_value, gcd, num_rows, num_bits, resident_bytes).  Needs no device."""
+    a = np.frombuffer(bytes(values_bytes) + b"\0", dtype=np.uint8)  # (an empty blob is still a pointer)
+    info = TqColumnInfo()
+    _check(lib().tq_column_parse(a.ctypes.data, a.size - 1, C.byref(info)))
+    return _column_info_dict(info)
 
 
 def lib():
@@ -241,6 +267,12 @@ def lib():
     L.tq_term_field.argtypes = [vp, C.c_uint32, u32p]
     L.tq_term_table_read.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.tq_term_table_info.argtypes = [vp, C.c_uint32, C.POINTER(TqTermTableInfo)]
+    L.tq_column_parse.argtypes = [vp, C.c_size_t, C.POINTER(TqColumnInfo)]
+    L.tq_column_upload.argtypes = [vp, vp, C.c_size_t, C.c_uint8, u32p, u32p]
+    L.tq_column_info.argtypes = [vp, C.c_uint32, C.POINTER(TqColumnInfo)]
+    L.tq_column_release.argtypes = [vp, C.c_uint32]
+    L.tq_column_decode.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.tq_range_prepare.argtypes = [vp, C.c_uint32, C.c_uint8, C.c_uint64, C.c_uint8, C.c_uint64, C.c_float, u32p, f32p]
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -926,6 +958,45 @@ class DeviceIndex:
 
     def term_set_release(self, h, segment_ord=0):
         _check(lib().tq_term_set_release(self.segment_raw(segment_ord), int(h)))
+
+    # ---- fast-field columns and range clauses (tq_column.cpp, tq_range.hip)
+    def add_column(self, values_bytes, cardinality=CARD_FULL, present=None, segment_ord=0):
+        """tq_column_upload on one segment: `values_bytes` = one serialized u64_based column-values blob; `present` (for
+        CARD_OPTIONAL) = ceil(max_doc / 32) uint32 words, bit d set when doc d has a value.  -> the column's index."""
+        a = np.frombuffer(bytes(values_bytes) + b"\0", dtype=np.uint8)
+        words = None if present is None else np.ascontiguousarray(present, dtype=np.uint32)
+        out = C.c_uint32()
+        _check(lib().tq_column_upload(self.segment_raw(segment_ord), a.ctypes.data, a.size - 1, int(cardinality),
+                                      _u32(words) if words is not None else None, C.byref(out)))
+        return int(out.value)
+
+    def column_info(self, column, segment_ord=0):
+        """tq_column_info -> dict of tq_column_info_t."""
+        info = TqColumnInfo()
+        _check(lib().tq_column_info(self.segment_raw(segment_ord), int(column), C.byref(info)))
+        return _column_info_dict(info)
+
+    def column_release(self, column, segment_ord=0):
+        _check(lib().tq_column_release(self.segment_raw(segment_ord), int(column)))
+
+    def column_decode(self, column, first_row=0, n=None, segment_ord=0):
+        """tq_column_decode: the values of rows [first_row, first_row + n) (default: to the last row) as uint64."""
+        if n is None:
+            n = self.column_info(column, segment_ord)["num_rows"] - first_row
+        out = np.zeros(max(1, int(n)), np.uint64)
+        _check(lib().tq_column_decode(self.segment_raw(segment_ord), int(column), int(first_row), int(n),
+                                      out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[: int(n)]
+
+    def range_prepare(self, column, lower, upper, boost=1.0, segment_ord=0):
+        """tq_range_prepare: a bound is None, ("in", v) or ("ex", v), v in the column's u64 space.  -> (handle, weight):
+        a RawHandle for the raw_* helpers' term lists — STAR (= TERM_ALL) where the reference answers with an AllScorer —
+        and the weight the clause scores."""
+        lk, lv = (0, 0) if lower is None else (BOUND_KINDS[lower[0]], int(lower[1]))
+        uk, uv = (0, 0) if upper is None else (BOUND_KINDS[upper[0]], int(upper[1]))
+        out, w = C.c_uint32(), C.c_float()
+        _check(lib().tq_range_prepare(self.segment_raw(segment_ord), int(column), lk, lv, uk, uv, float(boost), C.byref(out), C.byref(w)))
+        return (STAR if out.value == TERM_ALL else RawHandle(out.value)), float(w.value)
 
     def decode_postings(self, term_id, doc_freq, segment_ord=0):
         h = self.term_handle(term_id, segment_ord)

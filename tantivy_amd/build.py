@@ -20,6 +20,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_count.cpp"),
     os.path.join(HERE, "csrc", "tq_termset.hip"),
     os.path.join(HERE, "csrc", "tq_termset.cpp"),
+    os.path.join(HERE, "csrc", "tq_range.hip"),
+    os.path.join(HERE, "csrc", "tq_column.cpp"),
     os.path.join(HERE, "csrc", "tq_docset.hip"),
     os.path.join(HERE, "csrc", "tq_docset.cpp"),
     os.path.join(HERE, "csrc", "tq_docset_score.hip"),

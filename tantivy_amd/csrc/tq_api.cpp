@@ -281,6 +281,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_count_bits.release();
   s->d_count_wgs.release();
   s->d_set_work.release();
+  free_columns(s);
   s->d_docset_queries.release();
   s->d_docset_counts.release();
   s->d_docset_offs.release();

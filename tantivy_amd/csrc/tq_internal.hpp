@@ -326,6 +326,18 @@ struct tq_segment {
   std::vector<uint32_t> set_free_slots;
   std::vector<void *> set_free_tables;
   DevBuf d_set_work;
+  // fast-field columns (tq_column.cpp): u64_based column-values payloads as the file holds them, TQ_MAX_COLUMNS slots (a
+  // released slot is taken by the next upload); tq_range_prepare makes term-set slots of them
+  struct ColumnHost {
+    bool live = false;
+    tq_column_info_t info{};
+    TqkColumn dev{};            // payload / blocks / present point into the three allocations below
+    void *d_payload = nullptr;  // the codec's payload + 16 zero bytes
+    void *d_blocks = nullptr;   // BlockwiseLinear: TqkColBlock per block
+    void *d_present = nullptr;  // TQ_CARD_OPTIONAL: {presence bits, rows before the word}, n_words + 1 entries
+    uint64_t payload_len = 0;
+  };
+  ColumnHost columns[TQ_MAX_COLUMNS];
   uint32_t alive_docs = 0;  // docs below max_doc the alive bitset keeps (counted when it is set; without one: max_doc)
   std::unordered_map<uint64_t, uint32_t> term_by_off;
   // lists named by tq_segment_reserve_columns (postings_off): only they get doc-matrix columns
@@ -945,6 +957,12 @@ struct AllView {  // the entries of keep_mask as a query of their own (borrows q
 void all_strip_view(const tq_query &q, const AllForm &f, AllView &v);
 // ---- tq_termset.cpp: term sets (tq_term_set_prepare: a slot of the term table that is a bitmap and scores a constant)
 inline bool is_term_set(const tq_segment *s, uint32_t h) { return h < s->terms.size() && s->terms[h].set_kind == TermHost::kSet; }
+// a set's table: (max_doc / 32 words + the sentinel) from the released tables or the arena; back to them; and the slot of
+// the term table that makes a BUILT table a set of n_docs docs (tq_range_prepare's handles are such slots too)
+int set_table_acquire(tq_segment *s, void **tab);
+void set_table_release(tq_segment *s, void *tab);
+uint32_t set_slot_commit(tq_segment *s, void *tab, uint32_t n_docs);
+void free_columns(tq_segment *s);  // tq_column.cpp: the fast-field columns still held (tq_segment_free)
 // a list's bitmap as the count / doc-set expressions name it: its own where "use_dense" allows, a set's always (it has nothing else)
 inline const void *expression_bitmap(const tq_segment *s, const TermHost &th) {
   return th.dense_blob && (s->opt.use_dense || th.set_kind == TermHost::kSet) ? th.dense_blob : nullptr;

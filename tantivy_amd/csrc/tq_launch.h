@@ -379,6 +379,32 @@ hipError_t tqk_launch_termset_build(const TqdSegment &seg, const TqdTerm *terms,
                                     hipStream_t st);
 uint32_t tqk_termset_scan_tile();
 uint32_t tqk_termset_scratch_words(uint32_t n_words);
+// ... its rank stage alone, over a table of n_words + 1 entries whose .x words are written (bits at and past max_doc in the
+// last word are cleared first): tab[w].y = docs before word w, tab[n_words] = {0, docs}, scan_scratch as above
+hipError_t tqk_launch_bitmap_rank(uint2 *tab, uint32_t n_words, uint32_t max_doc, uint32_t *scan_scratch, hipStream_t st);
+// ---- fast-field ranges (tq_range.hip): a u64_based column-values payload in HBM (tq_column.cpp) against a value range
+#define TQK_COL_BITPACKED 0u
+#define TQK_COL_LINEAR 1u
+#define TQK_COL_BLOCKWISE 2u
+struct TqkColBlock {   // 32 bytes: one block of 512 rows of a BlockwiseLinear column
+  uint64_t slope, intercept;  // its Line
+  uint64_t data_off;          // byte offset of its bit-packed diffs in the payload (a multiple of 64)
+  uint32_t bit_width, pad_;
+};
+struct TqkColumn {
+  const uint32_t *payload;    // the codec's payload from its first byte, 256-byte aligned, 16 zero bytes behind it
+  const TqkColBlock *blocks;  // BlockwiseLinear: ceil(num_rows / 512) records
+  const uint2 *present;       // TQ_CARD_OPTIONAL: {32 presence bits, rows before the word} per 32 docs; null: row = doc
+  uint64_t slope, intercept;  // Linear: its Line
+  uint32_t codec, num_bits;   // num_bits: Bitpacked / Linear (BlockwiseLinear: per block)
+  uint32_t num_rows, max_doc;
+};
+// tab[w].x = the docs of word w whose packed value n lies in [lo, hi] (both inclusive; Linear: n is the value itself),
+// every word of the table written; the rank stage follows
+hipError_t tqk_launch_range_fill(const TqkColumn &col, uint64_t lo, uint64_t hi, uint2 *tab, uint32_t n_words, hipStream_t st);
+// out[i] = min + gcd * n of row first_row + i (Linear: n), i < n; the caller has checked first_row + n <= num_rows
+hipError_t tqk_launch_column_decode(const TqkColumn &col, uint64_t min_value, uint64_t gcd, uint32_t first_row, uint32_t n,
+                                    uint64_t *out, hipStream_t st);
 // ---- full doc sets over bitmaps (tq_docset.hip): the expression of TqkCountQuery with the result bits kept
 struct TqkDocsetQuery {           // 152 bytes
   uint32_t n_terms;               // lists: Must clauses first (a clause = a union of lists), then MustNot, then Should

@@ -15,14 +15,53 @@ constexpr uint32_t kConstScoreFlag = 1u << 25;  // TqdTermHead::has_freq bit 25
 inline size_t set_words(const tq_segment *s) { return ((size_t)s->max_doc + 31u) / 32u; }
 inline size_t set_bytes(const tq_segment *s) { return set_words(s) * sizeof(uint2); }
 
+}  // namespace
+
 // a released table goes back to the allocator when it had an allocation of its own; a piece of the arena waits for the next set
-void release_set_table(tq_segment *s, void *tab) {
+void set_table_release(tq_segment *s, void *tab) {
   if (!tab) return;
   const bool own = std::find(s->dense_extra.begin(), s->dense_extra.end(), tab) != s->dense_extra.end();
   dense_release(s, tab);
   if (!own) s->set_free_tables.push_back(tab);
 }
-}  // namespace
+
+int set_table_acquire(tq_segment *s, void **tab) {
+  if (!s->set_free_tables.empty()) {
+    *tab = s->set_free_tables.back();
+    s->set_free_tables.pop_back();
+    return TQ_OK;
+  }
+  return dense_alloc(s, (set_words(s) + 1u) * sizeof(uint2), tab);  // (+ the sentinel entry of every dense table)
+}
+
+uint32_t set_slot_commit(tq_segment *s, void *tab, uint32_t n_docs) {
+  TqdTerm dt{};
+  dt.dense = (const uint2 *)tab;
+  dt.doc_freq = n_docs;
+  dt.has_freq = kConstScoreFlag;
+  TermHost th;
+  th.dense_blob = tab;
+  th.doc_freq = n_docs;
+  th.postings_len = set_words(s) * sizeof(uint32_t);  // what a set adds to algorithmic_bytes / unique_bytes: its bits
+  th.wants_col = false;
+  th.set_kind = TermHost::kSet;
+  uint32_t handle;
+  if (!s->set_free_slots.empty()) {
+    handle = s->set_free_slots.back();
+    s->set_free_slots.pop_back();
+    s->terms[handle] = th;
+    s->h_dterms[handle] = dt;
+  } else {
+    handle = (uint32_t)s->terms.size();
+    s->terms.push_back(th);
+    s->h_dterms.push_back(dt);
+    ++s->n_set_slots;
+  }
+  mark_term_dirty(s, handle);
+  s->bytes_bitmaps += set_bytes(s);  // (not dense_bytes_total: which ordinary lists get bitmaps does not depend on sets)
+  s->share_span_terms = ~(size_t)0;  // (the tables' address span is taken again: tq_search.cpp)
+  return handle;
+}
 
 int check_set_query(const tq_segment *s, const tq_query &q, uint32_t qi, const char *fn, bool *has) {
   *has = false;
@@ -82,11 +121,8 @@ int tq_term_set_prepare(tq_segment *s, const tq_term_handle *members, uint32_t n
     }
     const size_t n_words = set_words(s);
     void *tab = nullptr;
-    if (!s->set_free_tables.empty()) {
-      tab = s->set_free_tables.back();
-      s->set_free_tables.pop_back();
-    } else {
-      const int arc = dense_alloc(s, (n_words + 1u) * sizeof(uint2), &tab);  // (+ the sentinel entry of every dense table)
+    {
+      const int arc = set_table_acquire(s, &tab);
       if (arc != TQ_OK) return arc;
     }
     const size_t bm_bytes = (bm.size() * sizeof(const uint2 *) + 255) & ~(size_t)255;
@@ -94,7 +130,7 @@ int tq_term_set_prepare(tq_segment *s, const tq_term_handle *members, uint32_t n
     const size_t scratch_words = tqk_termset_scratch_words((uint32_t)n_words);
     int rc = s->d_set_work.ensure(bm_bytes + item_bytes + scratch_words * sizeof(uint32_t));
     if (rc != TQ_OK) {
-      release_set_table(s, tab);
+      set_table_release(s, tab);
       return rc;
     }
     uint8_t *const work = (uint8_t *)s->d_set_work.p;
@@ -127,7 +163,7 @@ int tq_term_set_prepare(tq_segment *s, const tq_term_handle *members, uint32_t n
     if (ev1) (void)hipEventDestroy(ev1);
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(s->stream);
-      release_set_table(s, tab);
+      set_table_release(s, tab);
       return fail(TQ_ERR_HIP, "tq_term_set_prepare: %s", hipGetErrorString(e));
     }
     if (s->opt.timing) {  // (the last call's figures, as after a count or doc-set batch)
@@ -143,31 +179,7 @@ int tq_term_set_prepare(tq_segment *s, const tq_term_handle *members, uint32_t n
       s->stats.algorithmic_bytes = model;
       s->stats.chunks = (uint32_t)bm.size();  // the members that were OR-ed word-wise (the others were scattered)
     }
-    TqdTerm dt{};
-    dt.dense = (const uint2 *)tab;
-    dt.doc_freq = n_docs;
-    dt.has_freq = kConstScoreFlag;
-    TermHost th;
-    th.dense_blob = tab;
-    th.doc_freq = n_docs;
-    th.postings_len = n_words * sizeof(uint32_t);  // what a set adds to algorithmic_bytes / unique_bytes: its bits
-    th.wants_col = false;
-    th.set_kind = TermHost::kSet;
-    uint32_t handle;
-    if (!s->set_free_slots.empty()) {
-      handle = s->set_free_slots.back();
-      s->set_free_slots.pop_back();
-      s->terms[handle] = th;
-      s->h_dterms[handle] = dt;
-    } else {
-      handle = (uint32_t)s->terms.size();
-      s->terms.push_back(th);
-      s->h_dterms.push_back(dt);
-      ++s->n_set_slots;
-    }
-    mark_term_dirty(s, handle);
-    s->bytes_bitmaps += set_bytes(s);  // (not dense_bytes_total: which ordinary lists get bitmaps does not depend on sets)
-    s->share_span_terms = ~(size_t)0;  // (the tables' address span is taken again: tq_search.cpp)
+    const uint32_t handle = set_slot_commit(s, tab, n_docs);
     *out = handle;
     return TQ_OK;
   } catch (const std::exception &e) {
@@ -193,7 +205,7 @@ int tq_term_set_release(tq_segment *s, tq_term_handle set) {
     const int wrc = wait_segment_idle(s);  // batches may run on a caller's stream
     if (wrc != TQ_OK) return wrc;
   }
-  release_set_table(s, s->terms[set].dense_blob);
+  set_table_release(s, s->terms[set].dense_blob);
   s->bytes_bitmaps -= std::min(s->bytes_bitmaps, set_bytes(s));
   s->terms[set] = TermHost{};
   s->terms[set].wants_col = false;

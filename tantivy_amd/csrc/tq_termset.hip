@@ -149,9 +149,15 @@ hipError_t tqk_launch_termset_build(const TqdSegment &seg, const TqdTerm *terms,
   if (n_items) {
     termset_scatter_kernel<<<dim3(std::min<uint32_t>(n_items, 1u << 16)), dim3(256), 0, st>>>(seg, terms, d_items, n_items, tab);
   }
+  return tqk_launch_bitmap_rank(tab, n_words, seg.max_doc, scan_scratch, st);
+}
+
+// the rank stage alone, over a table whose .x words are written: what a term set's build ends with, and what the
+// fast-field columns (tq_column.cpp) run over a presence bitmap and over the bits range_fill_kernel leaves
+hipError_t tqk_launch_bitmap_rank(uint2 *tab, uint32_t n_words, uint32_t max_doc, uint32_t *scan_scratch, hipStream_t st) {
   const uint32_t n_tiles = (n_words + TS_TILE - 1u) / TS_TILE;
   // (a segment without docs: one launch for the sentinel and the count, over no word)
-  termset_sums_kernel<<<dim3(std::max(n_tiles, 1u)), dim3(TS_THREADS), 0, st>>>(tab, n_words, seg.max_doc, scan_scratch);
+  termset_sums_kernel<<<dim3(std::max(n_tiles, 1u)), dim3(TS_THREADS), 0, st>>>(tab, n_words, max_doc, scan_scratch);
   termset_tiles_kernel<<<dim3(1), dim3(TS_THREADS), 0, st>>>(scan_scratch, std::max(n_tiles, 1u));
   termset_rank_kernel<<<dim3(std::max(n_tiles, 1u)), dim3(TS_THREADS), 0, st>>>(tab, n_words, scan_scratch, std::max(n_tiles, 1u));
   return hipGetLastError();
