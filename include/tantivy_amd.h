@@ -811,6 +811,54 @@ int tq_docset_scored_batch_device(tq_segment *seg, const tq_query *queries, uint
                                   uint32_t *d_out_docs, float *d_out_scores, uint64_t out_cap,
                                   uint64_t *d_out_starts, void *hip_stream);
 
+/* ---- sort by fast field ----
+ * replaces: TopDocs::with_limit(k).order_by_fast_field(field, order) / order_by_u64_field / order_by((SortByStaticFastValue,
+ * ComparatorEnum)) on one segment (src/collector/top_score_collector.rs:217-223,299-330; collect_segment_top_k,
+ * src/collector/sort_key/sort_key_computer.rs:118-135): no scoring, the alive filter, and a TopNComputer over
+ * Option<u64> = Column<u64>::first(doc) (sort_by_static_fast_value.rs:62-96).  Row q holds the first min(k, matches) alive
+ * matching docs of query q under compare_for_top_k: the comparator on the key, then ASCENDING doc id whatever the order.
+ * The four ComparatorEnum values are two choices (order.rs:68-221,286-293):
+ *   Natural (= Order::Desc)            TQ_SORT_DESC, TQ_NULLS_LAST
+ *   ReverseNoneLower (= Order::Asc)    TQ_SORT_ASC,  TQ_NULLS_LAST
+ *   Reverse                            TQ_SORT_ASC,  TQ_NULLS_FIRST
+ *   NaturalNoneHigher                  TQ_SORT_DESC, TQ_NULLS_FIRST
+ * Docs without a value (a TQ_CARD_OPTIONAL column) are never dropped: they tie with each other, in doc order, after or
+ * before every doc with a value.  `column` is a handle of tq_column_upload (multivalued columns cannot be uploaded, so
+ * first(doc) is the doc's only value).
+ * tq_query.k is the query's offset+limit, 1..TQ_MAX_K; weights, tf_cache and the pruning fields are ignored (may be NULL).
+ * Outputs: row q = entries [q * out_stride, (q + 1) * out_stride) of out_docs / out_values / out_has_value, in result
+ * order, out_stride >= the largest k; out_values is in the column's u64 space (the caller applies T::from_u64, as the
+ * reference does after the top-k) and 0 where out_has_value is 0; the padding behind out_counts[q] real entries is
+ * (TQ_TERMINATED, 0, 0).  Nothing is written at or past a row's out_stride.
+ * Query shapes: exactly what tq_docset_batch takes under the segment's current options — flat AND / OR / BOOL with
+ * clause_of, MustNot and m-of-n, TQ_TERM_ALL, term-set and range handles as lists; under "docset_trees" = 1 also phrases,
+ * sloppy phrases and nested queries — with tq_docset_batch's refusals, codes and "query N" text under this function's
+ * name: the whole batch fails before any launch and the segment stays usable.  TQ_ERR_INVALID with a message: a column
+ * index out of range or a released column, order or nulls above 1, k of 0 or above TQ_MAX_K, out_stride below the largest k.
+ * No doc set is written: after the doc-set path's scatter / tree / sloppy-phrase launches, one selection launch per
+ * sub-batch (tq_sort.hip: workgroup = (query, slice of the bitmap words); match bits, column decode and a wavefront
+ * top-k over 98-bit keys (class, value or its complement, ~doc)) and, with more than one slice per query (option
+ * "sort_slices"), a merge launch.
+ * Afterwards tq_last_batch_match_counts gives every query's number of alive matches (Count + TopDocs in one pass),
+ * tq_batch_stats.matches their sum, kernel_mask = TQ_KERNEL_SORT (| TQ_KERNEL_DOCSET_TREE | TQ_KERNEL_PHRASE_SLOP where such
+ * a query ran), and
+ *   algorithmic_bytes = the doc-set figure for reading every list's words ONCE (lists x bitmap words x 4; a tree:
+ *                       (lists + 2) x bitmap words x 4)
+ *                     + 8 per matching doc with a value
+ *                     + 8 per matching doc of a TQ_CARD_OPTIONAL column (its presence word)
+ *                     + 13 per row entry written (doc, value, flag). */
+enum tq_sort_order { TQ_SORT_DESC = 0, TQ_SORT_ASC = 1 };
+enum tq_sort_nulls { TQ_NULLS_LAST = 0, TQ_NULLS_FIRST = 1 };
+int tq_search_sorted_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                           uint32_t column, uint8_t order, uint8_t nulls, uint32_t out_stride,
+                           uint32_t *out_docs, uint64_t *out_values, uint8_t *out_has_value, uint32_t *out_counts);
+/* Same with DEVICE outputs on the segment's device, enqueued on hip_stream (NULL = the segment's stream), no host
+ * synchronisation: returns TQ_OK once the work is enqueued, like tq_search_batch_device. */
+int tq_search_sorted_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                                  uint32_t column, uint8_t order, uint8_t nulls, uint32_t out_stride,
+                                  uint32_t *d_out_docs, uint64_t *d_out_values, uint8_t *d_out_has_value,
+                                  uint32_t *d_out_counts, void *hip_stream);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -848,6 +896,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_DOCSET_TREE 0x10000u /* docset_tree_bits_kernel (tq_docset_batch*, option "docset_trees": phrases and nested queries as match bits) */
 #define TQ_KERNEL_DOCSET_TREE_SCORE 0x20000u /* docset_tree_score_kernel (tq_docset_scored_batch*, option "docset_score_trees": the scores of such rows) */
 #define TQ_KERNEL_PHRASE_SLOP 0x40000u /* phrase_slop_kernel / phrase_slop_bits_kernel (TQ_MODE_PHRASE with slop > 0, over bitmap words) */
+#define TQ_KERNEL_SORT 0x80000u        /* sort_select_kernel / sort_merge_kernel (tq_search_sorted_batch*: top k by a fast-field column) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -932,6 +981,10 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        tq_docset_scored_batch_device also take those shapes (TQ_KERNEL_DOCSET_TREE | TQ_KERNEL_DOCSET_TREE_SCORE; weights
  *        and tf_cache required, see "doc sets with scores"); 0: refused with TQ_ERR_UNSUPPORTED as before.  Independent
  *        of "docset_trees", which the unscored variants alone look at,
+ *        "sort_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_search_sorted_batch* — slices of the
+ *        segment's bitmap words per query, one selection workgroup each; 0 = the host chooses (queries x slices fills the
+ *        machine, no slice below 1024 words), 1 = every query's row is written by its one workgroup and no merge is
+ *        launched, 2..256 = forced (a slice past the last word is empty).  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

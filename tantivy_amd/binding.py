@@ -62,12 +62,16 @@ KERNEL_ALL = 0x8000
 KERNEL_DOCSET_TREE = 0x10000
 KERNEL_DOCSET_TREE_SCORE = 0x20000
 KERNEL_PHRASE_SLOP = 0x40000
+KERNEL_SORT = 0x80000
+SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
+NULLS_LAST, NULLS_FIRST = 0, 1  # tq_sort_nulls (NULLS_FIRST: Reverse / NaturalNoneHigher)
+MAX_K = 1024  # TQ_MAX_K
 MAX_SLOP, SLOP_CARRY_CAP = 255, 32  # TQ_MAX_SLOP, TQ_SLOP_CARRY_CAP (include/tantivy_amd.h "Sloppy phrases")
 NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (include/tantivy_amd.h)
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
-                0x20000: "docset_tree_score", 0x40000: "phrase_slop"}
+                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort"}
 
 
 def kernel_names(mask):
@@ -158,6 +162,7 @@ EXPORTS = [
     "tq_term_field", "tqh_searcher_add_segment_fields", "tqh_searcher_add_remote_stats_fields",
     "tq_term_table_read", "tq_term_table_info",
     "tq_column_parse", "tq_column_upload", "tq_column_info", "tq_column_release", "tq_column_decode", "tq_range_prepare",
+    "tq_search_sorted_batch", "tq_search_sorted_batch_device",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -273,6 +278,10 @@ def lib():
     L.tq_column_release.argtypes = [vp, C.c_uint32]
     L.tq_column_decode.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.tq_range_prepare.argtypes = [vp, C.c_uint32, C.c_uint8, C.c_uint64, C.c_uint8, C.c_uint64, C.c_float, u32p, f32p]
+    L.tq_search_sorted_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32,
+                                         u32p, C.POINTER(C.c_uint64), u8p, u32p]
+    L.tq_search_sorted_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32,
+                                                vp, vp, vp, vp, vp]
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -391,6 +400,29 @@ def all_query_form(handles, weights=None, mode=MODE_BOOL, occurs=None, clause_of
     f = TqAllForm()
     rc = lib().tq_all_query_form(C.byref(q), C.byref(f))
     return rc, int(f.kind), float(f.base), int(f.min_should), int(f.keep_mask)
+
+
+def sort_key(value, has_value, order, nulls):
+    """The (class, value') part of the sorted calls' key, in Python ints; SMALLER sorts first.  value' is the value for
+    SORT_ASC and its complement for SORT_DESC; docs without a value after (NULLS_LAST) or before (NULLS_FIRST) the others."""
+    if not has_value:
+        return (0 if nulls == NULLS_FIRST else 2, 0)
+    v = int(value)
+    return (1, v if order == SORT_ASC else (1 << 64) - 1 - v)
+
+
+def merge_sorted_top_k(rows_per_segment, k, order, nulls, offset=0):
+    """The reference's merge_top_k (src/collector/top_score_collector.rs) over the segments' sorted rows of ONE query:
+    rows_per_segment[segment_ord] = (docs, values, has_value, count) as raw_search_sorted returns a row.  The merged order is
+    the comparator on Option<u64>, ties by ascending (segment_ord, doc); -> the entries [offset, offset + k) as a list of
+    (value or None, segment_ord, doc).  Host only."""
+    entries = []
+    for seg_ord, (docs, values, has_value, count) in enumerate(rows_per_segment):
+        for i in range(int(count)):
+            has = bool(has_value[i])
+            entries.append((sort_key(values[i], has, order, nulls), seg_ord, int(docs[i]), int(values[i]) if has else None))
+    entries.sort(key=lambda e: e[:3])
+    return [(v, s, d) for _, s, d, v in entries[int(offset): int(offset) + int(k)]]
 
 
 def term_dictionary_values(field_file):
@@ -1156,6 +1188,59 @@ class DeviceIndex:
         qs, keep = self._raw_flat_queries(queries, segment_ord)
         return lib().tq_docset_batch_device(self.segment_raw(segment_ord), qs, len(queries), d_docs.data_ptr(), int(cap),
                                             d_starts.data_ptr(), C.c_void_p(stream) if stream else None)
+
+    # ---- sort by fast field (tq_sort.cpp, tq_sort.hip)
+    def _raw_sorted_queries(self, queries, ks, segment_ord):
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        ks = [int(ks)] * len(queries) if np.isscalar(ks) else [int(k) for k in ks]
+        assert len(ks) == len(queries)
+        for i, k in enumerate(ks):
+            qs[i].k = k
+        return qs, keep, ks
+
+    def raw_search_sorted(self, queries, column, order, nulls, ks, stride=None, segment_ord=0, device=False):
+        """Direct tq_search_sorted_batch on one segment: the query tuples of raw_docset, `ks` = one k or one per query,
+        stride = the rows' length (default: the largest k).  -> (docs [n, stride] uint32, values [n, stride] uint64,
+        has_value [n, stride] uint8, counts [n] uint32).  device=True: through tq_search_sorted_batch_device into torch
+        tensors on the segment's GPU, copied back after a synchronisation."""
+        n = len(queries)
+        qs, keep, ks = self._raw_sorted_queries(queries, ks, segment_ord)
+        stride = int(stride) if stride is not None else max(ks + [1])
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_docs = torch.full((max(1, n), stride), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            d_vals = torch.full((max(1, n), stride), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_has = torch.full((max(1, n), stride), 0x5A, dtype=torch.uint8, device=dv)
+            d_cnt = torch.full((max(1, n),), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_search_sorted_batch_device(self.segment_raw(segment_ord), qs, n, int(column), int(order), int(nulls),
+                                                       stride, d_docs.data_ptr(), d_vals.data_ptr(), d_has.data_ptr(),
+                                                       d_cnt.data_ptr(), None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            return (d_docs.cpu().numpy().view(np.uint32)[:n], d_vals.cpu().numpy().view(np.uint64)[:n],
+                    d_has.cpu().numpy()[:n], d_cnt.cpu().numpy().view(np.uint32)[:n])
+        docs = np.full((max(1, n), stride), 0xDEADBEEF, np.uint32)
+        vals = np.full((max(1, n), stride), 0xDEADBEEF, np.uint64)
+        has = np.full((max(1, n), stride), 0xEF, np.uint8)
+        counts = np.full(max(1, n), 0xDEADBEEF, np.uint32)
+        _check(lib().tq_search_sorted_batch(self.segment_raw(segment_ord), qs, n, int(column), int(order), int(nulls), stride,
+                                            _u32(docs), vals.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            has.ctypes.data_as(C.POINTER(C.c_uint8)), _u32(counts)))
+        return docs[:n], vals[:n], has[:n], counts[:n]
+
+    def raw_search_sorted_device(self, queries, column, order, nulls, ks, stride, d_docs, d_values, d_has_value, d_counts,
+                                 segment_ord=0, stream=None):
+        """Direct tq_search_sorted_batch_device: d_docs (int32 / uint32), d_values (int64 / uint64), d_has_value (uint8) with
+        len(queries) * stride entries and d_counts (int32 / uint32, len(queries)) are torch tensors on the segment's GPU;
+        only enqueues.  -> rc"""
+        qs, keep, ks = self._raw_sorted_queries(queries, ks, segment_ord)
+        return lib().tq_search_sorted_batch_device(self.segment_raw(segment_ord), qs, len(queries), int(column), int(order),
+                                                   int(nulls), int(stride), d_docs.data_ptr(), d_values.data_ptr(),
+                                                   d_has_value.data_ptr(), d_counts.data_ptr(),
+                                                   C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

@@ -28,6 +28,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_docset_score_fields.hip"),
     os.path.join(HERE, "csrc", "tq_docset_tree.hip"),
     os.path.join(HERE, "csrc", "tq_docset_tree_score.hip"),
+    os.path.join(HERE, "csrc", "tq_sort.hip"),
+    os.path.join(HERE, "csrc", "tq_sort.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -54,6 +56,8 @@ SOURCES = [
 ]
 HEADERS = [
     os.path.join(HERE, "csrc", "tq_common.hpp"),
+    os.path.join(HERE, "csrc", "tq_column_read.hpp"),
+    os.path.join(HERE, "csrc", "tq_docset_word.hpp"),
     os.path.join(HERE, "csrc", "tq_device.h"),
     os.path.join(HERE, "csrc", "tq_launch.h"),
     os.path.join(HERE, "csrc", "tq_fields.h"),
@@ -88,7 +92,8 @@ def csrc_hash():
 KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip", "union_kernel": "tq_union.hip",
                 "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "docset_tree_score_kernel": "tq_docset_tree_score.hip", "tree_kernel": "tq_tree.hip", "tree_fields_kernel": "tq_tree_fields.hip", "docset_score_fields_kernel": "tq_docset_score_fields.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
                 "phrase_sweep_kernel": "tq_phrase.hip", "phrase_kernel": "tq_phrase.hip",
-                "phrase_slop_kernel": "tq_phrase_slop.hip", "phrase_slop_bits_kernel": "tq_phrase_slop.hip"}
+                "phrase_slop_kernel": "tq_phrase_slop.hip", "phrase_slop_bits_kernel": "tq_phrase_slop.hip",
+                "sort_select_kernel": "tq_sort.hip", "sort_merge_kernel": "tq_sort.hip"}
 
 
 def kernel_hash(kernel_names, read=None):

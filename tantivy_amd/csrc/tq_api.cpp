@@ -115,7 +115,8 @@ static int segment_upload_common(tq_ctx *ctx, int device, uint32_t max_doc, cons
       if (e == hipSuccess) e = hipEventCreate(&s->ev_k0[i]);
       if (e == hipSuccess) e = hipEventCreate(&s->ev_k1[i]);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, sizeof(unsigned long long));
+    // (word 0: the batch's matches; words 1 and 2: a sorted batch's valued matches and row entries, tq_sort.hip)
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 3u * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_tp_info, 2 * sizeof(TqpInfo));
     if (e != hipSuccess) rc = fail(TQ_ERR_HIP, "segment setup: %s", hipGetErrorString(e));
   }
@@ -292,6 +293,10 @@ void tq_segment_free(tq_segment *s) {
   s->d_docset_caches.release();
   s->d_docset_scores.release();
   s->d_docset_trees.release();
+  s->d_sort_ks.release();
+  s->d_sort_partials.release();
+  s->d_sort_slice_counts.release();
+  s->d_sort_rows.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
@@ -437,9 +442,19 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
       if (wrc != TQ_OK) return wrc;
     }
     unsigned long long m = 0;
-    HIP_TRY(hipMemcpy(&m, s->d_match_counter, sizeof m, hipMemcpyDeviceToHost));
-    s->stats.matches = m;
-    s->stats.algorithmic_bytes += m * s->stats_match_bytes;  // 1 fieldnorm byte per scored doc; 4 per doc of a doc set
+    if (s->stats_sorted) {  // a sorted batch: matches, matches with a value, row entries written
+      unsigned long long t[3] = {0, 0, 0};
+      HIP_TRY(hipMemcpy(t, s->d_match_counter, sizeof t, hipMemcpyDeviceToHost));
+      m = t[0];
+      s->stats.matches = m;
+      // a value per valued match, a presence word per match of an Optional column, 13 per entry (doc, value, flag)
+      s->stats.algorithmic_bytes += 8u * t[1] + (s->stats_sorted_optional ? 8u * t[0] : 0u) + 13u * t[2];
+      s->stats_sorted = false;
+    } else {
+      HIP_TRY(hipMemcpy(&m, s->d_match_counter, sizeof m, hipMemcpyDeviceToHost));
+      s->stats.matches = m;
+      s->stats.algorithmic_bytes += m * s->stats_match_bytes;  // 1 fieldnorm byte per scored doc; 4 per doc of a doc set
+    }
     if (s->opt.timing) {
       uint64_t first = s->batches_reported;
       if (s->batches_timed - first > (uint64_t)tq_segment::kTimingRing)
@@ -553,6 +568,8 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.docset_trees = (int)value;
   else if (!strcmp(name, "docset_score_trees") && (value == 0 || value == 1))
     s->opt.docset_score_trees = (int)value;
+  else if (!strcmp(name, "sort_slices") && value >= 0 && value <= 256)
+    s->opt.sort_slices = (int)value;
   else if (!strcmp(name, "ashare_inline_warm") && value >= 0 && value <= 2)
     s->opt.ashare_inline_warm = (int)value;
   else if (!strcmp(name, "ashare_min_batch") && value >= 0 && value <= 0x7FFFFFFF)

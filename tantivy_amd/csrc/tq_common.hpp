@@ -441,6 +441,70 @@ struct TopK {
   }
 };
 
+// TopK's sibling for keys wider than 64 bits (tq_sort.hip: class, 64-bit sort value, ~doc — 98 bits): a key is the pair
+// (hi, lo) compared lexicographically, larger is better, (0, 0) is the empty slot.  Same layout and insertion as TopK:
+// rank r*64+lane, descending, the k-th key as a strict threshold.
+__device__ __forceinline__ bool key2_gt(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl) {
+  return ah > bh || (ah == bh && al > bl);
+}
+template <int KPL>
+struct TopKW {
+  uint64_t hi[KPL], lo[KPL];
+  uint64_t thr_hi, thr_lo;  // k-th key ((0, 0) while not full)
+  uint32_t k;
+  __device__ __forceinline__ void reset(uint32_t kk) {
+#pragma unroll
+    for (int r = 0; r < KPL; ++r) hi[r] = lo[r] = 0;
+    thr_hi = thr_lo = 0;
+    k = kk;
+  }
+  __device__ __forceinline__ void refresh_thr() {
+    const uint32_t kr = (k - 1u) >> 6, kl = (k - 1u) & 63u;
+    uint64_t th = 0, tl = 0;
+#pragma unroll
+    for (int r = 0; r < KPL; ++r)
+      if ((uint32_t)r == kr) {
+        th = readlane64(hi[r], kl);
+        tl = readlane64(lo[r], kl);
+      }
+    thr_hi = th;
+    thr_lo = tl;
+  }
+  // every lane may offer one candidate
+  __device__ __forceinline__ void offer(bool has, uint64_t khi, uint64_t klo, int lane) {
+    uint64_t m = __ballot(has && key2_gt(khi, klo, thr_hi, thr_lo));
+    while (m) {
+      const uint32_t src = (uint32_t)__builtin_ctzll(m);
+      m &= m - 1;
+      const uint64_t nh = readlane64(khi, src), nl = readlane64(klo, src);
+      if (!key2_gt(nh, nl, thr_hi, thr_lo)) continue;
+      uint32_t pos = 0;
+#pragma unroll
+      for (int r = 0; r < KPL; ++r) pos += (uint32_t)__popcll(__ballot(key2_gt(hi[r], lo[r], nh, nl)));
+#pragma unroll
+      for (int r = KPL - 1; r >= 0; --r) {
+        uint64_t uh = __shfl_up(hi[r], 1, WAVE), ul = __shfl_up(lo[r], 1, WAVE);
+        if (r > 0) {
+          const uint64_t ch = readlane64(hi[r - 1], 63), cl = readlane64(lo[r - 1], 63);
+          if (lane == 0) {
+            uh = ch;
+            ul = cl;
+          }
+        }
+        const uint32_t rank = (uint32_t)r * 64u + (uint32_t)lane;
+        if (rank > pos) {
+          hi[r] = uh;
+          lo[r] = ul;
+        } else if (rank == pos) {
+          hi[r] = nh;
+          lo[r] = nl;
+        }
+      }
+      refresh_thr();
+    }
+  }
+};
+
 __device__ __forceinline__ void wave_mem_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();

@@ -14,6 +14,9 @@
 // next to the flat pass — which is launched over the runs of flat queries between the trees and so writes nothing over a
 // tree's row.  The lists' tables (their own or the probe pool's) live for the whole call; only the result bits are the
 // sub-batch's, and the scoring pass does not read them.
+// A SortSpec (tq_search_sorted_batch*, tq_sort.cpp): everything in front of a sub-batch's passes is the same — checks,
+// expressions, tree / slop planning, sub-batches, scatter, tree bits — and the selection launch(es) of tq_sort.hip take the
+// place of its count / scan / write passes; the rows go to the spec's device arrays under the caller's query index.
 #include "tq_internal.hpp"
 
 #include <deque>
@@ -165,12 +168,12 @@ enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
 
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only,
-                 const uint32_t *caller_q, uint32_t n_caller) {
+                 const uint32_t *caller_q, uint32_t n_caller, const SortSpec *sort) {
   // (tq_count_batch hands over a sub-array of its batch: what this call says about a sloppy phrase — refusals, the
   // overflow words — it says under the CALLER's index)
   auto named = [&](uint32_t qi) { return caller_q ? caller_q[qi] : qi; };
   const uint32_t n_over_words = caller_q ? n_caller : n_queries;
-  const char *const fn = count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
+  const char *const fn = sort ? sort->fn : count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
                                 : (device_out ? "tq_docset_batch_device" : "tq_docset_batch");
   // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
   static const uint32_t kStageMin = tune_u32("TQ_DOCSET_STAGE_MIN", 2048);
@@ -390,12 +393,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (wrc != TQ_OK) return wrc;
   }
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = TQ_KERNEL_DOCSET | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
+  s->stats.kernel_mask = (sort ? TQ_KERNEL_SORT : TQ_KERNEL_DOCSET) | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
                          (scored && !tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u) | (slop_qs.empty() ? 0u : TQ_KERNEL_PHRASE_SLOP);
   s->stats.algorithmic_bytes = algo_bytes;
   s->stats_pending = false;
   s->last_batch_queries = 0;
-  if (n_queries == 0 || n_tiles == 0) {  // no query, or a segment without docs: empty rows
+  if (!sort && (n_queries == 0 || n_tiles == 0)) {  // no query, or a segment without docs: empty rows
     if (device_out) {
       HIP_TRY(hipMemsetAsync(out_starts, 0, ((size_t)n_queries + 1u) * sizeof(uint64_t), st));
     } else {
@@ -417,7 +420,30 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   // (the sloppy phrases' records ride behind the tree records and their map, 64-byte aligned, in both buffers)
   const size_t slop_off = (tree_bytes + tree_map_bytes + 63u) & ~(size_t)63, slop_bytes = slop_qs.size() * sizeof(TqdSlopQuery);
   const size_t tree_blob_bytes = slop_bytes ? slop_off + slop_bytes : tree_bytes + tree_map_bytes;
-  int rc = s->h_docset.ensure(((q_bytes + wg_bytes + sq_bytes + cache_bytes + 63u) & ~(size_t)63) + tree_blob_bytes + 64u);
+  // a sorted call: the slices per query — enough workgroups for the machine, no slice below 1024 words (four steps), or what
+  // "sort_slices" forces —, the key slots per lane its largest k needs, and every query's k behind the blobs above
+  uint32_t sort_slices = 1, sort_wps = n_words, sort_kpl = 1;
+  const size_t ks_off = ((q_bytes + wg_bytes + sq_bytes + cache_bytes + 63u) & ~(size_t)63) + ((tree_blob_bytes + 63u) & ~(size_t)63);
+  const size_t ks_bytes = sort ? (size_t)n_queries * sizeof(uint32_t) : 0u;
+  if (sort) {
+    uint32_t max_k = 1;
+    for (uint32_t qi = 0; qi < n_queries; ++qi) max_k = std::max(max_k, queries[qi].k);
+    sort_kpl = max_k <= 64u ? 1 : max_k <= 256u ? 4 : 16;
+    if (s->opt.sort_slices > 0) {
+      sort_slices = (uint32_t)s->opt.sort_slices;
+    } else {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) cus = 256;
+      const uint32_t want = ((uint32_t)cus * 4u + max_sub_n - 1u) / std::max(1u, max_sub_n);
+      sort_slices = std::max(1u, std::min({want, 256u, n_words / (4u * tqk_sort_step_words())}));
+    }
+    sort_wps = (n_words + sort_slices - 1u) / sort_slices;
+  }
+  const size_t sort_part_bytes = sort_slices > 1u ? (size_t)max_sub_n * sort_slices * (size_t)sort_kpl * 64u * 2u * sizeof(uint64_t) : 0u;
+  int rc = s->h_docset.ensure(ks_off + ks_bytes + 64u);
+  if (rc == TQ_OK && sort) rc = s->d_sort_ks.ensure(ks_bytes);
+  if (rc == TQ_OK && sort_part_bytes) rc = s->d_sort_partials.ensure(sort_part_bytes);
+  if (rc == TQ_OK && sort_part_bytes) rc = s->d_sort_slice_counts.ensure((size_t)max_sub_n * sort_slices * sizeof(uint2));
   if (rc == TQ_OK && tree_blob_bytes) rc = s->d_docset_trees.ensure(tree_blob_bytes);
   if (rc == TQ_OK && slop_bytes) rc = s->d_slop_over.ensure((size_t)n_over_words * sizeof(uint32_t));
   if (rc == TQ_OK && scored) rc = s->d_docset_squeries.ensure(sq_bytes);
@@ -425,9 +451,9 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
   if (rc == TQ_OK) rc = s->d_count_wgs.ensure(wg_bytes);
   if (rc == TQ_OK) rc = s->d_count_bits.ensure((size_t)max_sub_temp * words_per_list * sizeof(uint32_t));
-  if (rc == TQ_OK) rc = s->d_docset_counts.ensure(max_entries * sizeof(uint32_t));
-  if (rc == TQ_OK) rc = s->d_docset_offs.ensure(max_entries * sizeof(uint64_t));
-  if (rc == TQ_OK) rc = s->d_docset_partials.ensure(((max_entries + tqk_docset_scan_tile() - 1) / tqk_docset_scan_tile()) * sizeof(uint64_t));
+  if (rc == TQ_OK && !sort) rc = s->d_docset_counts.ensure(max_entries * sizeof(uint32_t));
+  if (rc == TQ_OK && !sort) rc = s->d_docset_offs.ensure(max_entries * sizeof(uint64_t));
+  if (rc == TQ_OK && !sort) rc = s->d_docset_partials.ensure(((max_entries + tqk_docset_scan_tile() - 1) / tqk_docset_scan_tile()) * sizeof(uint64_t));
   if (rc == TQ_OK) rc = s->d_qmatches.ensure((size_t)n_queries * sizeof(uint32_t));
   if (rc == TQ_OK && !device_out) rc = s->d_docset_starts.ensure(((size_t)n_queries + 1u) * sizeof(uint64_t));
   if (rc != TQ_OK) return rc;
@@ -461,6 +487,12 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     if (slop_bytes) memcpy(h_tq + slop_off, slop_qs.data(), slop_bytes);
     HIP_TRY(hipMemcpyAsync(s->d_docset_trees.p, h_tq, tree_blob_bytes, hipMemcpyHostToDevice, st));
+  }
+  if (sort) {  // every query's k, and the three totals the selection adds to
+    uint32_t *const h_ks = (uint32_t *)((uint8_t *)s->h_docset.p + ks_off);
+    for (uint32_t qi = 0; qi < n_queries; ++qi) h_ks[qi] = queries[qi].k;
+    HIP_TRY(hipMemcpyAsync(s->d_sort_ks.p, h_ks, ks_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, 3u * sizeof(unsigned long long), st));
   }
   if (slop_bytes) {  // the overflow words, one per query of the batch (tq_last_batch_slop_overflows)
     HIP_TRY(hipMemsetAsync(s->d_slop_over.p, 0, (size_t)n_over_words * sizeof(uint32_t), st));
@@ -522,6 +554,32 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     p.max_doc = s->max_doc;
     p.stage_min_docs = kStageMin;
     hipError_t e = hipSuccess;
+    if (sort) {  // the selection in place of the count / scan / write passes: rows under the caller's query index
+      const tq_segment::ColumnHost &col = s->columns[sort->column];
+      TqkSortParams sp{};
+      sp.ds = p;
+      sp.col = col.dev;
+      sp.min_value = col.info.min_value;
+      sp.gcd = col.info.gcd;
+      sp.ks = (const uint32_t *)s->d_sort_ks.p + sb.q0;
+      sp.partials = (uint64_t *)s->d_sort_partials.p;
+      sp.slice_counts = (uint2 *)s->d_sort_slice_counts.p;
+      sp.out_docs = sort->d_docs + (size_t)sb.q0 * sort->out_stride;
+      sp.out_values = sort->d_values + (size_t)sb.q0 * sort->out_stride;
+      sp.out_has_value = sort->d_has_value + (size_t)sb.q0 * sort->out_stride;
+      sp.out_counts = sort->d_counts + sb.q0;
+      sp.query_sizes = p.query_sizes;
+      sp.totals = s->d_match_counter;
+      sp.n_slices = sort_slices;
+      sp.words_per_slice = sort_wps;
+      sp.out_stride = sort->out_stride;
+      sp.ascending = sort->ascending;
+      sp.nulls_first = sort->nulls_first;
+      e = tqk_launch_sort_select(sp, (int)sort_kpl, st);
+      if (e == hipSuccess) e = tqk_launch_sort_merge(sp, (int)sort_kpl, st);
+      if (e != hipSuccess) return fail(TQ_ERR_HIP, "sort kernel launch: %s", hipGetErrorString(e));
+      return TQ_OK;
+    }
     if (stages & DS_COUNT) {
       e = tqk_launch_docset_count(p, st);
       if (e == hipSuccess) e = tqk_launch_docset_scan(p, st);
@@ -596,6 +654,8 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     s->stats_pending = true;  // the total is on the device: tq_last_batch_stats reads it
     s->stats_match_bytes = scored ? 9 : 4;  // doc [+ score + fieldnorm byte]
+    s->stats_sorted = sort != nullptr;    // (its own byte model: tq_last_batch_stats)
+    s->stats_sorted_optional = sort && s->columns[sort->column].dev.present != nullptr;
     HIP_TRY(hipEventRecord(s->ev_batch_done, st));
     s->last_stream = st;
     s->batch_in_flight = true;

@@ -17,6 +17,7 @@
 //           (TQ_DOCSET_STAGE_MIN, 2048 of 65 536: measured in DESIGN.md 3.4a).  Every store is guarded by pos < out_cap.
 // HBM model: 2 x lists x 8 (4 for scattered lists) bytes per 32 docs read, 4 bytes per doc written.
 #include "tq_common.hpp"
+#include "tq_docset_word.hpp"  // SlicedCount / docset_head / docset_word / wave_incl_sum
 #include "tq_launch.h"
 
 namespace {
@@ -27,104 +28,6 @@ constexpr uint32_t DS_WORDS_PER_THREAD = 8;
 constexpr uint32_t DS_TILE_WORDS = DS_THREADS * DS_WORDS_PER_THREAD;  // 2048 words = 65 536 docs
 constexpr uint32_t DS_SCAN_PER_THREAD = 8;
 constexpr uint32_t DS_SCAN_TILE = DS_THREADS * DS_SCAN_PER_THREAD;  // table entries per scan workgroup
-
-// Bit-sliced counter of one-bit-per-doc inputs saturating at 15, the SlicedCount of tq_tree.hip (kept in step with
-// it by tests/test_gpu_docset.py's m-of-n shapes against the oracle): "at least m of the Should clauses", m <= 15.
-struct SlicedCount {
-  uint32_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-  __device__ __forceinline__ void add(uint32_t x) {
-    uint32_t c = p0 & x;
-    p0 ^= x;
-    x = c;
-    c = p1 & x;
-    p1 ^= x;
-    x = c;
-    c = p2 & x;
-    p2 ^= x;
-    x = c;
-    c = p3 & x;  // the carry out of the top plane: the count sticks at 15
-    p3 ^= x;
-    p0 |= c;
-    p1 |= c;
-    p2 |= c;
-    p3 |= c;
-  }
-  __device__ __forceinline__ uint32_t at_least(uint32_t m) const {  // m wave-uniform, 1..15
-    uint32_t gt = 0u, eq = 0xFFFFFFFFu;
-    const uint32_t pl[4] = {p0, p1, p2, p3};
-#pragma unroll
-    for (int i = 3; i >= 0; --i) {
-      if ((m >> i) & 1u) {
-        eq &= pl[i];
-      } else {
-        gt |= eq & pl[i];
-        eq &= ~pl[i];
-      }
-    }
-    return gt | eq;
-  }
-};
-
-struct DocsetHead {  // the scalar part of a TqkDocsetQuery
-  uint32_t n_terms, kinds, clause_end, should_end, narrow, min_should;
-};
-
-// The 32 result bits of bitmap word w (w < n_words) of one query: alive docs below max_doc only.
-__device__ __forceinline__ uint32_t docset_word(const TqkDocsetQuery *Q, const DocsetHead &h, const TqkDocsetParams &p,
-                                                uint32_t w) {
-  uint32_t must = 0xFFFFFFFFu, nots = 0u, clause = 0u, any = 0u, sclause = 0u;
-  SlicedCount sc;
-  for (uint32_t m = 0; m < h.n_terms; ++m) {
-    const uint32_t bits = ((h.narrow >> m) & 1u) ? reinterpret_cast<const uint32_t *>(Q->dense[m])[w] : Q->dense[m][w].x;
-    const uint32_t kind = (h.kinds >> (2u * m)) & 3u;
-    if (kind == TQK_COUNT_MUST) {
-      clause |= bits;
-      if ((h.clause_end >> m) & 1u) {
-        must &= clause;
-        clause = 0u;
-      }
-    } else if (kind == TQK_COUNT_NOT) {
-      nots |= bits;
-    } else {
-      sclause |= bits;
-      if ((h.should_end >> m) & 1u) {  // a Should clause (the OR of its lists) counts once
-        any |= sclause;
-        if (h.min_should >= 2u) sc.add(sclause);
-        sclause = 0u;
-      }
-    }
-  }
-  uint32_t res = must & ~nots;
-  if (h.min_should == 1u)
-    res &= any;
-  else if (h.min_should >= 2u)
-    res &= sc.at_least(h.min_should);
-  // AliveBitSet: bit d of byte d >> 3 (alive_bitset.rs:58-61) = bit d & 31 of little-endian word d >> 5
-  if (p.alive) res &= reinterpret_cast<const uint32_t *>(p.alive)[w];
-  // the segment's last word: an expression without Must lists is all ones there whatever the inputs hold
-  if (w == p.n_words - 1u && (p.max_doc & 31u)) res &= (1u << (p.max_doc & 31u)) - 1u;
-  return res;
-}
-
-__device__ __forceinline__ DocsetHead docset_head(const TqkDocsetQuery *Q) {
-  DocsetHead h;
-  h.n_terms = sload(&Q->n_terms);
-  h.kinds = sload(&Q->kinds);
-  h.clause_end = sload(&Q->clause_end);
-  h.should_end = sload(&Q->should_end);
-  h.narrow = sload(&Q->narrow);
-  h.min_should = sload(&Q->min_should);
-  return h;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(DS_THREADS) void docset_count_kernel(TqkDocsetParams p) {
   __shared__ uint32_t wave_cnt[DS_WAVES];

@@ -204,6 +204,7 @@ struct Options {
   int docset_temp_lists = 0;     // doc sets: lists without a bitmap scattered per launch (0 = what TQ_COUNT_TEMP_MB holds, at most 4096)
   int docset_trees = 0;          // doc sets: phrases and nested boolean queries through tq_docset_tree.hip (0 = refused, as before)
   int docset_score_trees = 0;    // scored doc sets: the same shapes, scored by tq_docset_tree_score.hip (0 = refused, as before)
+  int sort_slices = 0;           // sort by fast field: slices of the bitmap words per query (0 = the host chooses, 1..256 = forced)
   int ashare_inline_warm = 1;   // intersections: 0 = warm-up and main tasks as two dispatches, 1 = ONE dispatch where they are the batch's only
                                 // group and tasks of leaders without warm-up tasks fill the grid (build_ashare_plan), 2 = always one dispatch
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
@@ -352,11 +353,13 @@ struct tq_segment {
   // ... with scores (tq_docset_score.hip): scoring descriptors, the batch's Bm25Weight caches, the host variant's scores
   DevBuf d_docset_squeries, d_docset_caches, d_docset_scores;
   DevBuf d_docset_trees;  // ... of phrases and nested queries (tq_docset_tree.hip): their TqdTreeQuery records
+  // sort by fast field (tq_sort.hip): the queries' k, the slices' lists and counts, the host variant's rows
+  DevBuf d_sort_ks, d_sort_partials, d_sort_slice_counts, d_sort_rows;
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
            d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap +
-           d_docset_trees.cap;
+           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -445,6 +448,10 @@ struct tq_segment {
   bool stats_pending = false;
   uint32_t stats_match_bytes = 1;  // what a match adds to algorithmic_bytes once d_match_counter is read: a fieldnorm
                                    // byte per scored doc, 4 bytes per doc of a doc-set batch on the device (9 with scores)
+  // the pending batch is a sorted one (tq_search_sorted_batch*): d_match_counter[0..2] = matches, matches with a value, row
+  // entries written, which tq_last_batch_stats turns into bytes (8 per valued match, 8 per match of an Optional column, 13
+  // per entry); set or cleared wherever stats_pending is set
+  bool stats_sorted = false, stats_sorted_optional = false;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -1027,9 +1034,23 @@ void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, T
 // out_docs / out_scores / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on
 // hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used;
 // count_only (host outputs): the count pass and the row starts alone, no doc is written (tq_count_batch's ALL-BASED queries)
+// Sort by fast field (tq_sort.cpp): with a SortSpec the call validates, plans, cuts sub-batches, scatters and evaluates trees
+// and sloppy phrases exactly as for a doc set, and the selection launch(es) of tq_sort.hip take the place of every
+// sub-batch's count / scan / write passes.  Everything is enqueued (device_out = true; the pointers are DEVICE memory, the
+// rows of query q at q * out_stride); out_docs / out_scores / out_cap / out_starts of the call are not used.
+struct SortSpec {
+  const char *fn;  // the entry point's name, for messages
+  uint32_t column;
+  uint32_t ascending, nulls_first;
+  uint32_t out_stride;
+  uint32_t *d_docs;
+  uint64_t *d_values;
+  uint8_t *d_has_value;
+  uint32_t *d_counts;
+};
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false,
-                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0);
+                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0, const SortSpec *sort = nullptr);
 // (caller_q / n_caller — tq_count_batch, which hands over a sub-array of its n_caller queries: query qi of this call is
 // the caller's caller_q[qi]; sloppy phrases are named, and their overflow words indexed, by that)
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights

@@ -437,6 +437,31 @@ hipError_t tqk_launch_docset_scan(const TqkDocsetParams &p, hipStream_t st);
 hipError_t tqk_launch_docset_write(const TqkDocsetParams &p, hipStream_t st);
 uint32_t tqk_docset_tile_words();
 uint32_t tqk_docset_scan_tile();
+// ---- sort by fast field (tq_sort.hip): the top k of a doc set under a u64 column's order (tq_search_sorted_batch*).
+// The selection launch: workgroup = (query, slice of the bitmap words), query fastest; with n_slices == 1 it writes the
+// rows, else a sorted partial list per (query, slice) that the merge launch, one wavefront per query, reduces.
+struct TqkSortParams {
+  TqkDocsetParams ds;          // queries (one sub-batch), alive, n_queries, n_words, max_doc: what docset_word reads
+  TqkColumn col;               // the sort column
+  uint64_t min_value, gcd;     // value = min + gcd * packed (Linear: the packed value itself)
+  const uint32_t *ks;          // [n_queries] every query's k, 1..TQ_MAX_K
+  uint64_t *partials;          // [n_queries][n_slices][2][kpl * 64]: the slices' lists, hi words then lo words (n_slices > 1)
+  uint2 *slice_counts;         // [n_queries][n_slices] {matches, matches with a value} (n_slices > 1)
+  uint32_t *out_docs;          // rows of the sub-batch's first query on: [n_queries][out_stride]
+  uint64_t *out_values;
+  uint8_t *out_has_value;
+  uint32_t *out_counts;        // [n_queries]
+  uint32_t *query_sizes;       // [n_queries] alive matches per query
+  unsigned long long *totals;  // [3] += matches, matches with a value, row entries written (zeroed by the caller)
+  uint32_t n_slices, words_per_slice;
+  uint32_t out_stride;
+  uint32_t ascending;          // TQ_SORT_ASC
+  uint32_t nulls_first;        // TQ_NULLS_FIRST
+};
+// kpl: key slots per lane, 1 / 4 / 16 (k <= 64 / 256 / 1024 for every query of the launch)
+hipError_t tqk_launch_sort_select(const TqkSortParams &p, int kpl, hipStream_t st);
+hipError_t tqk_launch_sort_merge(const TqkSortParams &p, int kpl, hipStream_t st);
+uint32_t tqk_sort_step_words();  // bitmap words a selection workgroup takes per step
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)

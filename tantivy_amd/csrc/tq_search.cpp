@@ -1519,6 +1519,7 @@ int finish_batch(const Batch &b) {
   b.s->stats.unique_bytes = b.unique_bytes;
   b.s->stats_pending = true;
   b.s->stats_match_bytes = 1;
+  b.s->stats_sorted = false;
   return TQ_OK;
 }
 
