@@ -859,6 +859,98 @@ int tq_search_sorted_batch_device(tq_segment *seg, const tq_query *queries, uint
                                   uint32_t *d_out_docs, uint64_t *d_out_values, uint8_t *d_out_has_value,
                                   uint32_t *d_out_counts, void *hip_stream);
 
+/* ---- aggregations over a fast field: stats and histogram ----
+ * replaces, on one segment and for every query of a batch: a `stats` metric (count / sum / min / max / avg:
+ * src/aggregation/metric/stats.rs:86-176, IntermediateStats::collect and finalize) and optionally a `histogram` bucket
+ * aggregation — which with nanosecond arguments is also `date_histogram` with a fixed_interval — over a resident u64
+ * column (src/aggregation/bucket/histogram/histogram.rs:468-518 collect, :672-699 normalize_histogram_req, :738-769
+ * get_bucket_pos_f64 and compute_dense_range; src/aggregation/mod.rs:351-383 f64_from_fastfield_u64; common/src/lib.rs:
+ * 108-114 u64_to_f64), over the query's ALIVE MATCHING docs, in one pass over its match bits: no doc set is written.
+ *
+ * Value types: TQ_VALUE_U64 (also Bool), TQ_VALUE_I64 (also DateTime, nanoseconds), TQ_VALUE_F64 — how the column's u64
+ * space maps back (MonotonicallyMappableToU64).
+ *
+ * Stats, one tq_agg_stats_t per query:
+ *   matches               alive matching docs            count        those with a value (a TQ_CARD_OPTIONAL column)
+ *   min_value, max_value  in the column's U64 SPACE; UINT64_MAX / 0 when count == 0.  The three mappings keep order, so the
+ *                         caller converts after the fact, as for out_values of the sorted call
+ *   sum_lo, sum_hi        the exact 128-bit sum of the u64-space values.  U64: the sum.  I64: subtract count * 2^63.  The
+ *                         reference adds f64 with Kahan's algorithm in doc order; the integer sum is exact and order-free
+ *                         and equals it wherever every partial sum is below 2^53.  TQ_VALUE_F64: a sum in u64 space means
+ *                         nothing — both words are WRITTEN AS 0 (F64 sums are not served)
+ *   in_bounds             docs with a value inside the histogram's bounds = the sum of the row (0 without a histogram)
+ *   out_of_range          docs inside the bounds whose bucket fell outside the row: always 0 (see below), never written
+ * NaNs of an F64 column sit at the two ends of the mapped order, so min_value / max_value can be a NaN where the
+ * reference's f64::min / f64::max skip NaNs: not emulated.
+ *
+ * Histogram (histogram != 0).  Per doc with a value: val = f64_from_fastfield_u64(value) — U64 (double)v, I64
+ * (double)(int64_t)(v ^ 1 << 63), F64 from_bits(v & 1 << 63 ? v ^ 1 << 63 : ~v); if bounds_min <= val && val <= bounds_max
+ * the doc counts in bucket pos = (int64)floor((val - offset) / interval), the cast saturating.  The bounds are the hard
+ * bounds, or (-DBL_MAX, DBL_MAX) without them — the test is always made, so +-inf and NaN are never counted — and hard
+ * bounds that cannot exclude a value of the column (col min >= hard_min && col max <= hard_max) collapse to that
+ * sentinel.  Rows are DENSE over compute_dense_range: lo = max(f(col min), bounds_min), hi = min(f(col max), bounds_max),
+ * nothing when lo > hi (or the column has no row), base_pos = pos(lo), n_buckets = pos(hi) - base_pos + 1; entry i of a
+ * row is bucket base_pos + i, whose key is (base_pos + i) * interval + offset.  Subtraction, division by a positive
+ * interval and floor are monotonic, so every counted doc falls inside the row; the kernel still checks.  All of it is
+ * IEEE double arithmetic without contraction: device, host and any model agree bit for bit.  Date columns: interval,
+ * offset and bounds in nanoseconds (normalize_date_time applied by the caller).  Keys, gap filling, extended_bounds,
+ * min_doc_count, keyed and ordering are the caller's post-processing.
+ *
+ * tq_agg_histogram_plan is the host-only part (no device, like tq_column_parse): validation and the dense range, from a
+ * column's tq_column_info_t.  n_buckets == 0 when no value can be in bounds.  TQ_ERR_INVALID: interval <= 0 or not
+ * finite, offset not finite, hard bounds not finite or hard_min > hard_max, value_type above TQ_VALUE_F64.
+ * TQ_ERR_UNSUPPORTED naming the count: more than TQ_AGG_MAX_BUCKETS buckets (the reference's DEFAULT_BUCKET_LIMIT of 65 000
+ * rounded up to a power of two).  With histogram == 0 only value_type is checked and the plan is empty.
+ *
+ * tq_agg_batch: host outputs, blocking.  Buckets are uint32_t (a segment has fewer than 2^31 docs); row q = out_buckets +
+ * q * bucket_stride, of which entries [0, n_buckets) are written and NOTHING else; bucket_stride < n_buckets is
+ * TQ_ERR_INVALID; out_buckets may be NULL when histogram == 0 (or n_buckets == 0).  tq_query.k is ignored; weights,
+ * tf_cache and the pruning fields too.  Query shapes, options ("docset_trees", "docset_temp_lists"), refusals, codes and
+ * "query N" texts are tq_docset_batch's under this function's name, as for tq_search_sorted_batch; a column index out of
+ * range or a released column, and what the plan refuses, fail the whole batch before any launch and leave the segment
+ * usable.  A sloppy phrase whose carried list went over the cap: TQ_ERR_UNSUPPORTED naming it after the rows are written,
+ * as for tq_search_sorted_batch (the device variant: tq_last_batch_slop_overflows).
+ * Launches: after the doc-set path's scatter / tree / sloppy-phrase launches, one that initialises the records and rows
+ * and one aggregation launch per sub-batch (tq_agg.hip: workgroup = (query, slice of the bitmap words), option
+ * "agg_slices"; per-lane accumulators, wavefront shuffles, and integer vector atomics on the query's record and row — order-
+ * free, hence deterministic; a histogram of at most "agg_lds_buckets" buckets is counted in LDS first).
+ * Afterwards tq_last_batch_match_counts gives `matches`, kernel_mask = TQ_KERNEL_AGG (| TQ_KERNEL_DOCSET_TREE |
+ * TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = lists x bitmap words x 4 (a tree: (lists + 2) x bitmap words x 4)
+ *                     + 8 per matching doc with a value
+ *                     + 8 per matching doc of a TQ_CARD_OPTIONAL column (its presence word)
+ *                     + (64 + 4 x n_buckets) per query. */
+enum tq_value_type { TQ_VALUE_U64 = 0, TQ_VALUE_I64 = 1, TQ_VALUE_F64 = 2 };
+#define TQ_AGG_MAX_BUCKETS 65536u
+typedef struct tq_agg_request {
+  uint32_t column;         /* handle of tq_column_upload */
+  uint8_t value_type;      /* tq_value_type */
+  uint8_t histogram;       /* 0: stats alone; 1: and the histogram below */
+  uint8_t has_hard_bounds; /* 0 / 1 */
+  uint8_t reserved;
+  double interval, offset;
+  double hard_min, hard_max;
+} tq_agg_request; /* 40 bytes */
+typedef struct tq_agg_hist_plan_t {
+  int64_t base_pos;   /* bucket of a row's entry 0 */
+  uint32_t n_buckets; /* 0: no value can be in bounds */
+  uint32_t reserved;
+  double bounds_min, bounds_max; /* the effective bounds: hard, or the (-DBL_MAX, DBL_MAX) sentinel */
+} tq_agg_hist_plan_t; /* 32 bytes */
+typedef struct tq_agg_stats_t {
+  uint64_t matches, count;
+  uint64_t min_value, max_value;
+  uint64_t sum_lo, sum_hi;
+  uint64_t in_bounds, out_of_range;
+} tq_agg_stats_t; /* 64 bytes */
+int tq_agg_histogram_plan(const tq_column_info_t *info, const tq_agg_request *req, tq_agg_hist_plan_t *out);
+int tq_agg_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_request *req,
+                 tq_agg_stats_t *out_stats, uint32_t *out_buckets, uint32_t bucket_stride);
+/* Same with DEVICE outputs on the segment's device, enqueued on hip_stream (NULL = the segment's stream), no host
+ * synchronisation.  The call itself zeroes what it accumulates into: the same buffers may be used again. */
+int tq_agg_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_request *req,
+                        tq_agg_stats_t *d_out_stats, uint32_t *d_out_buckets, uint32_t bucket_stride, void *hip_stream);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -897,6 +989,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_DOCSET_TREE_SCORE 0x20000u /* docset_tree_score_kernel (tq_docset_scored_batch*, option "docset_score_trees": the scores of such rows) */
 #define TQ_KERNEL_PHRASE_SLOP 0x40000u /* phrase_slop_kernel / phrase_slop_bits_kernel (TQ_MODE_PHRASE with slop > 0, over bitmap words) */
 #define TQ_KERNEL_SORT 0x80000u        /* sort_select_kernel / sort_merge_kernel (tq_search_sorted_batch*: top k by a fast-field column) */
+#define TQ_KERNEL_AGG 0x100000u        /* agg_kernel (tq_agg_batch*: stats and histogram of a fast-field column) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -985,6 +1078,13 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        segment's bitmap words per query, one selection workgroup each; 0 = the host chooses (queries x slices fills the
  *        machine, no slice below 1024 words), 1 = every query's row is written by its one workgroup and no merge is
  *        launched, 2..256 = forced (a slice past the last word is empty).  Results do not depend on it,
+ *        "agg_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_agg_batch* — slices of the segment's
+ *        bitmap words per query, one aggregation workgroup each; 0 = the host chooses as for "sort_slices", 1..256 =
+ *        forced (a slice past the last word is empty).  Results do not depend on it,
+ *        "agg_lds_buckets" (0..8192 = the kernel's LDS capacity, default 8192; any other value: TQ_ERR_INVALID):
+ *        tq_agg_batch* — the largest n_buckets a workgroup counts in a private LDS table that it flushes once (a
+ *        table of 2 048 buckets, or of 8 192 at half the wavefronts per SIMD: two instantiations); above it every doc is
+ *        an atomic add on the query's row, several times slower on dense queries.  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

@@ -63,6 +63,9 @@ KERNEL_DOCSET_TREE = 0x10000
 KERNEL_DOCSET_TREE_SCORE = 0x20000
 KERNEL_PHRASE_SLOP = 0x40000
 KERNEL_SORT = 0x80000
+KERNEL_AGG = 0x100000
+VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
+AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
 SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
 NULLS_LAST, NULLS_FIRST = 0, 1  # tq_sort_nulls (NULLS_FIRST: Reverse / NaturalNoneHigher)
 MAX_K = 1024  # TQ_MAX_K
@@ -71,7 +74,7 @@ NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
-                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort"}
+                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg"}
 
 
 def kernel_names(mask):
@@ -163,6 +166,7 @@ EXPORTS = [
     "tq_term_table_read", "tq_term_table_info",
     "tq_column_parse", "tq_column_upload", "tq_column_info", "tq_column_release", "tq_column_decode", "tq_range_prepare",
     "tq_search_sorted_batch", "tq_search_sorted_batch_device",
+    "tq_agg_histogram_plan", "tq_agg_batch", "tq_agg_batch_device",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -192,6 +196,111 @@ MAX_COLUMNS = 16  # TQ_MAX_COLUMNS
 CARD_FULL, CARD_OPTIONAL, CARD_MULTIVALUED = 0, 1, 2  # tq_cardinality
 CODEC_BITPACKED, CODEC_LINEAR, CODEC_BLOCKWISE_LINEAR = 0, 1, 2  # tq_column_codec
 BOUND_KINDS = {"in": 1, "ex": 2}  # tq_bound_kind (None: TQ_BOUND_UNBOUNDED)
+
+
+class TqAggRequest(C.Structure):  # tq_agg_request
+    _fields_ = [("column", C.c_uint32), ("value_type", C.c_uint8), ("histogram", C.c_uint8), ("has_hard_bounds", C.c_uint8),
+                ("reserved", C.c_uint8), ("interval", C.c_double), ("offset", C.c_double), ("hard_min", C.c_double),
+                ("hard_max", C.c_double)]
+
+
+class TqAggHistPlan(C.Structure):  # tq_agg_hist_plan_t
+    _fields_ = [("base_pos", C.c_int64), ("n_buckets", C.c_uint32), ("reserved", C.c_uint32), ("bounds_min", C.c_double),
+                ("bounds_max", C.c_double)]
+
+
+# tq_agg_stats_t as a numpy structured dtype: one 64-byte record per query
+AGG_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("matches", "count", "min_value", "max_value", "sum_lo", "sum_hi",
+                                                     "in_bounds", "out_of_range")])
+
+
+def _agg_request(column, value_type, histogram):
+    """histogram: None (stats alone) or a dict with "interval" and optionally "offset" and "hard_bounds" = (min, max)."""
+    req = TqAggRequest(column=int(column), value_type=int(value_type))
+    if histogram is not None:
+        req.histogram = 1
+        req.interval = float(histogram["interval"])
+        req.offset = float(histogram.get("offset", 0.0))
+        hb = histogram.get("hard_bounds")
+        if hb is not None:
+            req.has_hard_bounds, req.hard_min, req.hard_max = 1, float(hb[0]), float(hb[1])
+    return req
+
+
+def agg_histogram_plan(info, value_type, interval, offset=0.0, hard_bounds=None):
+    """tq_agg_histogram_plan: validation and the dense bucket range of a histogram over a column, from its info dict
+    (column_parse / DeviceIndex.column_info).  -> {"base_pos", "n_buckets", "bounds_min", "bounds_max", "interval", "offset"}.
+    Needs no device."""
+    ci = TqColumnInfo(**{n: int(info[n]) for n, _ in TqColumnInfo._fields_ if n in info})
+    req = _agg_request(0, value_type, {"interval": interval, "offset": offset, "hard_bounds": hard_bounds})
+    plan = TqAggHistPlan()
+    _check(lib().tq_agg_histogram_plan(C.byref(ci), C.byref(req), C.byref(plan)))
+    return _agg_plan_dict(plan, req)
+
+
+def _agg_plan_dict(plan, req):
+    return {"base_pos": int(plan.base_pos), "n_buckets": int(plan.n_buckets), "bounds_min": float(plan.bounds_min),
+            "bounds_max": float(plan.bounds_max), "interval": float(req.interval), "offset": float(req.offset)}
+
+
+def agg_value_from_u64(v, value_type):
+    """A u64-space value in its typed space: int for U64 / I64, float for F64 (MonotonicallyMappableToU64 inverted)."""
+    v = int(v)
+    if value_type == VALUE_I64:
+        s = v ^ (1 << 63)
+        return s - (1 << 64) if s >> 63 else s
+    if value_type == VALUE_F64:
+        bits = v ^ (1 << 63) if v >> 63 else v ^ ((1 << 64) - 1)
+        return float(np.array([bits], np.uint64).view(np.float64)[0])
+    return v
+
+
+def merge_agg_stats(rows):
+    """The segments' tq_agg_stats_t records of ONE query (rows of raw_agg's structured array, or dicts) as one record, a
+    dict of Python ints: counts and the 128-bit sum add, min / max are the extremes.  Host only."""
+    out = {"matches": 0, "count": 0, "min_value": (1 << 64) - 1, "max_value": 0, "sum": 0, "in_bounds": 0, "out_of_range": 0}
+    for r in rows:
+        for n in ("matches", "count", "in_bounds", "out_of_range"):
+            out[n] += int(r[n])
+        out["sum"] += int(r["sum_lo"]) + (int(r["sum_hi"]) << 64)
+        out["min_value"] = min(out["min_value"], int(r["min_value"]))
+        out["max_value"] = max(out["max_value"], int(r["max_value"]))
+    out["sum_lo"], out["sum_hi"] = out["sum"] & ((1 << 64) - 1), out["sum"] >> 64
+    return out
+
+
+def agg_stats_finalize(stats_row, value_type):
+    """IntermediateStats::finalize (stats.rs:138-161) of one record, in the typed space: {"count", "sum", "min", "max",
+    "avg"}.  U64 / I64: sum is an exact Python int (I64: the u64-space sum minus count * 2^63), min / max ints, avg =
+    sum / count; F64: min / max floats, sum = avg = None (not served).  count == 0: min = max = avg = None, sum 0."""
+    count = int(stats_row["count"])
+    if value_type == VALUE_F64:
+        total = None
+    else:
+        total = int(stats_row["sum_lo"]) + (int(stats_row["sum_hi"]) << 64) - (count << 63 if value_type == VALUE_I64 else 0)
+    if count == 0:
+        return {"count": 0, "sum": total, "min": None, "max": None, "avg": None}
+    return {"count": count, "sum": total, "min": agg_value_from_u64(stats_row["min_value"], value_type),
+            "max": agg_value_from_u64(stats_row["max_value"], value_type), "avg": None if total is None else total / count}
+
+
+def merge_histograms(parts):
+    """The segments' histogram rows of ONE query and ONE request: parts = [(plan, counts)] as raw_agg returns them (plan
+    dict, counts = the query's row).  The rows are aligned by base_pos and added.  -> (keys, counts): keys[i] = pos *
+    interval + offset (get_bucket_key_from_pos) over the dense range from the lowest to the highest bucket of any segment,
+    counts a list of ints.  Host only; gap filling beyond that range, min_doc_count and ordering stay the caller's."""
+    parts = [(p, c) for p, c in parts if p["n_buckets"]]
+    if not parts:
+        return [], []
+    interval, offset = parts[0][0]["interval"], parts[0][0]["offset"]
+    assert all(p["interval"] == interval and p["offset"] == offset for p, _ in parts)
+    lo = min(p["base_pos"] for p, _ in parts)
+    hi = max(p["base_pos"] + p["n_buckets"] for p, _ in parts)
+    counts = [0] * (hi - lo)
+    for p, c in parts:
+        for i in range(p["n_buckets"]):
+            counts[p["base_pos"] - lo + i] += int(c[i])
+    return [float(pos) * interval + offset for pos in range(lo, hi)], counts
 
 
 def _column_info_dict(info):
@@ -282,6 +391,9 @@ def lib():
                                          u32p, C.POINTER(C.c_uint64), u8p, u32p]
     L.tq_search_sorted_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32,
                                                 vp, vp, vp, vp, vp]
+    L.tq_agg_histogram_plan.argtypes = [C.POINTER(TqColumnInfo), C.POINTER(TqAggRequest), C.POINTER(TqAggHistPlan)]
+    L.tq_agg_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest), vp, u32p, C.c_uint32]
+    L.tq_agg_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest), vp, vp, C.c_uint32, vp]
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -1241,6 +1353,51 @@ class DeviceIndex:
                                                    int(nulls), int(stride), d_docs.data_ptr(), d_values.data_ptr(),
                                                    d_has_value.data_ptr(), d_counts.data_ptr(),
                                                    C.c_void_p(stream) if stream else None)
+
+    # ---- aggregations over a fast field (tq_agg.cpp, tq_agg.hip)
+    def raw_agg(self, queries, column, value_type, histogram=None, segment_ord=0, device=False, stride=None):
+        """Direct tq_agg_batch on one segment: the query tuples of raw_docset; histogram = None (stats alone) or {"interval",
+        "offset", "hard_bounds": (min, max)}.  -> (stats: structured array [n] of AGG_STATS_DTYPE, buckets [n, n_buckets]
+        uint32, plan dict of agg_histogram_plan — n_buckets 0 without a histogram).  stride: the rows' stride in the call
+        (default n_buckets); device=True: through tq_agg_batch_device into torch tensors on the segment's GPU."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_request(column, value_type, histogram)
+        plan = TqAggHistPlan()
+        if histogram is not None:  # (the call makes the same plan; a refusal comes from the call, under its name)
+            info = TqColumnInfo()
+            if lib().tq_column_info(self.segment_raw(segment_ord), int(column), C.byref(info)) == 0:
+                lib().tq_agg_histogram_plan(C.byref(info), C.byref(req), C.byref(plan))
+        nb = int(plan.n_buckets)
+        stride = nb if stride is None else int(stride)
+        stats = np.zeros(max(1, n), AGG_STATS_DTYPE)
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_stats = torch.full((max(1, n), 8), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_rows = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_batch_device(self.segment_raw(segment_ord), qs, n, C.byref(req), d_stats.data_ptr(),
+                                             d_rows.data_ptr(), stride, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            stats = d_stats.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_STATS_DTYPE)
+            rows = d_rows.cpu().numpy().view(np.uint32)
+        else:
+            rows = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint32)
+            _check(lib().tq_agg_batch(self.segment_raw(segment_ord), qs, n, C.byref(req), stats.ctypes.data, _u32(rows), stride))
+        return stats[:n], rows[:n, :nb], _agg_plan_dict(plan, req)
+
+    def raw_agg_device(self, queries, column, value_type, histogram, stride, d_stats, d_buckets, segment_ord=0, stream=None):
+        """Direct tq_agg_batch_device: d_stats (int64 / uint64, 8 words per query) and d_buckets (int32 / uint32,
+        len(queries) * stride entries, or None without a histogram) are torch tensors on the segment's GPU; only enqueues.
+        -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_request(column, value_type, histogram)
+        return lib().tq_agg_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req), d_stats.data_ptr(),
+                                         d_buckets.data_ptr() if d_buckets is not None else None, int(stride),
+                                         C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

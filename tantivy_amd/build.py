@@ -30,6 +30,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_docset_tree_score.hip"),
     os.path.join(HERE, "csrc", "tq_sort.hip"),
     os.path.join(HERE, "csrc", "tq_sort.cpp"),
+    os.path.join(HERE, "csrc", "tq_agg.hip"),
+    os.path.join(HERE, "csrc", "tq_agg.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -93,7 +95,8 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "or_kernel": "tq_union.hip", "ushare_kernel": "tq_ushare.hip", "ashare_kernel": "tq_ashare.hip", "count_bitmap_kernel": "tq_count.hip", "docset_count_kernel": "tq_docset.hip", "docset_write_kernel": "tq_docset.hip", "docset_score_kernel": "tq_docset_score.hip", "docset_tree_bits_kernel": "tq_docset_tree.hip", "docset_tree_score_kernel": "tq_docset_tree_score.hip", "tree_kernel": "tq_tree.hip", "tree_fields_kernel": "tq_tree_fields.hip", "docset_score_fields_kernel": "tq_docset_score_fields.hip", "all_kernel": "tq_all.hip", "xunion_kernel": "tq_xunion.hip",
                 "phrase_sweep_kernel": "tq_phrase.hip", "phrase_kernel": "tq_phrase.hip",
                 "phrase_slop_kernel": "tq_phrase_slop.hip", "phrase_slop_bits_kernel": "tq_phrase_slop.hip",
-                "sort_select_kernel": "tq_sort.hip", "sort_merge_kernel": "tq_sort.hip"}
+                "sort_select_kernel": "tq_sort.hip", "sort_merge_kernel": "tq_sort.hip",
+                "agg_kernel": "tq_agg.hip", "agg_init_kernel": "tq_agg.hip"}
 
 
 def kernel_hash(kernel_names, read=None):

@@ -297,6 +297,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_sort_partials.release();
   s->d_sort_slice_counts.release();
   s->d_sort_rows.release();
+  s->d_agg_rows.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
@@ -442,7 +443,7 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
       if (wrc != TQ_OK) return wrc;
     }
     unsigned long long m = 0;
-    if (s->stats_sorted) {  // a sorted batch: matches, matches with a value, row entries written
+    if (s->stats_sorted) {  // a sorted batch: matches, matches with a value, row entries written (an aggregation: none)
       unsigned long long t[3] = {0, 0, 0};
       HIP_TRY(hipMemcpy(t, s->d_match_counter, sizeof t, hipMemcpyDeviceToHost));
       m = t[0];
@@ -570,6 +571,10 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.docset_score_trees = (int)value;
   else if (!strcmp(name, "sort_slices") && value >= 0 && value <= 256)
     s->opt.sort_slices = (int)value;
+  else if (!strcmp(name, "agg_slices") && value >= 0 && value <= 256)
+    s->opt.agg_slices = (int)value;
+  else if (!strcmp(name, "agg_lds_buckets") && value >= 0 && value <= (int64_t)tqk_agg_lds_buckets())
+    s->opt.agg_lds_buckets = (int)value;
   else if (!strcmp(name, "ashare_inline_warm") && value >= 0 && value <= 2)
     s->opt.ashare_inline_warm = (int)value;
   else if (!strcmp(name, "ashare_min_batch") && value >= 0 && value <= 0x7FFFFFFF)

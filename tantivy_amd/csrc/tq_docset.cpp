@@ -17,6 +17,8 @@
 // A SortSpec (tq_search_sorted_batch*, tq_sort.cpp): everything in front of a sub-batch's passes is the same — checks,
 // expressions, tree / slop planning, sub-batches, scatter, tree bits — and the selection launch(es) of tq_sort.hip take the
 // place of its count / scan / write passes; the rows go to the spec's device arrays under the caller's query index.
+// An AggSpec (tq_agg_batch*, tq_agg.cpp) is taken the same way: the aggregation launch of tq_agg.hip per sub-batch, behind
+// one launch that initialises the records and bucket rows of the whole batch.
 #include "tq_internal.hpp"
 
 #include <deque>
@@ -168,12 +170,12 @@ enum : uint32_t { DS_SCATTER = 1u, DS_COUNT = 2u, DS_WRITE = 4u };
 
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only,
-                 const uint32_t *caller_q, uint32_t n_caller, const SortSpec *sort) {
+                 const uint32_t *caller_q, uint32_t n_caller, const SortSpec *sort, const AggSpec *agg) {
   // (tq_count_batch hands over a sub-array of its batch: what this call says about a sloppy phrase — refusals, the
   // overflow words — it says under the CALLER's index)
   auto named = [&](uint32_t qi) { return caller_q ? caller_q[qi] : qi; };
   const uint32_t n_over_words = caller_q ? n_caller : n_queries;
-  const char *const fn = sort ? sort->fn : count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
+  const char *const fn = sort ? sort->fn : agg ? agg->fn : count_only ? "tq_count_batch" : scored ? (device_out ? "tq_docset_scored_batch_device" : "tq_docset_scored_batch")
                                 : (device_out ? "tq_docset_batch_device" : "tq_docset_batch");
   // the write pass stages the docs of a (query, tile) in LDS when the tile holds at least this many (of 65 536)
   static const uint32_t kStageMin = tune_u32("TQ_DOCSET_STAGE_MIN", 2048);
@@ -393,12 +395,13 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     if (wrc != TQ_OK) return wrc;
   }
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = (sort ? TQ_KERNEL_SORT : TQ_KERNEL_DOCSET) | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
+  s->stats.kernel_mask = (sort ? TQ_KERNEL_SORT : agg ? TQ_KERNEL_AGG : TQ_KERNEL_DOCSET) | (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
                          (scored && !tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u) | (slop_qs.empty() ? 0u : TQ_KERNEL_PHRASE_SLOP);
   s->stats.algorithmic_bytes = algo_bytes;
+  if (agg) s->stats.algorithmic_bytes += (uint64_t)n_queries * (sizeof(tq_agg_stats_t) + 4u * (uint64_t)agg->plan.n_buckets);
   s->stats_pending = false;
   s->last_batch_queries = 0;
-  if (!sort && (n_queries == 0 || n_tiles == 0)) {  // no query, or a segment without docs: empty rows
+  if (!sort && !agg && (n_queries == 0 || n_tiles == 0)) {  // no query, or a segment without docs: empty rows
     if (device_out) {
       HIP_TRY(hipMemsetAsync(out_starts, 0, ((size_t)n_queries + 1u) * sizeof(uint64_t), st));
     } else {
@@ -420,8 +423,16 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   // (the sloppy phrases' records ride behind the tree records and their map, 64-byte aligned, in both buffers)
   const size_t slop_off = (tree_bytes + tree_map_bytes + 63u) & ~(size_t)63, slop_bytes = slop_qs.size() * sizeof(TqdSlopQuery);
   const size_t tree_blob_bytes = slop_bytes ? slop_off + slop_bytes : tree_bytes + tree_map_bytes;
-  // a sorted call: the slices per query — enough workgroups for the machine, no slice below 1024 words (four steps), or what
-  // "sort_slices" forces —, the key slots per lane its largest k needs, and every query's k behind the blobs above
+  // the slices per query of a sorted or an aggregation call: enough workgroups for the machine, no slice below four steps
+  // of the walk (1024 words), or what "sort_slices" / "agg_slices" forces
+  auto pick_slices = [&](int forced, uint32_t step_words) -> uint32_t {
+    if (forced > 0) return (uint32_t)forced;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) cus = 256;
+    const uint32_t want = ((uint32_t)cus * 4u + max_sub_n - 1u) / std::max(1u, max_sub_n);
+    return std::max(1u, std::min({want, 256u, n_words / (4u * step_words)}));
+  };
+  // a sorted call: its slices, the key slots per lane its largest k needs, and every query's k behind the blobs above
   uint32_t sort_slices = 1, sort_wps = n_words, sort_kpl = 1;
   const size_t ks_off = ((q_bytes + wg_bytes + sq_bytes + cache_bytes + 63u) & ~(size_t)63) + ((tree_blob_bytes + 63u) & ~(size_t)63);
   const size_t ks_bytes = sort ? (size_t)n_queries * sizeof(uint32_t) : 0u;
@@ -429,15 +440,14 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     uint32_t max_k = 1;
     for (uint32_t qi = 0; qi < n_queries; ++qi) max_k = std::max(max_k, queries[qi].k);
     sort_kpl = max_k <= 64u ? 1 : max_k <= 256u ? 4 : 16;
-    if (s->opt.sort_slices > 0) {
-      sort_slices = (uint32_t)s->opt.sort_slices;
-    } else {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) cus = 256;
-      const uint32_t want = ((uint32_t)cus * 4u + max_sub_n - 1u) / std::max(1u, max_sub_n);
-      sort_slices = std::max(1u, std::min({want, 256u, n_words / (4u * tqk_sort_step_words())}));
-    }
+    sort_slices = pick_slices(s->opt.sort_slices, tqk_sort_step_words());
     sort_wps = (n_words + sort_slices - 1u) / sort_slices;
+  }
+  // an aggregation call: its slices
+  uint32_t agg_slices = 1, agg_wps = n_words;
+  if (agg) {
+    agg_slices = pick_slices(s->opt.agg_slices, tqk_agg_step_words());
+    agg_wps = (n_words + agg_slices - 1u) / agg_slices;
   }
   const size_t sort_part_bytes = sort_slices > 1u ? (size_t)max_sub_n * sort_slices * (size_t)sort_kpl * 64u * 2u * sizeof(uint64_t) : 0u;
   int rc = s->h_docset.ensure(ks_off + ks_bytes + 64u);
@@ -451,9 +461,9 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
   if (rc == TQ_OK) rc = s->d_docset_queries.ensure(q_bytes);
   if (rc == TQ_OK) rc = s->d_count_wgs.ensure(wg_bytes);
   if (rc == TQ_OK) rc = s->d_count_bits.ensure((size_t)max_sub_temp * words_per_list * sizeof(uint32_t));
-  if (rc == TQ_OK && !sort) rc = s->d_docset_counts.ensure(max_entries * sizeof(uint32_t));
-  if (rc == TQ_OK && !sort) rc = s->d_docset_offs.ensure(max_entries * sizeof(uint64_t));
-  if (rc == TQ_OK && !sort) rc = s->d_docset_partials.ensure(((max_entries + tqk_docset_scan_tile() - 1) / tqk_docset_scan_tile()) * sizeof(uint64_t));
+  if (rc == TQ_OK && !sort && !agg) rc = s->d_docset_counts.ensure(max_entries * sizeof(uint32_t));
+  if (rc == TQ_OK && !sort && !agg) rc = s->d_docset_offs.ensure(max_entries * sizeof(uint64_t));
+  if (rc == TQ_OK && !sort && !agg) rc = s->d_docset_partials.ensure(((max_entries + tqk_docset_scan_tile() - 1) / tqk_docset_scan_tile()) * sizeof(uint64_t));
   if (rc == TQ_OK) rc = s->d_qmatches.ensure((size_t)n_queries * sizeof(uint32_t));
   if (rc == TQ_OK && !device_out) rc = s->d_docset_starts.ensure(((size_t)n_queries + 1u) * sizeof(uint64_t));
   if (rc != TQ_OK) return rc;
@@ -493,6 +503,13 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     for (uint32_t qi = 0; qi < n_queries; ++qi) h_ks[qi] = queries[qi].k;
     HIP_TRY(hipMemcpyAsync(s->d_sort_ks.p, h_ks, ks_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, 3u * sizeof(unsigned long long), st));
+  }
+  if (agg) {  // what the aggregation launches add to: the totals, every query's match count, the records and bucket rows
+    HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, 3u * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(s->d_qmatches.p, 0, (size_t)n_queries * sizeof(uint32_t), st));
+    const hipError_t ie = tqk_launch_agg_init((TqkAggStats *)agg->d_stats, agg->d_buckets, n_queries, agg->plan.n_buckets,
+                                              agg->bucket_stride, st);
+    if (ie != hipSuccess) return fail(TQ_ERR_HIP, "aggregation init launch: %s", hipGetErrorString(ie));
   }
   if (slop_bytes) {  // the overflow words, one per query of the batch (tq_last_batch_slop_overflows)
     HIP_TRY(hipMemsetAsync(s->d_slop_over.p, 0, (size_t)n_over_words * sizeof(uint32_t), st));
@@ -580,6 +597,32 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
       if (e != hipSuccess) return fail(TQ_ERR_HIP, "sort kernel launch: %s", hipGetErrorString(e));
       return TQ_OK;
     }
+    if (agg) {  // the aggregation in place of the count / scan / write passes: records and rows under the caller's query index
+      const tq_segment::ColumnHost &col = s->columns[agg->column];
+      TqkAggParams ap{};
+      ap.ds = p;
+      ap.col = col.dev;
+      ap.min_value = col.info.min_value;
+      ap.gcd = col.info.gcd;
+      ap.stats = (TqkAggStats *)agg->d_stats + sb.q0;
+      ap.buckets = agg->d_buckets ? agg->d_buckets + (size_t)sb.q0 * agg->bucket_stride : nullptr;
+      ap.query_sizes = p.query_sizes;
+      ap.totals = s->d_match_counter;
+      ap.interval = agg->interval;
+      ap.offset = agg->offset;
+      ap.bounds_min = agg->plan.bounds_min;
+      ap.bounds_max = agg->plan.bounds_max;
+      ap.base_pos = agg->plan.base_pos;
+      ap.n_buckets = agg->plan.n_buckets;
+      ap.bucket_stride = agg->bucket_stride;
+      ap.lds_buckets = s->opt.agg_lds_buckets < 0 ? tqk_agg_lds_buckets() : (uint32_t)s->opt.agg_lds_buckets;
+      ap.value_type = agg->value_type;
+      ap.n_slices = agg_slices;
+      ap.words_per_slice = agg_wps;
+      e = tqk_launch_agg(ap, st);
+      if (e != hipSuccess) return fail(TQ_ERR_HIP, "aggregation kernel launch: %s", hipGetErrorString(e));
+      return TQ_OK;
+    }
     if (stages & DS_COUNT) {
       e = tqk_launch_docset_count(p, st);
       if (e == hipSuccess) e = tqk_launch_docset_scan(p, st);
@@ -654,8 +697,9 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uin
     }
     s->stats_pending = true;  // the total is on the device: tq_last_batch_stats reads it
     s->stats_match_bytes = scored ? 9 : 4;  // doc [+ score + fieldnorm byte]
-    s->stats_sorted = sort != nullptr;    // (its own byte model: tq_last_batch_stats)
-    s->stats_sorted_optional = sort && s->columns[sort->column].dev.present != nullptr;
+    s->stats_sorted = sort || agg;    // (its own byte model: tq_last_batch_stats)
+    s->stats_sorted_optional = (sort && s->columns[sort->column].dev.present != nullptr) ||
+                               (agg && s->columns[agg->column].dev.present != nullptr);
     HIP_TRY(hipEventRecord(s->ev_batch_done, st));
     s->last_stream = st;
     s->batch_in_flight = true;

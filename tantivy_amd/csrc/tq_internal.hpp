@@ -205,6 +205,8 @@ struct Options {
   int docset_trees = 0;          // doc sets: phrases and nested boolean queries through tq_docset_tree.hip (0 = refused, as before)
   int docset_score_trees = 0;    // scored doc sets: the same shapes, scored by tq_docset_tree_score.hip (0 = refused, as before)
   int sort_slices = 0;           // sort by fast field: slices of the bitmap words per query (0 = the host chooses, 1..256 = forced)
+  int agg_slices = 0;            // aggregations: the same for tq_agg_batch*
+  int agg_lds_buckets = -1;      // aggregations: the largest histogram that goes through LDS (-1 = the kernel's capacity)
   int ashare_inline_warm = 1;   // intersections: 0 = warm-up and main tasks as two dispatches, 1 = ONE dispatch where they are the batch's only
                                 // group and tasks of leaders without warm-up tasks fill the grid (build_ashare_plan), 2 = always one dispatch
   int ashare_min_batch = 16;    // intersections: the shared launch needs this many qualifying queries in the batch (512 until round 6)
@@ -355,11 +357,12 @@ struct tq_segment {
   DevBuf d_docset_trees;  // ... of phrases and nested queries (tq_docset_tree.hip): their TqdTreeQuery records
   // sort by fast field (tq_sort.hip): the queries' k, the slices' lists and counts, the host variant's rows
   DevBuf d_sort_ks, d_sort_partials, d_sort_slice_counts, d_sort_rows;
+  DevBuf d_agg_rows;  // aggregations (tq_agg.hip): the host variant's records and bucket rows
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
            d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap +
-           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap;
+           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap + d_agg_rows.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -450,7 +453,8 @@ struct tq_segment {
                                    // byte per scored doc, 4 bytes per doc of a doc-set batch on the device (9 with scores)
   // the pending batch is a sorted one (tq_search_sorted_batch*): d_match_counter[0..2] = matches, matches with a value, row
   // entries written, which tq_last_batch_stats turns into bytes (8 per valued match, 8 per match of an Optional column, 13
-  // per entry); set or cleared wherever stats_pending is set
+  // per entry); set or cleared wherever stats_pending is set.  An aggregation batch (tq_agg_batch*) is counted the same
+  // way: it writes no row entries, and its records and bucket rows are already in stats.algorithmic_bytes
   bool stats_sorted = false, stats_sorted_optional = false;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
@@ -1048,9 +1052,23 @@ struct SortSpec {
   uint8_t *d_has_value;
   uint32_t *d_counts;
 };
+// Aggregations (tq_agg.cpp): an AggSpec is taken like a SortSpec (not both) — the aggregation launch of tq_agg.hip in place
+// of every sub-batch's passes, behind one launch that initialises the whole batch's records and bucket rows.  d_stats /
+// d_buckets are DEVICE memory, the record of query q at q, its row at q * bucket_stride.
+struct AggSpec {
+  const char *fn;  // the entry point's name, for messages
+  uint32_t column;
+  uint32_t value_type;          // TQ_VALUE_*
+  tq_agg_hist_plan_t plan;      // n_buckets == 0: no histogram (none asked for, or no value can be in bounds)
+  double interval, offset;
+  uint32_t bucket_stride;
+  tq_agg_stats_t *d_stats;
+  uint32_t *d_buckets;
+};
 int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
                  uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false,
-                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0, const SortSpec *sort = nullptr);
+                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0, const SortSpec *sort = nullptr,
+                 const AggSpec *agg = nullptr);
 // (caller_q / n_caller — tq_count_batch, which hands over a sub-array of its n_caller queries: query qi of this call is
 // the caller's caller_q[qi]; sloppy phrases are named, and their overflow words indexed, by that)
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights

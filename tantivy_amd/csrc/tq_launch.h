@@ -462,6 +462,34 @@ struct TqkSortParams {
 hipError_t tqk_launch_sort_select(const TqkSortParams &p, int kpl, hipStream_t st);
 hipError_t tqk_launch_sort_merge(const TqkSortParams &p, int kpl, hipStream_t st);
 uint32_t tqk_sort_step_words();  // bitmap words a selection workgroup takes per step
+// ---- aggregations over a fast field (tq_agg.hip): stats and a histogram of a u64 column over a doc set (tq_agg_batch*).
+// One launch: workgroup = (query, slice of the bitmap words), query fastest; every workgroup adds its part to the query's
+// record (and bucket row) with vector atomics, so the records and rows are initialised in front of it (tqk_launch_agg_init).
+struct TqkAggStats {  // = tq_agg_stats_t, 64 bytes
+  unsigned long long matches, count, min_value, max_value, sum_lo, sum_hi, in_bounds, out_of_range;
+};
+struct TqkAggParams {
+  TqkDocsetParams ds;          // queries (one sub-batch), alive, n_queries, n_words, max_doc: what docset_word reads
+  TqkColumn col;               // the aggregated column
+  uint64_t min_value, gcd;     // value = min + gcd * packed (Linear: the packed value itself)
+  TqkAggStats *stats;          // records of the sub-batch's first query on: [n_queries]
+  uint32_t *buckets;           // rows of the sub-batch's first query on: [n_queries][bucket_stride] (histogram)
+  uint32_t *query_sizes;       // [n_queries] += alive matches per query (zeroed by the caller)
+  unsigned long long *totals;  // [2] += matches, matches with a value (zeroed by the caller)
+  double interval, offset;     // pos = floor((val - offset) / interval)
+  double bounds_min, bounds_max;  // the effective bounds (tq_agg_hist_plan_t): val is counted when min <= val <= max
+  int64_t base_pos;            // bucket of a row's entry 0
+  uint32_t n_buckets;          // entries of a row the launch may write (0 = no histogram)
+  uint32_t bucket_stride;
+  uint32_t lds_buckets;        // n_buckets <= this: a workgroup-private table in LDS, flushed at the end; above: the row
+  uint32_t value_type;         // TQ_VALUE_*: how a u64-space value becomes the f64 the histogram buckets
+  uint32_t n_slices, words_per_slice;
+};
+hipError_t tqk_launch_agg_init(TqkAggStats *stats, uint32_t *buckets, uint32_t n_queries, uint32_t n_buckets,
+                               uint32_t bucket_stride, hipStream_t st);
+hipError_t tqk_launch_agg(const TqkAggParams &p, hipStream_t st);
+uint32_t tqk_agg_step_words();   // bitmap words an aggregation workgroup takes per step
+uint32_t tqk_agg_lds_buckets();  // the LDS table's compile-time capacity in buckets
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
