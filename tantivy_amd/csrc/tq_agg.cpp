@@ -2,8 +2,9 @@
 // over a resident u64 column, per query of a batch, on the device (the reference: src/aggregation/metric/stats.rs:86-176;
 // src/aggregation/bucket/histogram/histogram.rs:468-518, 672-699, 738-769; src/aggregation/mod.rs:351-383).  The plan —
 // validation of the request, normalize_histogram_req's bounds and compute_dense_range — is host arithmetic and lives
-// here; everything in front of the aggregation launch — validation of the queries, the doc-set expression, tree and slop
-// planning, sub-batches, scatter — is docset_batch's (tq_docset.cpp) under an AggSpec, the kernels tq_agg.hip's.
+// here, as do the launch geometry and the launches (kernels: tq_agg.hip); the match words the aggregation reads —
+// validation of the queries, the doc-set expression, tree and slop planning, sub-batches, scatter — come from
+// docset_batch (tq_docset.cpp), which calls agg_prepare once and agg_launch per sub-batch.
 // Part of the C ABI library of include/tantivy_amd.h (internal declarations: tq_internal.hpp).
 #include "tq_internal.hpp"
 
@@ -90,6 +91,43 @@ int check_agg_call(tq_segment *s, const char *fn, const tq_agg_request *req, con
 
 }  // namespace
 
+// what the aggregation launches add to: the totals, every query's match count, the records and bucket rows
+int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_sub_n, uint32_t n_words, hipStream_t st) {
+  spec.n_slices = pick_slices(s, s->opt.agg_slices, tqk_agg_step_words(), max_sub_n, n_words);
+  spec.words_per_slice = (n_words + spec.n_slices - 1u) / spec.n_slices;
+  spec.optional = s->columns[spec.column].dev.present != nullptr;
+  s->stats.algorithmic_bytes += (uint64_t)n_queries * (sizeof(tq_agg_stats_t) + 4u * (uint64_t)spec.plan.n_buckets);
+  HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, 3u * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(s->d_qmatches.p, 0, (size_t)n_queries * sizeof(uint32_t), st));
+  return launched(tqk_launch_agg_init((TqkAggStats *)spec.d_stats, spec.d_buckets, n_queries, spec.plan.n_buckets, spec.bucket_stride, st), "aggregation init");
+}
+
+// the aggregation in place of the count / scan / write passes: records and rows under the caller's query index
+int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st) {
+  const tq_segment::ColumnHost &col = s->columns[spec.column];
+  TqkAggParams ap{};
+  ap.ds = p;
+  ap.col = col.dev;
+  ap.min_value = col.info.min_value;
+  ap.gcd = col.info.gcd;
+  ap.stats = (TqkAggStats *)spec.d_stats + q0;
+  ap.buckets = spec.d_buckets ? spec.d_buckets + (size_t)q0 * spec.bucket_stride : nullptr;
+  ap.query_sizes = p.query_sizes;
+  ap.totals = s->d_match_counter;
+  ap.interval = spec.interval;
+  ap.offset = spec.offset;
+  ap.bounds_min = spec.plan.bounds_min;
+  ap.bounds_max = spec.plan.bounds_max;
+  ap.base_pos = spec.plan.base_pos;
+  ap.n_buckets = spec.plan.n_buckets;
+  ap.bucket_stride = spec.bucket_stride;
+  ap.lds_buckets = s->opt.agg_lds_buckets < 0 ? tqk_agg_lds_buckets() : (uint32_t)s->opt.agg_lds_buckets;
+  ap.value_type = spec.value_type;
+  ap.n_slices = spec.n_slices;
+  ap.words_per_slice = spec.words_per_slice;
+  return launched(tqk_launch_agg(ap, st), "aggregation kernel");
+}
+
 }  // namespace tqi
 
 extern "C" {
@@ -109,8 +147,11 @@ int tq_agg_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queri
     tq_agg_hist_plan_t plan;
     const int rc = check_agg_call(s, fn, req, d_out_buckets, bucket_stride, &plan);
     if (rc != TQ_OK || n_queries == 0) return rc;
-    AggSpec spec{fn, req->column, req->value_type, plan, req->interval, req->offset, bucket_stride, d_out_stats, d_out_buckets};
-    return docset_batch(s, queries, n_queries, nullptr, nullptr, 0, nullptr, false, true, hip_stream, false, nullptr, 0, nullptr, &spec);
+    AggSpec spec{req->column, req->value_type, plan, req->interval, req->offset, bucket_stride, d_out_stats, d_out_buckets};
+    DocsetCall call(fn, DocsetConsumer::kAgg);
+    call.hip_stream = hip_stream;
+    call.agg = &spec;
+    return docset_batch(s, queries, n_queries, call);
   } catch (const std::exception &e) {
     return fail(TQ_ERR_HIP, "%s: %s", fn, e.what());
   }
@@ -126,19 +167,19 @@ int tq_agg_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, con
     int rc = check_agg_call(s, fn, req, out_buckets, bucket_stride, &plan);
     if (rc != TQ_OK || n_queries == 0) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    {
-      const int wrc = wait_segment_idle(s);  // (the buffer below may be a batch in flight's)
-      if (wrc != TQ_OK) return wrc;
-    }
+    rc = wait_segment_idle(s);  // (the buffer below may be a batch in flight's)
+    if (rc != TQ_OK) return rc;
     // on the device: [records | rows of n_buckets entries], copied back row by row into the caller's stride
     const size_t stats_bytes = (size_t)n_queries * sizeof(tq_agg_stats_t);
     const size_t row_bytes = (size_t)plan.n_buckets * sizeof(uint32_t);
     rc = s->d_agg_rows.ensure(stats_bytes + (size_t)n_queries * row_bytes + 64u);
     if (rc != TQ_OK) return rc;
     uint8_t *const base = (uint8_t *)s->d_agg_rows.p;
-    AggSpec spec{fn, req->column, req->value_type, plan, req->interval, req->offset, plan.n_buckets, (tq_agg_stats_t *)base,
+    AggSpec spec{req->column, req->value_type, plan, req->interval, req->offset, plan.n_buckets, (tq_agg_stats_t *)base,
                  plan.n_buckets ? (uint32_t *)(base + stats_bytes) : nullptr};
-    rc = docset_batch(s, queries, n_queries, nullptr, nullptr, 0, nullptr, false, true, nullptr, false, nullptr, 0, nullptr, &spec);
+    DocsetCall call(fn, DocsetConsumer::kAgg);
+    call.agg = &spec;
+    rc = docset_batch(s, queries, n_queries, call);
     if (rc != TQ_OK) return rc;
     hipStream_t st = s->stream;
     HIP_TRY(hipMemcpyAsync(out_stats, base, stats_bytes, hipMemcpyDeviceToHost, st));
@@ -149,12 +190,7 @@ int tq_agg_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, con
                                hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->d_agg_rows.cap > ((size_t)256 << 20)) s->d_agg_rows.release();  // (a large result is not kept as scratch)
-    if (s->last_batch_slop) {  // a sloppy phrase whose carried list went over the cap is reported; the other rows are valid
-      std::vector<uint32_t> over(s->slop_over_words);
-      HIP_TRY(hipMemcpy(over.data(), s->d_slop_over.p, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      return slop_overflow_verdict(fn, over.data(), (uint32_t)over.size());
-    }
-    return TQ_OK;
+    return slop_overflow_readback(s, fn);  // a sloppy phrase whose carried list went over the cap is reported; the other rows are valid
   } catch (const std::exception &e) {
     return fail(TQ_ERR_HIP, "%s: %s", fn, e.what());
   }

@@ -297,6 +297,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_sort_partials.release();
   s->d_sort_slice_counts.release();
   s->d_sort_rows.release();
+  s->h_sort_ks.release();
   s->d_agg_rows.release();
   s->h_docset.release();
   s->h_stage.release();
@@ -401,12 +402,22 @@ int tq_count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries,
   return count_batch(s, queries, n_queries, out_counts);
 }
 
+// a doc-set call whose consumer is its rows, into host buffers
+static DocsetCall rows_call(const char *fn, uint32_t *out_docs, float *out_scores, uint64_t out_cap, uint64_t *out_starts) {
+  DocsetCall call(fn);
+  call.out_docs = out_docs;
+  call.out_scores = out_scores;
+  call.out_cap = out_cap;
+  call.out_starts = out_starts;
+  return call;
+}
+
 int tq_docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, uint64_t out_cap,
                     uint64_t *out_starts) {
   if (!s || (!queries && n_queries) || (!out_docs && out_cap) || !out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_batch: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, out_docs, nullptr, out_cap, out_starts, false, false, nullptr);
+  return docset_batch(s, queries, n_queries, rows_call("tq_docset_batch", out_docs, nullptr, out_cap, out_starts));
 }
 
 int tq_docset_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *d_out_docs,
@@ -414,7 +425,10 @@ int tq_docset_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_qu
   if (!s || (!queries && n_queries) || (!d_out_docs && out_cap) || !d_out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_batch_device: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, d_out_docs, nullptr, out_cap, d_out_starts, false, true, hip_stream);
+  DocsetCall call = rows_call("tq_docset_batch_device", d_out_docs, nullptr, out_cap, d_out_starts);
+  call.device_out = true;
+  call.hip_stream = hip_stream;
+  return docset_batch(s, queries, n_queries, call);
 }
 
 int tq_docset_scored_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
@@ -422,7 +436,9 @@ int tq_docset_scored_batch(tq_segment *s, const tq_query *queries, uint32_t n_qu
   if (!s || (!queries && n_queries) || ((!out_docs || !out_scores) && out_cap) || !out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_scored_batch: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, out_docs, out_scores, out_cap, out_starts, true, false, nullptr);
+  DocsetCall call = rows_call("tq_docset_scored_batch", out_docs, out_scores, out_cap, out_starts);
+  call.scored = true;
+  return docset_batch(s, queries, n_queries, call);
 }
 
 int tq_docset_scored_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *d_out_docs,
@@ -430,7 +446,10 @@ int tq_docset_scored_batch_device(tq_segment *s, const tq_query *queries, uint32
   if (!s || (!queries && n_queries) || ((!d_out_docs || !d_out_scores) && out_cap) || !d_out_starts)
     return fail(TQ_ERR_INVALID, "tq_docset_scored_batch_device: null argument");
   TQ_SEGMENT_LOCK(s);
-  return docset_batch(s, queries, n_queries, d_out_docs, d_out_scores, out_cap, d_out_starts, true, true, hip_stream);
+  DocsetCall call = rows_call("tq_docset_scored_batch_device", d_out_docs, d_out_scores, out_cap, d_out_starts);
+  call.scored = call.device_out = true;
+  call.hip_stream = hip_stream;
+  return docset_batch(s, queries, n_queries, call);
 }
 
 int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {

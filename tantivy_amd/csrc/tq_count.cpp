@@ -291,8 +291,7 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
       const int src = sync_terms(s, s->stream);
       if (src != TQ_OK) return src;
       std::vector<uint4> wgs;
-      for (const auto &kv : temp_slot)
-        for (uint32_t j = 0; j < s->terms[kv.first].n_blocks; j += 4u) wgs.push_back(make_uint4(kv.first, j, kv.second, 0u));
+      for (const auto &kv : temp_slot) push_scatter_work(wgs, s, kv.first, kv.second);
       rc = s->d_count_bits.ensure((size_t)temp_slot.size() * words_per_list * sizeof(uint32_t));
       if (rc == TQ_OK) rc = s->d_count_wgs.ensure(wgs.size() * sizeof(uint4));
       if (rc != TQ_OK) return rc;
@@ -331,17 +330,15 @@ int count_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint
     for (uint32_t i = 0; i < n; ++i) qs[i] = given[all_q[i]];
     std::vector<uint64_t> starts((size_t)n + 1u);
     // (sloppy phrases are named, and their overflow words indexed, by the caller's query: all_q)
-    const int rc = docset_batch(s, qs.data(), n, nullptr, nullptr, 0, starts.data(), false, false, nullptr, true, all_q.data(), n_queries);
+    DocsetCall call("tq_count_batch", DocsetConsumer::kCount);
+    call.out_starts = starts.data();
+    call.caller_q = all_q.data();
+    call.n_caller = n_queries;
+    const int rc = docset_batch(s, qs.data(), n, call);
     // a carried list over the cap (the verdict comes behind the count pass: `starts` is filled): the counts of the other
     // queries are written and valid, the words of this batch stay readable (tq_last_batch_slop_overflows)
-    bool overflowed = false;
-    if (rc == TQ_ERR_UNSUPPORTED && s->last_batch_slop) {
-      const std::string err = g_last_error;
-      std::vector<uint32_t> over(n_queries);
-      HIP_TRY(hipMemcpy(over.data(), s->d_slop_over.p, (size_t)n_queries * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      for (uint32_t w : over) overflowed = overflowed || w != 0u;
-      g_last_error = err;
-    }
+    // (last_batch_slop is set once every query is checked and planned: the one refusal behind that is the overflow verdict)
+    const bool overflowed = rc == TQ_ERR_UNSUPPORTED && s->last_batch_slop;
     for (uint32_t i = 0; (rc == TQ_OK || overflowed) && i < n; ++i) out_counts[all_q[i]] = (uint32_t)(starts[i + 1u] - starts[i]);
     s->slop_over_words = n_queries;
     if (rc != TQ_OK) return rc;

@@ -47,6 +47,9 @@ namespace tqi {
 
 extern thread_local std::string g_last_error;
 int fail(int code, const char *fmt, ...);
+inline int launched(hipError_t e, const char *what) {  // the verdict on a kernel launch: TQ_OK, or TQ_ERR_HIP naming it
+  return e == hipSuccess ? TQ_OK : fail(TQ_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+}
 #define HIP_TRY(expr)                                                                    \
   do {                                                                                   \
     hipError_t e__ = (expr);                                                             \
@@ -357,6 +360,7 @@ struct tq_segment {
   DevBuf d_docset_trees;  // ... of phrases and nested queries (tq_docset_tree.hip): their TqdTreeQuery records
   // sort by fast field (tq_sort.hip): the queries' k, the slices' lists and counts, the host variant's rows
   DevBuf d_sort_ks, d_sort_partials, d_sort_slice_counts, d_sort_rows;
+  PinnedBuf h_sort_ks;  // ... the queries' k on their way up
   DevBuf d_agg_rows;  // aggregations (tq_agg.hip): the host variant's records and bucket rows
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
@@ -1023,27 +1027,24 @@ struct FlatClauses {
   uint32_t n_cl = 0, n_must = 0, n_should = 0;  // (n_should: the Should clauses that hold a list)
   bool empty = false;                           // a Must clause without a list: no doc matches
   uint32_t msm = 0;                             // minimum_number_should_match (a query with All clauses: what they left of it)
+  // BooleanWeight::complex_scorer (boolean_weight.rs:236-431): no list can match / all of the Should clauses are wanted: Must clauses
+  bool empty_set() const { return !all_based && (empty || msm > n_should || (n_must == 0 && n_should == 0)); }
+  bool should_is_must() const { return !all_based && msm >= 2 && msm == n_should; }
   // a query with All clauses that came out ALL-BASED (tq_all.cpp): the Should and MustNot clauses above, over every doc
   bool all_based = false, all_boost_mixed = false;
   float all_base = 0.0f;
 };
 enum { FLAT_OK = 0, FLAT_UNSUPPORTED, FLAT_INVALID };
 int parse_flat_clauses(tq_segment *s, const tq_query &q, FlatClauses &fc, const char **why);
-// ---- tq_docset.cpp: full doc sets (tq_docset_batch* / tq_docset_scored_batch*)
+// ---- tq_docset.cpp: full doc sets (tq_docset_batch* / tq_docset_scored_batch*) and what else consumes their match words
 // the query as a TqkDocsetQuery: FLAT_*; lists without a bitmap are left as their term HANDLE in dq.dense (narrow bit set);
 // fc_out (or null): the clauses it was made from
 int docset_expression(tq_segment *s, const tq_query &q, TqkDocsetQuery &dq, const char **why, FlatClauses *fc_out = nullptr);
 // the scoring lists of the same query in summation order (weights and access paths; cache_idx is left to the caller)
 void score_expression(tq_segment *s, const tq_query &q, const FlatClauses &fc, TqkScoreQuery &sq);
-// out_docs / out_scores / out_starts: host buffers, or device buffers (device_out) with the work only enqueued on
-// hip_stream; scored: out_scores[i] = the score of out_docs[i] (tq_docset_scored_batch*), else out_scores is not used;
-// count_only (host outputs): the count pass and the row starts alone, no doc is written (tq_count_batch's ALL-BASED queries)
-// Sort by fast field (tq_sort.cpp): with a SortSpec the call validates, plans, cuts sub-batches, scatters and evaluates trees
-// and sloppy phrases exactly as for a doc set, and the selection launch(es) of tq_sort.hip take the place of every
-// sub-batch's count / scan / write passes.  Everything is enqueued (device_out = true; the pointers are DEVICE memory, the
-// rows of query q at q * out_stride); out_docs / out_scores / out_cap / out_starts of the call are not used.
+// Sort by fast field (tq_sort.cpp): the selection launch(es) of tq_sort.hip in place of every sub-batch's count / scan /
+// write passes.  The pointers are DEVICE memory, the rows of query q at q * out_stride.
 struct SortSpec {
-  const char *fn;  // the entry point's name, for messages
   uint32_t column;
   uint32_t ascending, nulls_first;
   uint32_t out_stride;
@@ -1051,12 +1052,14 @@ struct SortSpec {
   uint64_t *d_values;
   uint8_t *d_has_value;
   uint32_t *d_counts;
+  // sort_prepare: the slices per query, the key slots per lane the largest k needs; the column has a presence table
+  uint32_t n_slices = 1, words_per_slice = 0, kpl = 1;
+  bool optional = false;
 };
-// Aggregations (tq_agg.cpp): an AggSpec is taken like a SortSpec (not both) — the aggregation launch of tq_agg.hip in place
-// of every sub-batch's passes, behind one launch that initialises the whole batch's records and bucket rows.  d_stats /
-// d_buckets are DEVICE memory, the record of query q at q, its row at q * bucket_stride.
+// Aggregations (tq_agg.cpp): the aggregation launch of tq_agg.hip in place of every sub-batch's passes, behind one launch
+// that initialises the whole batch's records and bucket rows.  d_stats / d_buckets are DEVICE memory, the record of
+// query q at q, its row at q * bucket_stride.
 struct AggSpec {
-  const char *fn;  // the entry point's name, for messages
   uint32_t column;
   uint32_t value_type;          // TQ_VALUE_*
   tq_agg_hist_plan_t plan;      // n_buckets == 0: no histogram (none asked for, or no value can be in bounds)
@@ -1064,13 +1067,66 @@ struct AggSpec {
   uint32_t bucket_stride;
   tq_agg_stats_t *d_stats;
   uint32_t *d_buckets;
+  uint32_t n_slices = 1, words_per_slice = 0;  // agg_prepare: as for a sort
+  bool optional = false;
 };
-int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, uint32_t *out_docs, float *out_scores,
-                 uint64_t out_cap, uint64_t *out_starts, bool scored, bool device_out, void *hip_stream, bool count_only = false,
-                 const uint32_t *caller_q = nullptr, uint32_t n_caller = 0, const SortSpec *sort = nullptr,
-                 const AggSpec *agg = nullptr);
-// (caller_q / n_caller — tq_count_batch, which hands over a sub-array of its n_caller queries: query qi of this call is
-// the caller's caller_q[qi]; sloppy phrases are named, and their overflow words indexed, by that)
+// One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
+// kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass
+// and out_starts alone, no doc is written (tq_count_batch); kSort / kAgg (device outputs): their spec.
+enum class DocsetConsumer { kRows, kCount, kSort, kAgg };
+struct DocsetCall {
+  const char *fn;  // the entry point's name, for messages
+  DocsetConsumer consumer;
+  bool scored = false;
+  bool device_out;  // the outputs are device buffers and the work is only enqueued, on hip_stream (null: the segment's)
+  void *hip_stream = nullptr;
+  uint32_t *out_docs = nullptr;  // kRows / kCount
+  float *out_scores = nullptr;
+  uint64_t out_cap = 0, *out_starts = nullptr;
+  SortSpec *sort = nullptr;  // kSort
+  AggSpec *agg = nullptr;    // kAgg
+  // tq_count_batch hands over a sub-array of its n_caller queries: query qi of this call is the caller's caller_q[qi];
+  // sloppy phrases are named, and their overflow words indexed, by that
+  const uint32_t *caller_q = nullptr;
+  uint32_t n_caller = 0;
+  explicit DocsetCall(const char *name, DocsetConsumer c = DocsetConsumer::kRows)
+      : fn(name), consumer(c), device_out(c == DocsetConsumer::kSort || c == DocsetConsumer::kAgg) {}
+};
+int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, const DocsetCall &call);
+// Consecutive whole queries whose lists without a bitmap, tree results and sloppy-phrase results fit the scratch together.
+struct DocsetSubBatch {
+  uint32_t q0 = 0, q1 = 0;
+  size_t wg0 = 0, wg1 = 0;  // its part of the scatter work list
+  uint32_t t0 = 0, t1 = 0;  // ... and of the tree records (tq_docset_tree.hip)
+  uint32_t s0 = 0, s1 = 0;  // ... and of the sloppy phrases' records (tq_phrase_slop.hip)
+  bool any_phrase = false;  // some tree of its queries has a phrase atom
+  uint32_t n_temp = 0;      // its slots of the scratch
+  bool score_blocks = false;  // some scoring list of its queries is reached by the block search
+};
+struct DocsetCut {
+  std::vector<DocsetSubBatch> subs;
+  std::vector<uint4> wgs;  // the scatter work list, sub-batch after sub-batch
+  uint32_t max_sub_temp = 0, max_sub_n = 0;  // the most slots / queries of one sub-batch
+};
+// Cuts the batch (host arithmetic alone; checked on the CPU by tools/planbench/plan_check.cpp).  A sub-batch holds at
+// most max_sub_queries queries and — unless it is a single query — max_temp slots.  In: every narrow dqs[].dense[m] the
+// list's term handle; tree_q / slop_qi the ascending queries whose one list is the result of tqs[] / slop_qs[] in the
+// same order; sqs empty or one per query.  Out: narrow dense[m] and part_start are SLOTS of their sub-batch's scratch.
+void cut_docset_subs(const tq_segment *s, std::vector<TqkDocsetQuery> &dqs, const std::vector<TqkScoreQuery> &sqs,
+                     const std::vector<uint32_t> &tree_q, std::vector<TqdTreeQuery> &tqs, const std::vector<uint32_t> &slop_qi,
+                     std::vector<TqdSlopQuery> &slop_qs, uint32_t max_temp, uint32_t max_sub_queries, DocsetCut &cut);
+// the scatter work list of one list without a bitmap: one entry (handle, first block, slot, 0) per four blocks
+inline void push_scatter_work(std::vector<uint4> &wgs, const tq_segment *s, uint32_t handle, uint32_t slot) {
+  for (uint32_t j = 0; j < s->terms[handle].n_blocks; j += 4u) wgs.push_back(make_uint4(handle, j, slot, 0u));
+}
+// ---- tq_sort.cpp / tq_agg.cpp as consumers of a doc-set call.  *_prepare, from the size-and-upload stage (the batch's
+// scratch is idle, d_qmatches sized): the launch geometry into the spec, the consumer's buffers, uploads and zeroes on st.
+// *_launch, per sub-batch behind its match bits: p is the sub-batch's filled TqkDocsetParams, q0 its first query.
+uint32_t pick_slices(const tq_segment *s, int forced, uint32_t step_words, uint32_t max_sub_n, uint32_t n_words);
+int sort_prepare(tq_segment *s, SortSpec &spec, const tq_query *queries, uint32_t n_queries, uint32_t max_sub_n, uint32_t n_words, hipStream_t st);
+int sort_launch(tq_segment *s, const SortSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
+int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_sub_n, uint32_t n_words, hipStream_t st);
+int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
 // Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the
@@ -1098,6 +1154,8 @@ int slop_view(const tq_segment *s, const tq_query &q, uint32_t qi, const char *f
 int plan_slop_query(tq_segment *s, const tq_query &view, uint32_t qi, uint32_t slop, TqdSlopQuery &sq, uint64_t &qbytes, bool result_bitmap);
 // TQ_ERR_UNSUPPORTED naming the first query with a non-zero overflow word, or TQ_OK
 int slop_overflow_verdict(const char *fn, const uint32_t *over, uint32_t n_queries);
+// ... over the words the last batch left on the device, read back (the batch is over); no sloppy phrase in it: TQ_OK
+int slop_overflow_readback(tq_segment *s, const char *fn);
 int slop_overflow_fail(const char *fn, uint32_t qi, uint32_t docs);
 // ---- the planners
 int build_group_chunks(Group &g, bool or_windows, PlanScratch &ps, bool boolean_group = false);

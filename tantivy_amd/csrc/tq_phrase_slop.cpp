@@ -85,6 +85,13 @@ int slop_overflow_verdict(const char *fn, const uint32_t *over, uint32_t n_queri
   return TQ_OK;
 }
 
+int slop_overflow_readback(tq_segment *s, const char *fn) {
+  if (!s->last_batch_slop) return TQ_OK;
+  std::vector<uint32_t> over(s->slop_over_words);
+  HIP_TRY(hipMemcpy(over.data(), s->d_slop_over.p, over.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return slop_overflow_verdict(fn, over.data(), (uint32_t)over.size());
+}
+
 }  // namespace tqi
 
 extern "C" int tq_last_batch_slop_overflows(tq_segment *s, uint32_t *out, uint32_t n) {

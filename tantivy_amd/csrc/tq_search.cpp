@@ -1133,10 +1133,6 @@ DevBuf &list_stage(DeviceScratch &sc, int gi) {
   return gi == kGAShare ? sc.ashare_stage : gi == kGBShare ? sc.bshare_stage : sc.share_stage;
 }
 
-int launched(hipError_t e, const char *what) {
-  return e == hipSuccess ? TQ_OK : fail(TQ_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-}
-
 // Every buffer the batch zeroes, cleared by one launch; the result-list groups' grids, words and staging lists.
 int zero_batch_buffers(Batch &b) {
   TqkZeroParams zp{};

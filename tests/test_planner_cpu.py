@@ -110,6 +110,19 @@ def test_count_expressions_match_boolean_semantics(plan_check, seed):
     assert "count:" in r.stdout and "ok" in r.stdout
 
 
+@pytest.mark.parametrize("seed", range(4))
+def test_docset_sub_batches_tile_the_batch(plan_check, seed):
+    """tq_docset.cpp::cut_docset_subs (the doc-set route's sub-batch cutter, host arithmetic alone) over a host-only
+    segment: the sub-batches tile the queries, the scatter work list and the tree / sloppy-phrase records in order; none
+    exceeds max_sub_queries, none of several queries exceeds max_temp slots; within a sub-batch equal handles share a
+    slot, different handles and every tree / sloppy-phrase result have their own, all below n_temp; every (list without a
+    bitmap, four-block group) stands in the sub-batch's work exactly once with its slot; max_sub_temp / max_sub_n are the
+    maxima (odd seeds: a scored call's score_blocks flags as well)."""
+    r = subprocess.run([plan_check, str(seed), "subs"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr + r.stdout
+    assert "subs:" in r.stdout and "ok" in r.stdout
+
+
 def test_eight_planners_at_once(tmp_path_factory):
     """eight ranks of a node plan their batches at the same time on the node's few
     granted CPUs.  Eight concurrent processes (one per CPU where there are eight) each plan the headline

@@ -873,8 +873,139 @@ static int check_count(int seed) {
   return 0;
 }
 
+// The doc-set route's sub-batch cutter (tq_docset.cpp::cut_docset_subs) over a host-only segment: 60 queries of 1-16 lists
+// over 40 handles, about half of them without a bitmap (1-9 blocks), every seventh query a tree, every eleventh a sloppy
+// phrase, under a tight and a loose scratch (max_temp 16 / 4096) and query limit (max_sub_queries 5 / 2^26).
+static int check_subs(int seed) {
+  std::mt19937 rng(seed + 1700);
+  auto uni = [&](uint32_t lo, uint32_t hi) { return std::uniform_int_distribution<uint32_t>(lo, hi)(rng); };
+  tq_segment seg;
+  const uint32_t n_handles = 40, n_queries = 60;
+  static const uint2 kBitmap[1] = {};  // what a list with a bitmap points at: never read here
+  std::vector<uint8_t> narrow(n_handles);
+  for (uint32_t h = 0; h < n_handles; ++h) {
+    TermHost th;
+    narrow[h] = (uint8_t)uni(0, 1);
+    th.n_blocks = uni(1, 9);
+    seg.terms.push_back(th);
+  }
+  std::vector<TqkDocsetQuery> dqs(n_queries);
+  std::vector<TqkScoreQuery> sqs(seed % 2 ? n_queries : 0u);  // (odd seeds: a scored call)
+  std::vector<uint32_t> tree_q, slop_qi;
+  std::vector<TqdTreeQuery> tqs;
+  std::vector<TqdSlopQuery> slop_qs;
+  std::vector<std::vector<uint32_t>> handles(n_queries);  // per query and list: the handle of a list without a bitmap, or ~0
+  for (uint32_t qi = 0; qi < n_queries; ++qi) {
+    TqkDocsetQuery &dq = dqs[qi];
+    dq = TqkDocsetQuery{};
+    if (qi % 7u == 6u || qi % 11u == 10u) {  // one Must list that is a result slot
+      dq.n_terms = dq.narrow = dq.clause_end = 1u;
+      if (qi % 7u == 6u) {
+        tree_q.push_back(qi);
+        tqs.push_back(TqdTreeQuery{});
+        tqs.back().has_phrase = uni(0, 2) == 0 ? 1u : 0u;
+        tqs.back().part_start = ~0u;
+      } else {
+        slop_qi.push_back(qi);
+        slop_qs.push_back(TqdSlopQuery{});
+        slop_qs.back().part_start = ~0u;
+      }
+      continue;
+    }
+    dq.n_terms = uni(1, 16);
+    for (uint32_t m = 0; m < dq.n_terms; ++m) {
+      const uint32_t h = uni(0, n_handles - 1);
+      handles[qi].push_back(narrow[h] ? h : ~0u);
+      dq.dense[m] = narrow[h] ? (const uint2 *)(uintptr_t)h : kBitmap;
+      if (narrow[h]) dq.narrow |= 1u << m;
+    }
+    if (!sqs.empty()) {
+      sqs[qi].n_lists = uni(0, 4);
+      for (uint32_t m = 0; m < sqs[qi].n_lists; ++m) sqs[qi].access |= (uni(0, 5) ? (uint32_t)TQK_SCORE_BITMAP : (uint32_t)TQK_SCORE_BLOCKS) << (2u * m);
+    }
+  }
+  uint32_t n_subs_seen = 0;
+  for (const uint32_t max_temp : {16u, 4096u})
+    for (const uint32_t max_sub_queries : {5u, 1u << 26}) {
+      std::vector<TqkDocsetQuery> d = dqs;
+      std::vector<TqdTreeQuery> t = tqs;
+      std::vector<TqdSlopQuery> sl = slop_qs;
+      DocsetCut cut;
+      cut_docset_subs(&seg, d, sqs, tree_q, t, slop_qi, sl, max_temp, max_sub_queries, cut);
+      uint32_t q_at = 0, t_at = 0, s_at = 0, max_sub_temp = 0, max_sub_n = 0;
+      size_t wg_at = 0;
+      for (const DocsetSubBatch &sb : cut.subs) {
+        // the sub-batches tile [0, n) in order, and so do their parts of the work list and of the tree / slop records
+        if (sb.q0 != q_at || sb.q1 <= sb.q0 || sb.wg0 != wg_at || sb.wg1 < sb.wg0 || sb.t0 != t_at || sb.t1 < sb.t0 || sb.s0 != s_at || sb.s1 < sb.s0)
+          return fail_msg("sub-batch ranges do not continue the ones before", sb.q0, q_at);
+        q_at = sb.q1, wg_at = sb.wg1, t_at = sb.t1, s_at = sb.s1;
+        if (sb.q1 - sb.q0 > max_sub_queries) return fail_msg("a sub-batch holds more queries than max_sub_queries", sb.q0, sb.q1);
+        if (sb.n_temp > max_temp && sb.q1 - sb.q0 != 1u) return fail_msg("a sub-batch of several queries takes more than max_temp slots", sb.q0, sb.n_temp);
+        std::unordered_map<uint32_t, uint32_t> slot_of;  // handle -> slot
+        std::vector<uint8_t> taken(sb.n_temp, 0);       // slot -> 1 a list's, 2 a result's
+        uint32_t n_tree = 0, n_slop = 0;
+        bool any_phrase = false, score_blocks = false;
+        for (uint32_t qi = sb.q0; qi < sb.q1; ++qi) {
+          const bool tree = qi % 7u == 6u, slop = !tree && qi % 11u == 10u;
+          if (tree || slop) {  // a result slot of its own, in its record and in the query's one list
+            const uint32_t part = tree ? t[sb.t0 + n_tree].part_start : sl[sb.s0 + n_slop].part_start;
+            if ((tree ? tree_q[sb.t0 + n_tree] : slop_qi[sb.s0 + n_slop]) != qi) return fail_msg("the t / s range does not hold the query's record", qi);
+            if (part >= sb.n_temp || taken[part] || (uint32_t)(uintptr_t)d[qi].dense[0] != part) return fail_msg("a result's slot is out of range, shared, or not the query's", qi, part);
+            taken[part] = 2;
+            any_phrase = any_phrase || (tree && t[sb.t0 + n_tree].has_phrase);
+            (tree ? n_tree : n_slop)++;
+            continue;
+          }
+          for (uint32_t m = 0; m < d[qi].n_terms; ++m) {
+            const uint32_t h = handles[qi][m];
+            if (h == ~0u) {
+              if (d[qi].dense[m] != kBitmap) return fail_msg("a bitmap pointer was touched", qi, m);
+              continue;
+            }
+            const uint32_t got = (uint32_t)(uintptr_t)d[qi].dense[m];
+            if (got >= sb.n_temp || taken[got] == 2) return fail_msg("a list's slot is out of range or a result's", qi, got);
+            const auto it = slot_of.emplace(h, got).first;
+            if (it->second != got) return fail_msg("one handle, two slots in a sub-batch", qi, h);
+            taken[got] = 1;
+          }
+          for (uint32_t m = 0; !sqs.empty() && m < sqs[qi].n_lists; ++m) score_blocks = score_blocks || ((sqs[qi].access >> (2u * m)) & 3u) == TQK_SCORE_BLOCKS;
+        }
+        if (n_tree != sb.t1 - sb.t0 || n_slop != sb.s1 - sb.s0) return fail_msg("the t / s ranges do not count the sub-batch's trees / sloppy phrases", sb.q0);
+        if (slot_of.size() + n_tree + n_slop != sb.n_temp) return fail_msg("n_temp is not the number of slots in use", sb.q0, sb.n_temp);
+        std::vector<uint32_t> seen_slots;
+        for (const auto &kv : slot_of) seen_slots.push_back(kv.second);
+        std::sort(seen_slots.begin(), seen_slots.end());
+        if (std::adjacent_find(seen_slots.begin(), seen_slots.end()) != seen_slots.end()) return fail_msg("two handles share a slot", sb.q0);
+        if (any_phrase != sb.any_phrase || score_blocks != sb.score_blocks) return fail_msg("any_phrase / score_blocks is not the sub-batch's", sb.q0);
+        // every (list without a bitmap, group of four blocks) once in the sub-batch's work, with the list's slot
+        std::vector<uint32_t> groups;
+        for (size_t w = sb.wg0; w < sb.wg1; ++w) {
+          const uint4 e = cut.wgs[w];
+          const auto it = slot_of.find(e.x);
+          if (it == slot_of.end() || e.z != it->second || e.y % 4u || e.y >= seg.terms[e.x].n_blocks || e.w) return fail_msg("a work entry names no list of the sub-batch, or another slot", sb.q0, e.x);
+          groups.push_back(e.x * 16u + e.y / 4u);
+        }
+        std::sort(groups.begin(), groups.end());
+        if (std::adjacent_find(groups.begin(), groups.end()) != groups.end()) return fail_msg("a block group stands in the work list twice", sb.q0);
+        size_t want_groups = 0;
+        for (const auto &kv : slot_of) want_groups += (seg.terms[kv.first].n_blocks + 3u) / 4u;
+        if (groups.size() != want_groups) return fail_msg("the work list misses a block group", sb.q0, (long)groups.size());
+        max_sub_temp = std::max(max_sub_temp, sb.n_temp);
+        max_sub_n = std::max(max_sub_n, sb.q1 - sb.q0);
+      }
+      if (q_at != n_queries || wg_at != cut.wgs.size() || t_at != tree_q.size() || s_at != slop_qi.size()) return fail_msg("the sub-batches do not reach the end", q_at);
+      if (max_sub_temp != cut.max_sub_temp || max_sub_n != cut.max_sub_n) return fail_msg("max_sub_temp / max_sub_n are not the maxima", cut.max_sub_temp, cut.max_sub_n);
+      if (max_temp == 4096u && max_sub_queries == (1u << 26) && cut.subs.size() != 1u) return fail_msg("a batch that fits was cut", (long)cut.subs.size());
+      if (max_sub_queries == 5u && cut.subs.size() < n_queries / 5u) return fail_msg("fewer sub-batches than the query limit asks for", (long)cut.subs.size());
+      n_subs_seen += (uint32_t)cut.subs.size();
+    }
+  printf("subs: %u sub-batches over 4 settings ok\n", n_subs_seen);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   const int seed = argc > 1 ? atoi(argv[1]) : 1;
+  if (argc > 2 && !strcmp(argv[2], "subs")) return check_subs(seed);
   if (argc > 2 && !strcmp(argv[2], "share")) return check_share(seed);
   if (argc > 2 && !strcmp(argv[2], "pool")) return check_pool(seed);
   if (argc > 2 && !strcmp(argv[2], "dense")) return check_dense(seed);
