@@ -951,6 +951,60 @@ int tq_agg_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, c
 int tq_agg_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_request *req,
                         tq_agg_stats_t *d_out_stats, uint32_t *d_out_buckets, uint32_t bucket_stride, void *hip_stream);
 
+/* ---- sub-aggregations: stats of a second column per histogram bucket ----
+ * replaces a `histogram` / `date_histogram` with ONE `stats` / `avg` / `min` / `max` / `sum` / `value_count` sub-aggregation
+ * (src/aggregation/bucket/histogram/histogram.rs:489-505, the nested path of collect; src/aggregation/metric/stats.rs:
+ * 282-306 SegmentStatsCollector::collect under a parent_bucket_id, :164 IntermediateStats::collect): "avg / max of latency
+ * per hour".  One pass over every query's match bits, no doc set written.
+ *
+ * req is tq_agg_batch's request for the BUCKET column A and must ask for the histogram (histogram == 0: TQ_ERR_INVALID); the
+ * plan is tq_agg_histogram_plan's.  out_stats and out_buckets are what tq_agg_batch writes for the same request, bit for bit.
+ * out_bucket_stats: row q = out_bucket_stats + q * bucket_stride — the count rows' stride — of which entries [0, n_buckets)
+ * are written and NOTHING else; entry i is the record of the METRIC column B over exactly the docs counted in bucket i
+ * (the docs with a value in A inside the effective bounds; a doc outside them, or without a value in A, enters no record):
+ *   count                 those docs with a value in B (a TQ_CARD_OPTIONAL B without a value contributes nothing: the
+ *                         reference's fetch_block_with_missing with missing = None)
+ *   min_value, max_value  in B's u64 space; UINT64_MAX / 0 when count == 0
+ *   sum_lo, sum_hi        the exact 128-bit sum of B's u64-space values, as in tq_agg_stats_t (it equals the reference's
+ *                         Kahan f64 sum in doc order wherever every partial sum is below 2^53)
+ * B has its own value type: with TQ_VALUE_F64 both sum words are written as 0 and min / max can be a NaN at either end of
+ * the mapped order.  B may be the column A.
+ * Refused before any launch, the segment stays usable (TQ_ERR_INVALID): what tq_agg_batch refuses, histogram == 0, a metric
+ * column that is not live, a metric value_type above TQ_VALUE_F64, a null out_bucket_stats when n_buckets > 0.  Query
+ * shapes, options, the sloppy-phrase verdict and the message texts are tq_agg_batch's under this function's name.
+ * Launches: tq_agg_batch's, with the records initialised beside the rows and agg_sub_kernel (tq_agg_sub.hip) as the
+ * aggregation launch: per bucketed doc a second column read, then the bucket's entry of a workgroup-private LDS table
+ * (n_buckets <= min("agg_lds_buckets", the kernel's capacity: 40 bytes per bucket) — flushed once with vector atomics) or,
+ * above it, the query's row and records directly.  Integer atomics: deterministic.
+ * Afterwards tq_last_batch_match_counts as before, kernel_mask = TQ_KERNEL_AGG_SUB (| TQ_KERNEL_DOCSET_TREE |
+ * TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = tq_agg_batch's for column A
+ *                     + 8 per bucketed doc with a value in B
+ *                     + 8 per bucketed doc of a TQ_CARD_OPTIONAL B (its presence word)
+ *                     + 40 x n_buckets per query.
+ * Not served: several metric columns or sibling aggregations in one call, nested buckets, `missing`, F64 sums. */
+typedef struct tq_agg_metric_request {
+  uint32_t column;     /* metric column B: a handle of tq_column_upload; may equal req->column */
+  uint8_t value_type;  /* tq_value_type of B */
+  uint8_t reserved[3]; /* zero */
+} tq_agg_metric_request; /* 8 bytes */
+typedef struct tq_agg_bucket_stats_t {
+  uint64_t count;                /* docs of the bucket with a value in B */
+  uint64_t min_value, max_value; /* B's u64 space; UINT64_MAX / 0 when count == 0 */
+  uint64_t sum_lo, sum_hi;       /* exact 128-bit sum; TQ_VALUE_F64: written as 0 */
+} tq_agg_bucket_stats_t; /* 40 bytes */
+int tq_agg_sub_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_request *req,
+                     const tq_agg_metric_request *metric, tq_agg_stats_t *out_stats, uint32_t *out_buckets,
+                     tq_agg_bucket_stats_t *out_bucket_stats, uint32_t bucket_stride);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream), no host synchronisation.  The call itself
+ * zeroes what it accumulates into: the same buffers may be used again. */
+int tq_agg_sub_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_request *req,
+                            const tq_agg_metric_request *metric, tq_agg_stats_t *d_out_stats, uint32_t *d_out_buckets,
+                            tq_agg_bucket_stats_t *d_out_bucket_stats, uint32_t bucket_stride, void *hip_stream);
+/* The LDS tables' capacities in buckets of the two instantiations of agg_sub_kernel: out[0] the small one, out[1] the
+ * large one; a histogram of more than min("agg_lds_buckets", out[1]) buckets is accumulated in global memory. */
+void tq_agg_sub_lds_capacities(uint32_t out[2]);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -990,6 +1044,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_PHRASE_SLOP 0x40000u /* phrase_slop_kernel / phrase_slop_bits_kernel (TQ_MODE_PHRASE with slop > 0, over bitmap words) */
 #define TQ_KERNEL_SORT 0x80000u        /* sort_select_kernel / sort_merge_kernel (tq_search_sorted_batch*: top k by a fast-field column) */
 #define TQ_KERNEL_AGG 0x100000u        /* agg_kernel (tq_agg_batch*: stats and histogram of a fast-field column) */
+#define TQ_KERNEL_AGG_SUB 0x200000u    /* agg_sub_kernel (tq_agg_sub_batch*: the histogram with a metric column's stats per bucket) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -1084,7 +1139,8 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        "agg_lds_buckets" (0..8192 = the kernel's LDS capacity, default 8192; any other value: TQ_ERR_INVALID):
  *        tq_agg_batch* — the largest n_buckets a workgroup counts in a private LDS table that it flushes once (a
  *        table of 2 048 buckets, or of 8 192 at half the wavefronts per SIMD: two instantiations); above it every doc is
- *        an atomic add on the query's row, several times slower on dense queries.  Results do not depend on it,
+ *        an atomic add on the query's row, several times slower on dense queries.  tq_agg_sub_batch*: min(the option,
+ *        tq_agg_sub_lds_capacities' large capacity).  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

@@ -64,6 +64,7 @@ KERNEL_DOCSET_TREE_SCORE = 0x20000
 KERNEL_PHRASE_SLOP = 0x40000
 KERNEL_SORT = 0x80000
 KERNEL_AGG = 0x100000
+KERNEL_AGG_SUB = 0x200000
 VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
 AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
 SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
@@ -74,7 +75,7 @@ NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
-                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg"}
+                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub"}
 
 
 def kernel_names(mask):
@@ -167,6 +168,7 @@ EXPORTS = [
     "tq_column_parse", "tq_column_upload", "tq_column_info", "tq_column_release", "tq_column_decode", "tq_range_prepare",
     "tq_search_sorted_batch", "tq_search_sorted_batch_device",
     "tq_agg_histogram_plan", "tq_agg_batch", "tq_agg_batch_device",
+    "tq_agg_sub_batch", "tq_agg_sub_batch_device", "tq_agg_sub_lds_capacities",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -212,6 +214,14 @@ class TqAggHistPlan(C.Structure):  # tq_agg_hist_plan_t
 # tq_agg_stats_t as a numpy structured dtype: one 64-byte record per query
 AGG_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("matches", "count", "min_value", "max_value", "sum_lo", "sum_hi",
                                                      "in_bounds", "out_of_range")])
+
+
+class TqAggMetricRequest(C.Structure):  # tq_agg_metric_request
+    _fields_ = [("column", C.c_uint32), ("value_type", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+# tq_agg_bucket_stats_t: one 40-byte record per bucket of a sub-aggregation's row
+AGG_BUCKET_STATS_DTYPE = np.dtype([(n, np.uint64) for n in ("count", "min_value", "max_value", "sum_lo", "sum_hi")])
 
 
 def _agg_request(column, value_type, histogram):
@@ -282,6 +292,39 @@ def agg_stats_finalize(stats_row, value_type):
         return {"count": 0, "sum": total, "min": None, "max": None, "avg": None}
     return {"count": count, "sum": total, "min": agg_value_from_u64(stats_row["min_value"], value_type),
             "max": agg_value_from_u64(stats_row["max_value"], value_type), "avg": None if total is None else total / count}
+
+
+def agg_sub_lds_capacities():
+    """tq_agg_sub_lds_capacities: the LDS tables' capacities in buckets of agg_sub_kernel's (small, large) instantiation.
+    Needs no device."""
+    out = (C.c_uint32 * 2)()
+    lib().tq_agg_sub_lds_capacities(out)
+    return int(out[0]), int(out[1])
+
+
+def merge_bucket_stats(parts):
+    """The segments' bucket-record rows of ONE query and ONE request: parts = [(plan, records)] as raw_agg_sub returns them
+    (plan dict, records = the query's row of AGG_BUCKET_STATS_DTYPE, or dicts).  The rows are aligned by base_pos over
+    merge_histograms' range; counts and 128-bit sums add, min / max are the extremes.  -> (keys, records): records are
+    dicts of Python ints like merge_agg_stats', which agg_stats_finalize takes.  Host only."""
+    parts = [(p, r) for p, r in parts if p["n_buckets"]]
+    if not parts:
+        return [], []
+    interval, offset = parts[0][0]["interval"], parts[0][0]["offset"]
+    assert all(p["interval"] == interval and p["offset"] == offset for p, _ in parts)
+    lo = min(p["base_pos"] for p, _ in parts)
+    hi = max(p["base_pos"] + p["n_buckets"] for p, _ in parts)
+    out = [{"count": 0, "min_value": (1 << 64) - 1, "max_value": 0, "sum": 0} for _ in range(hi - lo)]
+    for p, recs in parts:
+        for i in range(p["n_buckets"]):
+            o, r = out[p["base_pos"] - lo + i], recs[i]
+            o["count"] += int(r["count"])
+            o["sum"] += int(r["sum_lo"]) + (int(r["sum_hi"]) << 64)
+            o["min_value"] = min(o["min_value"], int(r["min_value"]))
+            o["max_value"] = max(o["max_value"], int(r["max_value"]))
+    for o in out:
+        o["sum_lo"], o["sum_hi"] = o["sum"] & ((1 << 64) - 1), o["sum"] >> 64
+    return [float(pos) * interval + offset for pos in range(lo, hi)], out
 
 
 def merge_histograms(parts):
@@ -394,6 +437,12 @@ def lib():
     L.tq_agg_histogram_plan.argtypes = [C.POINTER(TqColumnInfo), C.POINTER(TqAggRequest), C.POINTER(TqAggHistPlan)]
     L.tq_agg_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest), vp, u32p, C.c_uint32]
     L.tq_agg_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest), vp, vp, C.c_uint32, vp]
+    L.tq_agg_sub_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest), C.POINTER(TqAggMetricRequest),
+                                   vp, u32p, vp, C.c_uint32]
+    L.tq_agg_sub_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRequest),
+                                          C.POINTER(TqAggMetricRequest), vp, vp, vp, C.c_uint32, vp]
+    L.tq_agg_sub_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
+    L.tq_agg_sub_lds_capacities.restype = None
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -1398,6 +1447,60 @@ class DeviceIndex:
         return lib().tq_agg_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req), d_stats.data_ptr(),
                                          d_buckets.data_ptr() if d_buckets is not None else None, int(stride),
                                          C.c_void_p(stream) if stream else None)
+
+    # ---- sub-aggregations (tq_agg.cpp, tq_agg_sub.hip)
+    def raw_agg_sub(self, queries, column, value_type, histogram, metric_column, metric_value_type, segment_ord=0, device=False,
+                    stride=None):
+        """Direct tq_agg_sub_batch on one segment: raw_agg's arguments for the bucket column (histogram = None is refused by
+        the call) and the metric column with its value type.  -> (stats, buckets [n, n_buckets] uint32, bucket_stats
+        [n, n_buckets] of AGG_BUCKET_STATS_DTYPE, plan dict).  stride: the stride of both kinds of rows in the call (default
+        n_buckets); device=True: through tq_agg_sub_batch_device into torch tensors on the segment's GPU."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_request(column, value_type, histogram)
+        metric = TqAggMetricRequest(column=int(metric_column), value_type=int(metric_value_type))
+        plan = TqAggHistPlan()
+        if histogram is not None:  # (the call makes the same plan; a refusal comes from the call, under its name)
+            info = TqColumnInfo()
+            if lib().tq_column_info(self.segment_raw(segment_ord), int(column), C.byref(info)) == 0:
+                lib().tq_agg_histogram_plan(C.byref(info), C.byref(req), C.byref(plan))
+        nb = int(plan.n_buckets)
+        stride = nb if stride is None else int(stride)
+        stats = np.zeros(max(1, n), AGG_STATS_DTYPE)
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_stats = torch.full((max(1, n), 8), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_rows = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            d_recs = torch.full((max(1, n), max(1, stride) * 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_sub_batch_device(self.segment_raw(segment_ord), qs, n, C.byref(req), C.byref(metric),
+                                                 d_stats.data_ptr(), d_rows.data_ptr(), d_recs.data_ptr(), stride, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            stats = d_stats.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_STATS_DTYPE)
+            rows = d_rows.cpu().numpy().view(np.uint32)
+            recs = d_recs.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_BUCKET_STATS_DTYPE).reshape(max(1, n), max(1, stride))
+        else:
+            rows = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint32)
+            recs = np.full((max(1, n), max(1, stride) * 5), 0xDEADBEEF, np.uint64)
+            _check(lib().tq_agg_sub_batch(self.segment_raw(segment_ord), qs, n, C.byref(req), C.byref(metric), stats.ctypes.data,
+                                          _u32(rows), recs.ctypes.data, stride))
+            recs = recs.reshape(-1).view(AGG_BUCKET_STATS_DTYPE).reshape(max(1, n), max(1, stride))
+        return stats[:n], rows[:n, :nb], recs[:n, :nb], _agg_plan_dict(plan, req)
+
+    def raw_agg_sub_device(self, queries, column, value_type, histogram, metric_column, metric_value_type, stride, d_stats,
+                           d_buckets, d_bucket_stats, segment_ord=0, stream=None):
+        """Direct tq_agg_sub_batch_device: raw_agg_device's tensors and d_bucket_stats (int64 / uint64, 5 words per entry,
+        len(queries) * stride entries; or None) on the segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_request(column, value_type, histogram)
+        metric = TqAggMetricRequest(column=int(metric_column), value_type=int(metric_value_type))
+        return lib().tq_agg_sub_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req), C.byref(metric),
+                                             d_stats.data_ptr(), d_buckets.data_ptr() if d_buckets is not None else None,
+                                             d_bucket_stats.data_ptr() if d_bucket_stats is not None else None, int(stride),
+                                             C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

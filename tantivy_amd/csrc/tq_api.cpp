@@ -115,8 +115,9 @@ static int segment_upload_common(tq_ctx *ctx, int device, uint32_t max_doc, cons
       if (e == hipSuccess) e = hipEventCreate(&s->ev_k0[i]);
       if (e == hipSuccess) e = hipEventCreate(&s->ev_k1[i]);
     }
-    // (word 0: the batch's matches; words 1 and 2: a sorted batch's valued matches and row entries, tq_sort.hip)
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 3u * sizeof(unsigned long long));
+    // (word 0: the batch's matches; words 1 and 2: a sorted batch's valued matches and row entries, tq_sort.hip; words 3
+    // and 4: a sub-aggregation's bucketed docs with a metric value and bucketed docs, tq_agg_sub.hip)
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 5u * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_tp_info, 2 * sizeof(TqpInfo));
     if (e != hipSuccess) rc = fail(TQ_ERR_HIP, "segment setup: %s", hipGetErrorString(e));
   }
@@ -469,6 +470,11 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
       s->stats.matches = m;
       // a value per valued match, a presence word per match of an Optional column, 13 per entry (doc, value, flag)
       s->stats.algorithmic_bytes += 8u * t[1] + (s->stats_sorted_optional ? 8u * t[0] : 0u) + 13u * t[2];
+      if (s->stats_agg_metric) {
+        unsigned long long b[2] = {0, 0};
+        HIP_TRY(hipMemcpy(b, s->d_match_counter + 3, sizeof b, hipMemcpyDeviceToHost));
+        s->stats.algorithmic_bytes += 8u * b[0] + (s->stats_agg_metric_optional ? 8u * b[1] : 0u);
+      }
       s->stats_sorted = false;
     } else {
       HIP_TRY(hipMemcpy(&m, s->d_match_counter, sizeof m, hipMemcpyDeviceToHost));

@@ -460,6 +460,9 @@ struct tq_segment {
   // per entry); set or cleared wherever stats_pending is set.  An aggregation batch (tq_agg_batch*) is counted the same
   // way: it writes no row entries, and its records and bucket rows are already in stats.algorithmic_bytes
   bool stats_sorted = false, stats_sorted_optional = false;
+  // ... a sub-aggregation (tq_agg_sub_batch*): d_match_counter[3..4] = bucketed docs with a value in the metric column,
+  // bucketed docs (8 per valued one, 8 per bucketed doc of an Optional metric column); set beside stats_sorted
+  bool stats_agg_metric = false, stats_agg_metric_optional = false;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -1069,6 +1072,10 @@ struct AggSpec {
   uint32_t *d_buckets;
   uint32_t n_slices = 1, words_per_slice = 0;  // agg_prepare: as for a sort
   bool optional = false;
+  // tq_agg_sub_batch*: a record of the metric column per bucket, at q * bucket_stride like the rows (null: no metric)
+  const tq_agg_metric_request *metric = nullptr;
+  tq_agg_bucket_stats_t *d_bucket_stats = nullptr;
+  bool metric_optional = false;  // agg_prepare
 };
 // One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
 // kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass

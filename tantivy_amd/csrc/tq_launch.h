@@ -490,6 +490,24 @@ hipError_t tqk_launch_agg_init(TqkAggStats *stats, uint32_t *buckets, uint32_t n
 hipError_t tqk_launch_agg(const TqkAggParams &p, hipStream_t st);
 uint32_t tqk_agg_step_words();   // bitmap words an aggregation workgroup takes per step
 uint32_t tqk_agg_lds_buckets();  // the LDS table's compile-time capacity in buckets
+// ---- sub-aggregations (tq_agg_sub.hip): the launch above with a record of a METRIC column B per bucket of the histogram
+// (tq_agg_sub_batch*).  The records, like the rows, are added to with vector atomics: tqk_launch_agg_sub_init in front.
+struct TqkAggBucketStats {  // = tq_agg_bucket_stats_t, 40 bytes
+  unsigned long long count, min_value, max_value, sum_lo, sum_hi;
+};
+struct TqkAggSubParams {
+  TqkAggParams a;              // the bucket column A and everything tqk_launch_agg takes (n_buckets >= 1); a.totals is [5]:
+                               // += matches, matches with a value in A, -, bucketed docs with a value in B, bucketed docs
+  TqkColumn col_b;             // the metric column
+  uint64_t min_value_b, gcd_b;
+  TqkAggBucketStats *bucket_stats;  // records of the sub-batch's first query on: [n_queries][a.bucket_stride]
+  uint32_t value_type_b;       // TQ_VALUE_F64: no sum
+};
+hipError_t tqk_launch_agg_sub_init(TqkAggBucketStats *bucket_stats, uint32_t n_queries, uint32_t n_buckets, uint32_t bucket_stride,
+                                   hipStream_t st);
+hipError_t tqk_launch_agg_sub(const TqkAggSubParams &p, hipStream_t st);
+// the LDS tables' compile-time capacities in buckets: out[0] the small instantiation's, out[1] the large one's
+void tqk_agg_sub_lds_capacities(uint32_t out[2]);
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
