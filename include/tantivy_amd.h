@@ -1005,6 +1005,94 @@ int tq_agg_sub_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n
  * large one; a histogram of more than min("agg_lds_buckets", out[1]) buckets is accumulated in global memory. */
 void tq_agg_sub_lds_capacities(uint32_t out[2]);
 
+/* ---- terms aggregation: the top values of a fast field by doc count ----
+ * replaces a `terms` bucket aggregation over a resident u64 column ("top 10 status among +body:error +timestamp:[a TO b]";
+ * src/aggregation/bucket/term_agg/mod.rs:836-899 SegmentTermCollector::collect, :1000-1111
+ * into_intermediate_bucket_result, :1328-1353 cut_off_buckets, :316-335 TermsAggregationInternal::from_req), per query of
+ * a batch, in one pass over the query's match bits and one selection pass on the device: no doc set is written and only
+ * the surviving (key, doc_count) pairs leave the device.
+ *
+ * Per query, over its alive matching docs that have a value in the column (TQ_CARD_FULL or TQ_CARD_OPTIONAL; a doc without
+ * a value enters nothing: `missing` is not served): a value's key index is (value - min_value) / gcd, an exact integer in
+ * [0, n_keys), n_keys = (max_value - min_value) / gcd + 1 — no f64 anywhere, so keys above 2^53 are exact.  The ENTRIES
+ * are the indices with a doc count > 0, ordered by req->order:
+ *   TQ_TERMS_COUNT_DESC   count descending, ties by ascending key (the reference's default order)
+ *   TQ_TERMS_COUNT_ASC    count ascending, ties by ascending key
+ *   TQ_TERMS_KEY_ASC      key ascending
+ *   TQ_TERMS_KEY_DESC     key descending
+ * (the reference cuts with select_nth_unstable / sort_unstable: which of several equal-count keys survive at the cut is
+ * unspecified there; here it is the ascending key, always).  The first n_returned = min(segment_size, distinct) entries are
+ * written in that order: out_keys[q * out_stride + j] = min_value + gcd * index — the column's u64 space: a term ordinal of
+ * a str / bytes column, which the caller resolves in the dictionary; I64 / F64 / Date are mapped back as out_values of
+ * tq_search_sorted_batch — and out_counts[q * out_stride + j] its doc count.  One tq_agg_terms_t per query:
+ *   matches                      alive matching docs
+ *   count                        those with a value = the sum of all entries' counts
+ *   sum_other_doc_count          the sum of the counts from entry number segment_size on (cut_off_buckets)
+ *   distinct                     entries before the cut
+ *   n_returned                   entries written
+ *   doc_count_error_upper_bound  the count of entry number segment_size (0-based) in that order, 0 if there is none
+ *   out_of_range                 docs whose index fell outside [0, n_keys): 0 by the column's own min / max / gcd
+ * sum_other_doc_count and doc_count_error_upper_bound do not depend on the tie-break.  `size`, `min_doc_count`,
+ * `show_term_doc_count_error`, the merge across segments and the final cut are the caller's post-processing; segment_size
+ * is the reference's (default 10 x size).
+ *
+ * tq_agg_terms_plan is the host-only part (no device): n_keys, min_value and gcd from a column's tq_column_info_t, and the
+ * validation of the request.  A column without a row plans n_keys = 0: the call then returns records of zeros with
+ * `matches` filled.  TQ_ERR_UNSUPPORTED naming n_keys: more than TQ_AGG_MAX_BUCKETS keys (the count rows are dense, sized
+ * like the histogram's; the reference's hash-map path for high-cardinality columns is not served).  TQ_ERR_INVALID:
+ * segment_size == 0 or > TQ_AGG_TERMS_MAX_SIZE (tq_agg_terms_max_size), an order above TQ_TERMS_KEY_DESC.
+ *
+ * tq_agg_terms_batch: host outputs, blocking.  Of row q entries [0, n_returned) hold the result; the host variant writes
+ * entries [n_returned, min(segment_size, n_keys)) as zeros and nothing past them.  Refused before any launch, the segment
+ * stays usable: what the plan refuses, a column that is not live, out_stride < min(segment_size, n_keys), null outputs
+ * (TQ_ERR_INVALID).  Query shapes, options ("agg_slices", "agg_lds_buckets", "docset_trees", "docset_temp_lists"), the
+ * sloppy-phrase verdict and the message texts are tq_agg_batch's under this function's name.
+ * Launches: after the doc-set path's scatter / tree / sloppy-phrase launches, one that initialises the records and the
+ * per-query count rows — n_queries x n_keys x 4 bytes of segment scratch, never an output —, one agg_terms_count_kernel
+ * launch per sub-batch (tq_agg_terms.hip: agg_kernel's walk; counts in a workgroup-private LDS table when n_keys <=
+ * min("agg_lds_buckets", tq_agg_terms_lds_capacities' large capacity), else vector atomics on the scratch row) and ONE
+ * agg_terms_select_kernel launch behind the last sub-batch (a workgroup per query: radix select of the cut, compaction, a
+ * sort in LDS).  Integer arithmetic only: deterministic.
+ * Afterwards tq_last_batch_match_counts gives `matches`, kernel_mask = TQ_KERNEL_AGG_TERMS (| TQ_KERNEL_DOCSET_TREE |
+ * TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = lists x bitmap words x 4 (a tree: (lists + 2) x bitmap words x 4)
+ *                     + 8 per matching doc with a value
+ *                     + 8 per matching doc of a TQ_CARD_OPTIONAL column (its presence word)
+ *                     + (40 + 4 x n_keys) per query + 12 per entry returned.
+ * Not served: sub-aggregations under terms and ordering by one, `missing`, `include` / `exclude`, multivalued columns,
+ * more than TQ_AGG_MAX_BUCKETS keys. */
+#define TQ_AGG_TERMS_MAX_SIZE 1024u
+enum tq_terms_order { TQ_TERMS_COUNT_DESC = 0, TQ_TERMS_COUNT_ASC = 1, TQ_TERMS_KEY_ASC = 2, TQ_TERMS_KEY_DESC = 3 };
+typedef struct tq_agg_terms_request {
+  uint32_t column;       /* handle of tq_column_upload */
+  uint32_t order;        /* tq_terms_order */
+  uint32_t segment_size; /* 1 .. TQ_AGG_TERMS_MAX_SIZE */
+} tq_agg_terms_request; /* 12 bytes */
+typedef struct tq_agg_terms_plan_t {
+  uint64_t min_value, gcd; /* key = min_value + gcd * index */
+  uint32_t n_keys;         /* 0: the column has no row */
+  uint32_t reserved;
+} tq_agg_terms_plan_t; /* 24 bytes */
+typedef struct tq_agg_terms_t {
+  uint64_t matches, count;
+  uint64_t sum_other_doc_count;
+  uint32_t distinct, n_returned;
+  uint32_t doc_count_error_upper_bound, out_of_range;
+} tq_agg_terms_t; /* 40 bytes */
+int tq_agg_terms_plan(const tq_column_info_t *info, const tq_agg_terms_request *req, tq_agg_terms_plan_t *out);
+int tq_agg_terms_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_request *req,
+                       tq_agg_terms_t *out_terms, uint64_t *out_keys, uint32_t *out_counts, uint32_t out_stride);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream), no host synchronisation.  Entries at or
+ * past n_returned of a row are NOT touched.  The call itself zeroes what it accumulates into: the same buffers may be used
+ * again. */
+int tq_agg_terms_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_request *req,
+                              tq_agg_terms_t *d_out_terms, uint64_t *d_out_keys, uint32_t *d_out_counts, uint32_t out_stride,
+                              void *hip_stream);
+/* The LDS tables' capacities in keys of the two instantiations of agg_terms_count_kernel: out[0] the small one, out[1] the
+ * large one; more than min("agg_lds_buckets", out[1]) keys are counted in global memory. */
+void tq_agg_terms_lds_capacities(uint32_t out[2]);
+uint32_t tq_agg_terms_max_size(void); /* TQ_AGG_TERMS_MAX_SIZE */
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -1045,6 +1133,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_SORT 0x80000u        /* sort_select_kernel / sort_merge_kernel (tq_search_sorted_batch*: top k by a fast-field column) */
 #define TQ_KERNEL_AGG 0x100000u        /* agg_kernel (tq_agg_batch*: stats and histogram of a fast-field column) */
 #define TQ_KERNEL_AGG_SUB 0x200000u    /* agg_sub_kernel (tq_agg_sub_batch*: the histogram with a metric column's stats per bucket) */
+#define TQ_KERNEL_AGG_TERMS 0x400000u  /* agg_terms_count_kernel / agg_terms_select_kernel (tq_agg_terms_batch*: the top values of a column by doc count) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -1133,14 +1222,16 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        segment's bitmap words per query, one selection workgroup each; 0 = the host chooses (queries x slices fills the
  *        machine, no slice below 1024 words), 1 = every query's row is written by its one workgroup and no merge is
  *        launched, 2..256 = forced (a slice past the last word is empty).  Results do not depend on it,
- *        "agg_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_agg_batch* — slices of the segment's
+ *        "agg_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_agg_batch*, tq_agg_sub_batch*,
+ *        tq_agg_terms_batch* — slices of the segment's
  *        bitmap words per query, one aggregation workgroup each; 0 = the host chooses as for "sort_slices", 1..256 =
  *        forced (a slice past the last word is empty).  Results do not depend on it,
  *        "agg_lds_buckets" (0..8192 = the kernel's LDS capacity, default 8192; any other value: TQ_ERR_INVALID):
  *        tq_agg_batch* — the largest n_buckets a workgroup counts in a private LDS table that it flushes once (a
  *        table of 2 048 buckets, or of 8 192 at half the wavefronts per SIMD: two instantiations); above it every doc is
  *        an atomic add on the query's row, several times slower on dense queries.  tq_agg_sub_batch*: min(the option,
- *        tq_agg_sub_lds_capacities' large capacity).  Results do not depend on it,
+ *        tq_agg_sub_lds_capacities' large capacity); tq_agg_terms_batch*: min(the option, tq_agg_terms_lds_capacities'
+ *        large capacity) keys.  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

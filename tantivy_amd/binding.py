@@ -65,6 +65,7 @@ KERNEL_PHRASE_SLOP = 0x40000
 KERNEL_SORT = 0x80000
 KERNEL_AGG = 0x100000
 KERNEL_AGG_SUB = 0x200000
+KERNEL_AGG_TERMS = 0x400000
 VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
 AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
 SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
@@ -75,7 +76,8 @@ NESTED_PHRASE = 0x10  # tq_query.nested_occurs flag: the atom is a PhraseQuery (
 KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0x10: "phrase", 0x20: "phrase_sweep",
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
-                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub"}
+                0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub",
+                0x400000: "agg_terms"}
 
 
 def kernel_names(mask):
@@ -169,6 +171,8 @@ EXPORTS = [
     "tq_search_sorted_batch", "tq_search_sorted_batch_device",
     "tq_agg_histogram_plan", "tq_agg_batch", "tq_agg_batch_device",
     "tq_agg_sub_batch", "tq_agg_sub_batch_device", "tq_agg_sub_lds_capacities",
+    "tq_agg_terms_plan", "tq_agg_terms_batch", "tq_agg_terms_batch_device", "tq_agg_terms_lds_capacities",
+    "tq_agg_terms_max_size",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -327,6 +331,92 @@ def merge_bucket_stats(parts):
     return [float(pos) * interval + offset for pos in range(lo, hi)], out
 
 
+class TqAggTermsRequest(C.Structure):  # tq_agg_terms_request
+    _fields_ = [("column", C.c_uint32), ("order", C.c_uint32), ("segment_size", C.c_uint32)]
+
+
+class TqAggTermsPlan(C.Structure):  # tq_agg_terms_plan_t
+    _fields_ = [("min_value", C.c_uint64), ("gcd", C.c_uint64), ("n_keys", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# tq_agg_terms_t: one 40-byte record per query of a terms aggregation
+AGG_TERMS_DTYPE = np.dtype([("matches", np.uint64), ("count", np.uint64), ("sum_other_doc_count", np.uint64),
+                            ("distinct", np.uint32), ("n_returned", np.uint32), ("doc_count_error_upper_bound", np.uint32),
+                            ("out_of_range", np.uint32)])
+TERMS_COUNT_DESC, TERMS_COUNT_ASC, TERMS_KEY_ASC, TERMS_KEY_DESC = 0, 1, 2, 3  # tq_terms_order
+AGG_TERMS_MAX_SIZE = 1024  # TQ_AGG_TERMS_MAX_SIZE
+
+
+def agg_terms_plan(info, order=TERMS_COUNT_DESC, segment_size=10):
+    """tq_agg_terms_plan: the validation of a terms request and the key range of a column, from its info dict (column_parse /
+    DeviceIndex.column_info).  -> {"n_keys", "min_value", "gcd"}; key i of a count row is min_value + gcd * i.  Needs no
+    device."""
+    ci = TqColumnInfo(**{n: int(info[n]) for n, _ in TqColumnInfo._fields_ if n in info})
+    req = TqAggTermsRequest(column=0, order=int(order), segment_size=int(segment_size))
+    plan = TqAggTermsPlan()
+    _check(lib().tq_agg_terms_plan(C.byref(ci), C.byref(req), C.byref(plan)))
+    return _agg_terms_plan_dict(plan)
+
+
+def _agg_terms_plan_dict(plan):
+    return {"n_keys": int(plan.n_keys), "min_value": int(plan.min_value), "gcd": int(plan.gcd)}
+
+
+def agg_terms_lds_capacities():
+    """tq_agg_terms_lds_capacities: the LDS tables' capacities in keys of agg_terms_count_kernel's (small, large)
+    instantiation.  Needs no device."""
+    out = (C.c_uint32 * 2)()
+    lib().tq_agg_terms_lds_capacities(out)
+    return int(out[0]), int(out[1])
+
+
+def agg_terms_max_size():
+    """tq_agg_terms_max_size: the largest segment_size a terms request may carry.  Needs no device."""
+    return int(lib().tq_agg_terms_max_size())
+
+
+def merge_terms(per_segment_results):
+    """The segments' terms results of ONE query and ONE request as one intermediate result, as merge_fruits does for
+    IntermediateTermBucketResult (intermediate_agg_result.rs:745-759): counts add per key, sum_other_doc_count and
+    doc_count_error_upper_bound add.  An item is (keys, counts, record) — the query's rows and its AGG_TERMS_DTYPE record as
+    raw_agg_terms returns them, of which the first n_returned entries are taken — or a dict this function returned.
+    -> {"entries": {key: doc_count}, "sum_other_doc_count", "doc_count_error_upper_bound"} of Python ints.  Host only."""
+    out = {"entries": {}, "sum_other_doc_count": 0, "doc_count_error_upper_bound": 0}
+    for part in per_segment_results:
+        if isinstance(part, dict):
+            items, other, err = part["entries"].items(), part["sum_other_doc_count"], part["doc_count_error_upper_bound"]
+        else:
+            keys, counts, rec = part
+            n = int(rec["n_returned"])
+            items = zip(keys[:n], counts[:n])
+            other, err = rec["sum_other_doc_count"], rec["doc_count_error_upper_bound"]
+        for k, c in items:
+            out["entries"][int(k)] = out["entries"].get(int(k), 0) + int(c)
+        out["sum_other_doc_count"] += int(other)
+        out["doc_count_error_upper_bound"] += int(err)
+    return out
+
+
+def terms_finalize(merged, size=10, min_doc_count=1, order=TERMS_COUNT_DESC):
+    """IntermediateTermBucketResult::into_final_result (intermediate_agg_result.rs:869-961) of merge_terms' result: entries
+    below min_doc_count are dropped, the rest ordered (ties of a count order by ascending key, where the reference's unstable
+    sort leaves them unspecified), cut at `size`; what the cut removes is added to sum_other_doc_count, not to the error
+    bound.  -> {"buckets": [(key, doc_count)], "sum_other_doc_count", "doc_count_error_upper_bound"}.  Host only."""
+    entries = [(k, c) for k, c in merged["entries"].items() if c >= min_doc_count]
+    if order == TERMS_COUNT_DESC:
+        entries.sort(key=lambda e: (-e[1], e[0]))
+    elif order == TERMS_COUNT_ASC:
+        entries.sort(key=lambda e: (e[1], e[0]))
+    elif order == TERMS_KEY_ASC:
+        entries.sort(key=lambda e: e[0])
+    elif order == TERMS_KEY_DESC:
+        entries.sort(key=lambda e: -e[0])
+    else:
+        raise ValueError("order %r" % (order,))
+    return {"buckets": entries[:size], "sum_other_doc_count": merged["sum_other_doc_count"] + sum(c for _, c in entries[size:]),
+            "doc_count_error_upper_bound": merged["doc_count_error_upper_bound"]}
+
+
 def merge_histograms(parts):
     """The segments' histogram rows of ONE query and ONE request: parts = [(plan, counts)] as raw_agg returns them (plan
     dict, counts = the query's row).  The rows are aligned by base_pos and added.  -> (keys, counts): keys[i] = pos *
@@ -443,6 +533,14 @@ def lib():
                                           C.POINTER(TqAggMetricRequest), vp, vp, vp, C.c_uint32, vp]
     L.tq_agg_sub_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
     L.tq_agg_sub_lds_capacities.restype = None
+    L.tq_agg_terms_plan.argtypes = [C.POINTER(TqColumnInfo), C.POINTER(TqAggTermsRequest), C.POINTER(TqAggTermsPlan)]
+    L.tq_agg_terms_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsRequest), vp, vp, u32p, C.c_uint32]
+    L.tq_agg_terms_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsRequest), vp, vp, vp,
+                                            C.c_uint32, vp]
+    L.tq_agg_terms_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
+    L.tq_agg_terms_lds_capacities.restype = None
+    L.tq_agg_terms_max_size.argtypes = []
+    L.tq_agg_terms_max_size.restype = C.c_uint32
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
                                                   C.POINTER(TqhTermInfo), u8p, C.c_uint32]
     L.tqh_searcher_add_remote_stats_fields.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, u32p, u32p, C.c_uint32]
@@ -1501,6 +1599,62 @@ class DeviceIndex:
                                              d_stats.data_ptr(), d_buckets.data_ptr() if d_buckets is not None else None,
                                              d_bucket_stats.data_ptr() if d_bucket_stats is not None else None, int(stride),
                                              C.c_void_p(stream) if stream else None)
+
+    # ---- terms aggregation (tq_agg_terms.cpp, tq_agg_terms.hip)
+    def agg_terms_plan(self, column, order=TERMS_COUNT_DESC, segment_size=10, segment_ord=0):
+        """tq_agg_terms_plan of a resident column: {"n_keys", "min_value", "gcd"}."""
+        return agg_terms_plan(self.column_info(column, segment_ord), order, segment_size)
+
+    def raw_agg_terms(self, queries, column, order=TERMS_COUNT_DESC, segment_size=10, segment_ord=0, device=False, stride=None):
+        """Direct tq_agg_terms_batch on one segment: the query tuples of raw_docset.  -> (terms: structured array [n] of
+        AGG_TERMS_DTYPE, keys [n, width] uint64, counts [n, width] uint32, plan dict of agg_terms_plan), width =
+        min(segment_size, n_keys); of row q the first terms[q]["n_returned"] entries are the result, in the request's order.
+        stride: the rows' stride in the call (default width); device=True: through tq_agg_terms_batch_device into torch
+        tensors on the segment's GPU (entries past n_returned keep the fill)."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = TqAggTermsRequest(column=int(column), order=int(order), segment_size=int(segment_size))
+        plan = TqAggTermsPlan()
+        info = TqColumnInfo()  # (the call makes the same plan; a refusal comes from the call, under its name)
+        if lib().tq_column_info(self.segment_raw(segment_ord), int(column), C.byref(info)) == 0:
+            lib().tq_agg_terms_plan(C.byref(info), C.byref(req), C.byref(plan))
+        width = min(int(segment_size), int(plan.n_keys))
+        stride = width if stride is None else int(stride)
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_terms = torch.full((max(1, n), 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_keys = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_counts = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_terms_batch_device(self.segment_raw(segment_ord), qs, n, C.byref(req), d_terms.data_ptr(),
+                                                   d_keys.data_ptr(), d_counts.data_ptr(), stride, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            terms = d_terms.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_TERMS_DTYPE)
+            keys = d_keys.cpu().numpy().view(np.uint64)
+            counts = d_counts.cpu().numpy().view(np.uint32)
+        else:
+            terms = np.zeros(max(1, n), AGG_TERMS_DTYPE)
+            keys = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint64)
+            counts = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint32)
+            _check(lib().tq_agg_terms_batch(self.segment_raw(segment_ord), qs, n, C.byref(req), terms.ctypes.data, keys.ctypes.data,
+                                            _u32(counts), stride))
+        return terms[:n], keys[:n, :width], counts[:n, :width], _agg_terms_plan_dict(plan)
+
+    def raw_agg_terms_device(self, queries, column, order, segment_size, stride, d_terms, d_keys, d_counts, segment_ord=0,
+                             stream=None):
+        """Direct tq_agg_terms_batch_device: d_terms (int64 / uint64, 5 words per query), d_keys (int64 / uint64) and d_counts
+        (int32 / uint32), len(queries) * stride entries each (or None), are torch tensors on the segment's GPU; only
+        enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = TqAggTermsRequest(column=int(column), order=int(order), segment_size=int(segment_size))
+        return lib().tq_agg_terms_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req),
+                                               d_terms.data_ptr() if d_terms is not None else None,
+                                               d_keys.data_ptr() if d_keys is not None else None,
+                                               d_counts.data_ptr() if d_counts is not None else None, int(stride),
+                                               C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

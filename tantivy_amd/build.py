@@ -33,6 +33,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_agg.hip"),
     os.path.join(HERE, "csrc", "tq_agg_sub.hip"),
     os.path.join(HERE, "csrc", "tq_agg.cpp"),
+    os.path.join(HERE, "csrc", "tq_agg_terms.hip"),
+    os.path.join(HERE, "csrc", "tq_agg_terms.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -98,7 +100,9 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "phrase_slop_kernel": "tq_phrase_slop.hip", "phrase_slop_bits_kernel": "tq_phrase_slop.hip",
                 "sort_select_kernel": "tq_sort.hip", "sort_merge_kernel": "tq_sort.hip",
                 "agg_kernel": "tq_agg.hip", "agg_init_kernel": "tq_agg.hip",
-                "agg_sub_kernel": "tq_agg_sub.hip", "agg_sub_init_kernel": "tq_agg_sub.hip"}
+                "agg_sub_kernel": "tq_agg_sub.hip", "agg_sub_init_kernel": "tq_agg_sub.hip",
+                "agg_terms_count_kernel": "tq_agg_terms.hip", "agg_terms_select_kernel": "tq_agg_terms.hip",
+                "agg_terms_init_kernel": "tq_agg_terms.hip"}
 
 
 def kernel_hash(kernel_names, read=None):

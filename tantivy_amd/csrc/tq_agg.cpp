@@ -182,6 +182,7 @@ int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_s
   spec.n_slices = pick_slices(s, s->opt.agg_slices, tqk_agg_step_words(), max_sub_n, n_words);
   spec.words_per_slice = (n_words + spec.n_slices - 1u) / spec.n_slices;
   spec.optional = s->columns[spec.column].dev.present != nullptr;
+  if (spec.terms) return agg_terms_prepare(s, spec, n_queries, st);
   s->stats.algorithmic_bytes += (uint64_t)n_queries * (sizeof(tq_agg_stats_t) + 4u * (uint64_t)spec.plan.n_buckets);
   HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, (spec.metric ? 5u : 3u) * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(s->d_qmatches.p, 0, (size_t)n_queries * sizeof(uint32_t), st));
@@ -195,6 +196,7 @@ int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_s
 
 // the aggregation in place of the count / scan / write passes: records and rows under the caller's query index
 int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st) {
+  if (spec.terms) return agg_terms_launch(s, spec, p, q0, st);
   const tq_segment::ColumnHost &col = s->columns[spec.column];
   TqkAggParams ap{};
   ap.ds = p;
@@ -230,6 +232,10 @@ int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uin
   sp.bucket_stats = (TqkAggBucketStats *)spec.d_bucket_stats + (size_t)q0 * spec.bucket_stride;
   sp.value_type_b = spec.metric->value_type;
   return launched(tqk_launch_agg_sub(sp, st), "sub-aggregation kernel");
+}
+
+int agg_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st) {
+  return spec.terms ? agg_terms_finish(s, spec, n_queries, st) : TQ_OK;
 }
 
 }  // namespace tqi

@@ -116,7 +116,8 @@ static int segment_upload_common(tq_ctx *ctx, int device, uint32_t max_doc, cons
       if (e == hipSuccess) e = hipEventCreate(&s->ev_k1[i]);
     }
     // (word 0: the batch's matches; words 1 and 2: a sorted batch's valued matches and row entries, tq_sort.hip; words 3
-    // and 4: a sub-aggregation's bucketed docs with a metric value and bucketed docs, tq_agg_sub.hip)
+    // and 4: a sub-aggregation's bucketed docs with a metric value and bucketed docs, tq_agg_sub.hip; word 3 of a terms
+    // aggregation: the entries returned, tq_agg_terms.hip)
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 5u * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_tp_info, 2 * sizeof(TqpInfo));
     if (e != hipSuccess) rc = fail(TQ_ERR_HIP, "segment setup: %s", hipGetErrorString(e));
@@ -300,6 +301,7 @@ void tq_segment_free(tq_segment *s) {
   s->d_sort_rows.release();
   s->h_sort_ks.release();
   s->d_agg_rows.release();
+  s->d_agg_term_rows.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();
@@ -474,6 +476,11 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
         unsigned long long b[2] = {0, 0};
         HIP_TRY(hipMemcpy(b, s->d_match_counter + 3, sizeof b, hipMemcpyDeviceToHost));
         s->stats.algorithmic_bytes += 8u * b[0] + (s->stats_agg_metric_optional ? 8u * b[1] : 0u);
+      }
+      if (s->stats_agg_terms) {  // 12 per entry returned (key, doc count)
+        unsigned long long e = 0;
+        HIP_TRY(hipMemcpy(&e, s->d_match_counter + 3, sizeof e, hipMemcpyDeviceToHost));
+        s->stats.algorithmic_bytes += 12u * e;
       }
       s->stats_sorted = false;
     } else {

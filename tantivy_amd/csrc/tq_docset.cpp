@@ -13,7 +13,7 @@
 // docset_batch runs one DocsetCall as stages around one Batch record: check_and_express, plan_trees, cut_docset_subs,
 // size_and_upload, then per sub-batch launch_match_bits and launch_consumer, driven by run_device / run_host.  The consumer
 // of a sub-batch's match words is one of four: rows, the count pass alone (tq_count_batch), or the launches tq_sort.cpp
-// (tq_search_sorted_batch*) / tq_agg.cpp (tq_agg_batch*, tq_agg_sub_batch*) put in place of the count / scan / write passes.
+// (tq_search_sorted_batch*) / tq_agg.cpp (tq_agg_batch*, tq_agg_sub_batch*, tq_agg_terms_batch*) put in place of the count / scan / write passes.
 #include "tq_internal.hpp"
 
 #include <deque>
@@ -608,7 +608,8 @@ int run_device(const Batch &b) {
   tq_segment *const s = b.s;
   const DocsetCall &call = b.call;
   if (b.timed) HIP_TRY(hipEventRecord(s->ev_k0[b.ring], b.st));
-  const int rc = sweep(b, DS_SCATTER | DS_COUNT | DS_WRITE, call.out_docs, call.out_scores, call.out_cap);
+  int rc = sweep(b, DS_SCATTER | DS_COUNT | DS_WRITE, call.out_docs, call.out_scores, call.out_cap);
+  if (rc == TQ_OK && call.consumer == Consumer::kAgg) rc = agg_finish(s, *call.agg, b.n_queries, b.st);
   if (rc != TQ_OK) return rc;
   if (b.timed) {
     HIP_TRY(hipEventRecord(s->ev_k1[b.ring], b.st));
@@ -621,6 +622,7 @@ int run_device(const Batch &b) {
   s->stats_sorted_optional = (call.sort && call.sort->optional) || (call.agg && call.agg->optional);
   s->stats_agg_metric = call.agg && call.agg->metric;
   s->stats_agg_metric_optional = call.agg && call.agg->metric_optional;
+  s->stats_agg_terms = call.agg && call.agg->terms;
   HIP_TRY(hipEventRecord(s->ev_batch_done, b.st));
   s->last_stream = b.st;
   s->batch_in_flight = true;
@@ -691,7 +693,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, con
   if (rc != TQ_OK) return rc;
   const bool scored = call.scored;
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = (call.consumer == Consumer::kSort ? TQ_KERNEL_SORT : call.consumer == Consumer::kAgg ? (call.agg->metric ? TQ_KERNEL_AGG_SUB : TQ_KERNEL_AGG) : TQ_KERNEL_DOCSET) |
+  s->stats.kernel_mask = (call.consumer == Consumer::kSort ? TQ_KERNEL_SORT : call.consumer == Consumer::kAgg ? (call.agg->terms ? TQ_KERNEL_AGG_TERMS : call.agg->metric ? TQ_KERNEL_AGG_SUB : TQ_KERNEL_AGG) : TQ_KERNEL_DOCSET) |
                          (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (b.tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
                          (scored && !b.tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u) | (b.slop_qs.empty() ? 0u : TQ_KERNEL_PHRASE_SLOP);
   s->stats.algorithmic_bytes = b.algo_bytes;

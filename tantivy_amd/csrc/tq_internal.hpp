@@ -362,11 +362,12 @@ struct tq_segment {
   DevBuf d_sort_ks, d_sort_partials, d_sort_slice_counts, d_sort_rows;
   PinnedBuf h_sort_ks;  // ... the queries' k on their way up
   DevBuf d_agg_rows;  // aggregations (tq_agg.hip): the host variant's records and bucket rows
+  DevBuf d_agg_term_rows;  // terms aggregation (tq_agg_terms.hip): the batch's count rows, n_queries x n_keys
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
            d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap +
-           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap + d_agg_rows.cap;
+           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap + d_agg_rows.cap + d_agg_term_rows.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -463,6 +464,8 @@ struct tq_segment {
   // ... a sub-aggregation (tq_agg_sub_batch*): d_match_counter[3..4] = bucketed docs with a value in the metric column,
   // bucketed docs (8 per valued one, 8 per bucketed doc of an Optional metric column); set beside stats_sorted
   bool stats_agg_metric = false, stats_agg_metric_optional = false;
+  // ... a terms aggregation (tq_agg_terms_batch*): d_match_counter[3] = entries returned (12 bytes each); the same
+  bool stats_agg_terms = false;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -1076,6 +1079,14 @@ struct AggSpec {
   const tq_agg_metric_request *metric = nullptr;
   tq_agg_bucket_stats_t *d_bucket_stats = nullptr;
   bool metric_optional = false;  // agg_prepare
+  // tq_agg_terms_batch* (tq_agg_terms.cpp): in place of stats and histogram, the terms request (null: none) with its plan;
+  // the record of query q at d_terms + q, its output rows at q * terms_stride; the count rows are the segment's scratch
+  const tq_agg_terms_request *terms = nullptr;
+  tq_agg_terms_plan_t terms_plan{};
+  tq_agg_terms_t *d_terms = nullptr;
+  uint64_t *d_term_keys = nullptr;
+  uint32_t *d_term_counts = nullptr;
+  uint32_t terms_stride = 0;
 };
 // One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
 // kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass
@@ -1134,6 +1145,12 @@ int sort_prepare(tq_segment *s, SortSpec &spec, const tq_query *queries, uint32_
 int sort_launch(tq_segment *s, const SortSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
 int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_sub_n, uint32_t n_words, hipStream_t st);
 int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
+// behind the last sub-batch's agg_launch, once: a terms aggregation's selection (anything else: nothing)
+int agg_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
+// tq_agg_terms.cpp: what the three do for a spec with `terms`
+int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
+int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
+int agg_terms_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
 // Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the

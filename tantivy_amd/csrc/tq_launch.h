@@ -508,6 +508,42 @@ hipError_t tqk_launch_agg_sub_init(TqkAggBucketStats *bucket_stats, uint32_t n_q
 hipError_t tqk_launch_agg_sub(const TqkAggSubParams &p, hipStream_t st);
 // the LDS tables' compile-time capacities in buckets: out[0] the small instantiation's, out[1] the large one's
 void tqk_agg_sub_lds_capacities(uint32_t out[2]);
+// ---- terms aggregation (tq_agg_terms.hip): doc counts per key of a column over a doc set, then the top segment_size
+// entries per query (tq_agg_terms_batch*).  tqk_launch_agg_terms_init in front; one count launch per sub-batch adds to the
+// records and to the per-query scratch rows with vector atomics; one select launch behind the last of them writes the output
+// rows and the rest of the records.
+struct TqkAggTerms {  // = tq_agg_terms_t, 40 bytes
+  unsigned long long matches, count, sum_other_doc_count;
+  uint32_t distinct, n_returned, doc_count_error_upper_bound, out_of_range;
+};
+struct TqkAggTermsParams {
+  TqkDocsetParams ds;          // queries (one sub-batch), alive, n_queries, n_words, max_doc: what docset_word reads
+  TqkColumn col;               // the aggregated column
+  uint64_t min_value, gcd;     // key index = (value - min) / gcd: the packed value (Linear: computed)
+  TqkAggTerms *records;        // records of the sub-batch's first query on: [n_queries]
+  uint32_t *rows;              // scratch rows of the sub-batch's first query on: [n_queries][n_keys]
+  uint32_t *query_sizes;       // [n_queries] += alive matches per query (zeroed by the caller)
+  unsigned long long *totals;  // [5] += matches, matches with a value, -, entries returned (the select launch), - (zeroed by the caller)
+  uint32_t n_keys;             // entries of a scratch row, <= TQ_AGG_MAX_BUCKETS
+  uint32_t lds_buckets;        // n_keys <= this: a workgroup-private table in LDS, flushed at the end; above: the row
+  uint32_t n_slices, words_per_slice;
+};
+struct TqkAggTermsSelectParams {
+  TqkAggTerms *records;        // [n_queries] of the whole batch
+  const uint32_t *rows;        // [n_queries][n_keys]
+  uint64_t *out_keys;          // [n_queries][out_stride]: entries [0, n_returned) of a row are written
+  uint32_t *out_counts;        // the same
+  unsigned long long *totals;  // [3] += n_returned
+  uint64_t min_value, gcd;     // key = min + gcd * index
+  uint32_t n_queries, n_keys, out_stride;
+  uint32_t segment_size;       // 1 .. tqk_agg_terms_max_size()
+  uint32_t order;              // TQ_TERMS_ORDER_*
+};
+hipError_t tqk_launch_agg_terms_init(TqkAggTerms *records, uint32_t *rows, uint32_t n_queries, uint32_t n_keys, hipStream_t st);
+hipError_t tqk_launch_agg_terms_count(const TqkAggTermsParams &p, hipStream_t st);
+hipError_t tqk_launch_agg_terms_select(const TqkAggTermsSelectParams &p, hipStream_t st);
+void tqk_agg_terms_lds_capacities(uint32_t out[2]);  // the count kernel's two LDS tables, in keys: small, large
+uint32_t tqk_agg_terms_max_size();                   // the largest segment_size
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
