@@ -1059,7 +1059,7 @@ void tq_agg_sub_lds_capacities(uint32_t out[2]);
  *                     + 8 per matching doc with a value
  *                     + 8 per matching doc of a TQ_CARD_OPTIONAL column (its presence word)
  *                     + (40 + 4 x n_keys) per query + 12 per entry returned.
- * Not served: sub-aggregations under terms and ordering by one, `missing`, `include` / `exclude`, multivalued columns,
+ * Not served here: a sub-aggregation under terms and ordering by it (tq_agg_terms_sub_batch below), `missing`, `include` / `exclude`, multivalued columns,
  * more than TQ_AGG_MAX_BUCKETS keys. */
 #define TQ_AGG_TERMS_MAX_SIZE 1024u
 enum tq_terms_order { TQ_TERMS_COUNT_DESC = 0, TQ_TERMS_COUNT_ASC = 1, TQ_TERMS_KEY_ASC = 2, TQ_TERMS_KEY_DESC = 3 };
@@ -1092,6 +1092,84 @@ int tq_agg_terms_batch_device(tq_segment *seg, const tq_query *queries, uint32_t
  * large one; more than min("agg_lds_buckets", out[1]) keys are counted in global memory. */
 void tq_agg_terms_lds_capacities(uint32_t out[2]);
 uint32_t tq_agg_terms_max_size(void); /* TQ_AGG_TERMS_MAX_SIZE */
+
+/* ---- terms aggregation with a metric: stats of a second column per key, and order by it ----
+ * replaces a `terms` aggregation with ONE stats / avg / min / max / sum / value_count sub-aggregation, optionally ordered
+ * by it ("top 10 service by avg latency among +body:error +timestamp:[a TO b]", `"order": {"lat.avg": "desc"}`;
+ * src/aggregation/bucket/term_agg/mod.rs:836-899 collect with a sub-aggregation, :1040-1111 the order by a
+ * sub-aggregation and cut_off_buckets; src/aggregation/metric/stats.rs:282-306, :325-357 compute_metric_value).
+ *
+ * Per query, over its alive matching docs that have a value in the key column A — exactly what tq_agg_terms_batch runs
+ * over, with its plan (tq_agg_terms_plan) and its exact integer key index: each key gets a doc count and a
+ * tq_agg_bucket_stats_t over the docs counted under it: `count` the number of those docs that have a value in the metric
+ * column B (which may be A), min_value / max_value in B's u64 space (UINT64_MAX / 0 when count == 0), the exact 128-bit
+ * sum (TQ_VALUE_F64: both sum words 0, as for tq_agg_sub_batch).  The entries are the keys with a doc count > 0; the first
+ * min(segment_size, distinct) are written in req->order as (out_keys, out_counts, out_entry_stats)[q * out_stride + j].
+ * The tq_agg_terms_t record means what it means for tq_agg_terms_batch: the error bound is the doc count of entry number
+ * segment_size in the order used, sum_other_doc_count the doc counts from that entry on — cut_off_buckets, which the
+ * reference also applies under a sub-aggregation order.
+ *
+ * Orders: the four of tq_agg_terms_batch — record, keys and counts are then that call's, bit for bit — and
+ *   TQ_TERMS_METRIC_DESC  the largest order value first, ties by ascending key
+ *   TQ_TERMS_METRIC_ASC   the smallest order value first, ties by ascending key
+ * (the reference's select_nth_unstable_by(partial_cmp) leaves ties unspecified).  The ORDER VALUE of an entry is a
+ * fixed-width unsigned integer image of req->order_metric of its record, monotone in the typed value, the one
+ * tq_agg_terms_metric_image returns (the same code the kernel runs):
+ *   TQ_METRIC_VALUE_COUNT  the record's count
+ *   TQ_METRIC_MIN / _MAX   the u64-space value (tantivy's mapping is monotone for U64 / I64 / F64)
+ *   TQ_METRIC_SUM          the exact typed sum as a biased 96-bit integer: U64 the sum; I64 sum - count x 2^63 + 2^95
+ *   TQ_METRIC_AVG          the monotone u64 image (f64_to_u64) of the f64 that is the CORRECTLY ROUNDED (half to even)
+ *                          quotient of the exact typed sum by count — integer long division, not f64 arithmetic on a
+ *                          rounded sum
+ * An entry whose record has count == 0 orders as typed 0 under MIN / MAX / AVG (compute_metric_value(..).unwrap_or(0.0)).
+ * The exact order refines the reference's f64 order: it can only separate what f64 ties.
+ *
+ * Refused before any launch, the segment stays usable, the message carries the called function's name: everything
+ * tq_agg_terms_batch refuses; TQ_ERR_INVALID: an order above TQ_TERMS_METRIC_ASC, an order_metric above TQ_METRIC_AVG
+ * under a metric order, non-zero reserved, a metric column that is not live, a metric_value_type above TQ_VALUE_F64, a null
+ * out_entry_stats when min(segment_size, n_keys) > 0; TQ_ERR_UNSUPPORTED naming the pair: a SUM or AVG order over a
+ * TQ_VALUE_F64 metric (F64 sums are not served).  Query shapes, options, the sloppy-phrase verdict and the message texts
+ * are tq_agg_batch's under this function's name.
+ * Launches: after the doc-set path's launches one that initialises the records and the scratch — per query a count row and a
+ * record row, n_keys x 44 bytes of segment scratch, never an output —, one agg_terms_sub_count_kernel launch per sub-batch
+ * (tq_agg_terms_sub.hip; a workgroup-private LDS table when n_keys <= min("agg_lds_buckets",
+ * tq_agg_terms_sub_lds_capacities' large capacity), else vector atomics on the scratch rows) and ONE
+ * agg_terms_sub_select_kernel launch behind the last sub-batch.  Integer arithmetic only: deterministic.
+ * Afterwards kernel_mask = TQ_KERNEL_AGG_TERMS_SUB (| TQ_KERNEL_DOCSET_TREE | TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = tq_agg_terms_batch's
+ *                     + 8 per counted doc with a value in B
+ *                     + 8 per counted doc of a TQ_CARD_OPTIONAL B (its presence word)
+ *                     + 40 x n_keys per query + 40 per entry returned.
+ * Not served: more than one metric column, nested bucket aggregations, `missing`, `include` / `exclude`, F64 sums,
+ * multivalued columns, more than TQ_AGG_MAX_BUCKETS keys. */
+/* two more values of tq_terms_order, for tq_agg_terms_sub_batch* alone (tq_agg_terms_plan / tq_agg_terms_batch* refuse them) */
+#define TQ_TERMS_METRIC_DESC 4u
+#define TQ_TERMS_METRIC_ASC 5u
+enum tq_terms_metric { TQ_METRIC_VALUE_COUNT = 0, TQ_METRIC_MIN = 1, TQ_METRIC_MAX = 2, TQ_METRIC_SUM = 3, TQ_METRIC_AVG = 4 };
+typedef struct tq_agg_terms_sub_request {
+  uint32_t column;            /* key column A */
+  uint32_t order;             /* tq_terms_order, 0..5 */
+  uint32_t segment_size;      /* 1 .. TQ_AGG_TERMS_MAX_SIZE */
+  uint32_t metric_column;     /* metric column B (may be A) */
+  uint8_t metric_value_type;  /* tq_value_type of B */
+  uint8_t order_metric;       /* tq_terms_metric; read only under the two METRIC orders */
+  uint8_t reserved[2];        /* zero */
+} tq_agg_terms_sub_request; /* 20 bytes */
+int tq_agg_terms_sub_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_sub_request *req,
+                           tq_agg_terms_t *out_terms, uint64_t *out_keys, uint32_t *out_counts,
+                           tq_agg_bucket_stats_t *out_entry_stats, uint32_t out_stride);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream), no host synchronisation.  Entries at or
+ * past n_returned of a row are NOT touched. */
+int tq_agg_terms_sub_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_sub_request *req,
+                                  tq_agg_terms_t *d_out_terms, uint64_t *d_out_keys, uint32_t *d_out_counts,
+                                  tq_agg_bucket_stats_t *d_out_entry_stats, uint32_t out_stride, void *hip_stream);
+/* The LDS tables' capacities in keys of the two instantiations of agg_terms_sub_count_kernel: out[0] the small one, out[1]
+ * the large one; more than min("agg_lds_buckets", out[1]) keys are accumulated in global memory. */
+void tq_agg_terms_sub_lds_capacities(uint32_t out[2]);
+/* The order value of one record (host only, no device): out[0] the low 64 bits, out[1] the high ones (non-zero for
+ * TQ_METRIC_SUM alone).  TQ_ERR_INVALID: a null argument, a value_type above TQ_VALUE_F64, a metric above TQ_METRIC_AVG, a
+ * count of 2^32 or more or a sum of 2^96 or more; TQ_ERR_UNSUPPORTED: SUM or AVG of TQ_VALUE_F64. */
+int tq_agg_terms_metric_image(const tq_agg_bucket_stats_t *rec, uint32_t value_type, uint32_t metric, uint64_t out[2]);
 
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
@@ -1134,6 +1212,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_AGG 0x100000u        /* agg_kernel (tq_agg_batch*: stats and histogram of a fast-field column) */
 #define TQ_KERNEL_AGG_SUB 0x200000u    /* agg_sub_kernel (tq_agg_sub_batch*: the histogram with a metric column's stats per bucket) */
 #define TQ_KERNEL_AGG_TERMS 0x400000u  /* agg_terms_count_kernel / agg_terms_select_kernel (tq_agg_terms_batch*: the top values of a column by doc count) */
+#define TQ_KERNEL_AGG_TERMS_SUB 0x800000u /* agg_terms_sub_count_kernel / agg_terms_sub_select_kernel (tq_agg_terms_sub_batch*: a metric column's stats per key, order by it) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -1223,7 +1302,7 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        machine, no slice below 1024 words), 1 = every query's row is written by its one workgroup and no merge is
  *        launched, 2..256 = forced (a slice past the last word is empty).  Results do not depend on it,
  *        "agg_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_agg_batch*, tq_agg_sub_batch*,
- *        tq_agg_terms_batch* — slices of the segment's
+ *        tq_agg_terms_batch*, tq_agg_terms_sub_batch* — slices of the segment's
  *        bitmap words per query, one aggregation workgroup each; 0 = the host chooses as for "sort_slices", 1..256 =
  *        forced (a slice past the last word is empty).  Results do not depend on it,
  *        "agg_lds_buckets" (0..8192 = the kernel's LDS capacity, default 8192; any other value: TQ_ERR_INVALID):
@@ -1231,7 +1310,8 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        table of 2 048 buckets, or of 8 192 at half the wavefronts per SIMD: two instantiations); above it every doc is
  *        an atomic add on the query's row, several times slower on dense queries.  tq_agg_sub_batch*: min(the option,
  *        tq_agg_sub_lds_capacities' large capacity); tq_agg_terms_batch*: min(the option, tq_agg_terms_lds_capacities'
- *        large capacity) keys.  Results do not depend on it,
+ *        large capacity) keys; tq_agg_terms_sub_batch*: min(the option, tq_agg_terms_sub_lds_capacities' large capacity)
+ *        keys.  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

@@ -66,6 +66,7 @@ KERNEL_SORT = 0x80000
 KERNEL_AGG = 0x100000
 KERNEL_AGG_SUB = 0x200000
 KERNEL_AGG_TERMS = 0x400000
+KERNEL_AGG_TERMS_SUB = 0x800000
 VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
 AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
 SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
@@ -77,7 +78,7 @@ KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
                 0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub",
-                0x400000: "agg_terms"}
+                0x400000: "agg_terms", 0x800000: "agg_terms_sub"}
 
 
 def kernel_names(mask):
@@ -173,6 +174,7 @@ EXPORTS = [
     "tq_agg_sub_batch", "tq_agg_sub_batch_device", "tq_agg_sub_lds_capacities",
     "tq_agg_terms_plan", "tq_agg_terms_batch", "tq_agg_terms_batch_device", "tq_agg_terms_lds_capacities",
     "tq_agg_terms_max_size",
+    "tq_agg_terms_sub_batch", "tq_agg_terms_sub_batch_device", "tq_agg_terms_sub_lds_capacities", "tq_agg_terms_metric_image",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -417,6 +419,111 @@ def terms_finalize(merged, size=10, min_doc_count=1, order=TERMS_COUNT_DESC):
             "doc_count_error_upper_bound": merged["doc_count_error_upper_bound"]}
 
 
+class TqAggTermsSubRequest(C.Structure):  # tq_agg_terms_sub_request
+    _fields_ = [("column", C.c_uint32), ("order", C.c_uint32), ("segment_size", C.c_uint32), ("metric_column", C.c_uint32),
+                ("metric_value_type", C.c_uint8), ("order_metric", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+TERMS_METRIC_DESC, TERMS_METRIC_ASC = 4, 5  # tq_terms_order, tq_agg_terms_sub_batch* alone
+METRIC_VALUE_COUNT, METRIC_MIN, METRIC_MAX, METRIC_SUM, METRIC_AVG = 0, 1, 2, 3, 4  # tq_terms_metric
+
+
+def agg_terms_sub_lds_capacities():
+    """tq_agg_terms_sub_lds_capacities: the LDS tables' capacities in keys of agg_terms_sub_count_kernel's (small, large)
+    instantiation.  Needs no device."""
+    out = (C.c_uint32 * 2)()
+    lib().tq_agg_terms_sub_lds_capacities(out)
+    return int(out[0]), int(out[1])
+
+
+def agg_terms_metric_image(record, value_type, metric):
+    """tq_agg_terms_metric_image: the order value of one bucket record (a row of AGG_BUCKET_STATS_DTYPE, or a dict with
+    "count", "min_value", "max_value", "sum_lo", "sum_hi") under a metric order, a Python int of up to 96 bits — the code the
+    selection kernel runs, on the host.  Needs no device."""
+    rec = np.zeros(1, AGG_BUCKET_STATS_DTYPE)
+    for n in AGG_BUCKET_STATS_DTYPE.names:
+        rec[n][0] = int(record[n])
+    out = (C.c_uint64 * 2)()
+    _check(lib().tq_agg_terms_metric_image(rec.ctypes.data, int(value_type), int(metric), out))
+    return int(out[0]) | (int(out[1]) << 64)
+
+
+def _record_dict(r):
+    """A bucket record (structured row or dict) as a dict of Python ints with the 128-bit "sum"."""
+    if "sum" in (r.keys() if isinstance(r, dict) else ()):
+        total = int(r["sum"])
+    else:
+        total = int(r["sum_lo"]) + (int(r["sum_hi"]) << 64)
+    return {"count": int(r["count"]), "min_value": int(r["min_value"]), "max_value": int(r["max_value"]), "sum": total,
+            "sum_lo": total & ((1 << 64) - 1), "sum_hi": total >> 64}
+
+
+def merge_terms_sub(per_segment_results):
+    """merge_terms with a record per key: an item is (keys, counts, records, terms record) — the query's rows as
+    raw_agg_terms_sub returns them, of which the first n_returned entries are taken — or a dict this function returned.
+    Counts add per key as in merge_terms; the records add per key as in merge_bucket_stats (counts and 128-bit sums add, min
+    / max are the extremes).  -> {"entries": {key: (doc_count, record dict)}, "sum_other_doc_count",
+    "doc_count_error_upper_bound"}.  Host only."""
+    out = {"entries": {}, "sum_other_doc_count": 0, "doc_count_error_upper_bound": 0}
+    for part in per_segment_results:
+        if isinstance(part, dict):
+            items = [(k, c, r) for k, (c, r) in part["entries"].items()]
+            other, err = part["sum_other_doc_count"], part["doc_count_error_upper_bound"]
+        else:
+            keys, counts, records, rec = part
+            n = int(rec["n_returned"])
+            items = zip(keys[:n], counts[:n], records[:n])
+            other, err = rec["sum_other_doc_count"], rec["doc_count_error_upper_bound"]
+        for k, c, r in items:
+            r = _record_dict(r)
+            if int(k) in out["entries"]:
+                c0, r0 = out["entries"][int(k)]
+                r = _record_dict({"count": r0["count"] + r["count"], "min_value": min(r0["min_value"], r["min_value"]),
+                                  "max_value": max(r0["max_value"], r["max_value"]), "sum": r0["sum"] + r["sum"]})
+                c = c0 + int(c)
+            out["entries"][int(k)] = (int(c), r)
+        out["sum_other_doc_count"] += int(other)
+        out["doc_count_error_upper_bound"] += int(err)
+    return out
+
+
+_METRIC_FIELDS = {METRIC_VALUE_COUNT: "count", METRIC_MIN: "min", METRIC_MAX: "max", METRIC_SUM: "sum", METRIC_AVG: "avg"}
+
+
+def terms_sub_finalize(merged, value_type, size=10, min_doc_count=1, order=TERMS_COUNT_DESC, order_metric=METRIC_AVG):
+    """IntermediateTermBucketResult::into_final_result (intermediate_agg_result.rs:869-961) of merge_terms_sub's result.  The
+    four old orders as terms_finalize; under a metric order the buckets are ordered by the finalized metric
+    (agg_stats_finalize of the merged record: exact ints, avg = sum / count correctly rounded); an entry WITHOUT a metric
+    value (count == 0 under min / max / avg) sorts as f64::MIN at this stage (:918-939), not as 0; ties go by ascending key.
+    F64: sum / avg are not served.  -> {"buckets": [(key, doc_count, stats dict)], "sum_other_doc_count",
+    "doc_count_error_upper_bound"}.  Host only."""
+    entries = [(k, c, agg_stats_finalize(r, value_type)) for k, (c, r) in merged["entries"].items() if c >= min_doc_count]
+    if order in (TERMS_METRIC_DESC, TERMS_METRIC_ASC):
+        field = _METRIC_FIELDS[order_metric]
+        if value_type == VALUE_F64 and order_metric in (METRIC_SUM, METRIC_AVG):
+            raise ValueError("an order by %s of an F64 metric is not served" % field)
+        f64_min = -float(np.finfo(np.float64).max)
+
+        def val(e):
+            v = e[2][field]
+            return f64_min if v is None else v
+
+        entries.sort(key=lambda e: e[0])
+        entries.sort(key=val, reverse=order == TERMS_METRIC_DESC)  # (stable: ties keep the ascending key)
+    elif order == TERMS_COUNT_DESC:
+        entries.sort(key=lambda e: (-e[1], e[0]))
+    elif order == TERMS_COUNT_ASC:
+        entries.sort(key=lambda e: (e[1], e[0]))
+    elif order == TERMS_KEY_ASC:
+        entries.sort(key=lambda e: e[0])
+    elif order == TERMS_KEY_DESC:
+        entries.sort(key=lambda e: -e[0])
+    else:
+        raise ValueError("order %r" % (order,))
+    return {"buckets": entries[:size], "sum_other_doc_count": merged["sum_other_doc_count"] + sum(e[1] for e in entries[size:]),
+            "doc_count_error_upper_bound": merged["doc_count_error_upper_bound"]}
+
+
 def merge_histograms(parts):
     """The segments' histogram rows of ONE query and ONE request: parts = [(plan, counts)] as raw_agg returns them (plan
     dict, counts = the query's row).  The rows are aligned by base_pos and added.  -> (keys, counts): keys[i] = pos *
@@ -539,6 +646,13 @@ def lib():
                                             C.c_uint32, vp]
     L.tq_agg_terms_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
     L.tq_agg_terms_lds_capacities.restype = None
+    L.tq_agg_terms_sub_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsSubRequest), vp, vp, u32p, vp,
+                                         C.c_uint32]
+    L.tq_agg_terms_sub_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsSubRequest), vp, vp, vp, vp,
+                                                C.c_uint32, vp]
+    L.tq_agg_terms_sub_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
+    L.tq_agg_terms_sub_lds_capacities.restype = None
+    L.tq_agg_terms_metric_image.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.tq_agg_terms_max_size.argtypes = []
     L.tq_agg_terms_max_size.restype = C.c_uint32
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
@@ -1655,6 +1769,70 @@ class DeviceIndex:
                                                d_keys.data_ptr() if d_keys is not None else None,
                                                d_counts.data_ptr() if d_counts is not None else None, int(stride),
                                                C.c_void_p(stream) if stream else None)
+
+    # ---- terms aggregation with a metric (tq_agg_terms_sub.cpp, tq_agg_terms_sub.hip)
+    def raw_agg_terms_sub(self, queries, column, metric_column, metric_value_type, order=TERMS_COUNT_DESC, segment_size=10,
+                          order_metric=METRIC_AVG, segment_ord=0, device=False, stride=None, reserved=(0, 0)):
+        """Direct tq_agg_terms_sub_batch on one segment: raw_agg_terms' arguments and the metric column.  -> (terms, keys
+        [n, width] uint64, counts [n, width] uint32, records [n, width] of AGG_BUCKET_STATS_DTYPE, plan dict), width =
+        min(segment_size, n_keys); of row q the first terms[q]["n_returned"] entries are the result, in the request's order.
+        stride: the rows' stride in the call (default width; the rows come back `stride` wide when it is given);
+        device=True: through tq_agg_terms_sub_batch_device into torch tensors on the segment's GPU (entries past n_returned
+        keep the fill)."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = TqAggTermsSubRequest(column=int(column), order=int(order), segment_size=int(segment_size), metric_column=int(metric_column),
+                                   metric_value_type=int(metric_value_type), order_metric=int(order_metric))
+        req.reserved[0], req.reserved[1] = int(reserved[0]), int(reserved[1])
+        plan = TqAggTermsPlan()
+        info = TqColumnInfo()  # (the call makes the same plan; a refusal comes from the call, under its name)
+        if lib().tq_column_info(self.segment_raw(segment_ord), int(column), C.byref(info)) == 0:
+            treq = TqAggTermsRequest(column=int(column), order=min(int(order), TERMS_KEY_DESC), segment_size=int(segment_size))
+            lib().tq_agg_terms_plan(C.byref(info), C.byref(treq), C.byref(plan))
+        width = min(int(segment_size), int(plan.n_keys))
+        out_w = width if stride is None else int(stride)
+        stride = out_w
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_terms = torch.full((max(1, n), 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_keys = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_counts = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            d_recs = torch.full((max(1, n), max(1, stride) * 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_terms_sub_batch_device(self.segment_raw(segment_ord), qs, n, C.byref(req), d_terms.data_ptr(),
+                                                       d_keys.data_ptr(), d_counts.data_ptr(), d_recs.data_ptr(), stride, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            terms = d_terms.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_TERMS_DTYPE)
+            keys = d_keys.cpu().numpy().view(np.uint64)
+            counts = d_counts.cpu().numpy().view(np.uint32)
+            recs = d_recs.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_BUCKET_STATS_DTYPE).reshape(max(1, n), max(1, stride))
+        else:
+            terms = np.zeros(max(1, n), AGG_TERMS_DTYPE)
+            keys = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint64)
+            counts = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint32)
+            recs = np.full((max(1, n), max(1, stride) * 5), 0xDEADBEEF, np.uint64).reshape(-1).view(AGG_BUCKET_STATS_DTYPE)
+            recs = recs.reshape(max(1, n), max(1, stride))
+            _check(lib().tq_agg_terms_sub_batch(self.segment_raw(segment_ord), qs, n, C.byref(req), terms.ctypes.data, keys.ctypes.data,
+                                                _u32(counts), recs.ctypes.data, stride))
+        return terms[:n], keys[:n, :out_w], counts[:n, :out_w], recs[:n, :out_w], _agg_terms_plan_dict(plan)
+
+    def raw_agg_terms_sub_device(self, queries, column, metric_column, metric_value_type, order, segment_size, order_metric, stride,
+                                 d_terms, d_keys, d_counts, d_records, segment_ord=0, stream=None, reserved=(0, 0)):
+        """Direct tq_agg_terms_sub_batch_device: raw_agg_terms_device's tensors and d_records (int64 / uint64, 5 words per
+        entry, len(queries) * stride entries, or None), torch tensors on the segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = TqAggTermsSubRequest(column=int(column), order=int(order), segment_size=int(segment_size), metric_column=int(metric_column),
+                                   metric_value_type=int(metric_value_type), order_metric=int(order_metric))
+        req.reserved[0], req.reserved[1] = int(reserved[0]), int(reserved[1])
+        return lib().tq_agg_terms_sub_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req),
+                                                   d_terms.data_ptr() if d_terms is not None else None,
+                                                   d_keys.data_ptr() if d_keys is not None else None,
+                                                   d_counts.data_ptr() if d_counts is not None else None,
+                                                   d_records.data_ptr() if d_records is not None else None, int(stride),
+                                                   C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

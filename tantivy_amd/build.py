@@ -35,6 +35,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_agg.cpp"),
     os.path.join(HERE, "csrc", "tq_agg_terms.hip"),
     os.path.join(HERE, "csrc", "tq_agg_terms.cpp"),
+    os.path.join(HERE, "csrc", "tq_agg_terms_sub.hip"),
+    os.path.join(HERE, "csrc", "tq_agg_terms_sub.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -62,6 +64,7 @@ SOURCES = [
 HEADERS = [
     os.path.join(HERE, "csrc", "tq_common.hpp"),
     os.path.join(HERE, "csrc", "tq_column_read.hpp"),
+    os.path.join(HERE, "csrc", "tq_agg_metric_image.hpp"),
     os.path.join(HERE, "csrc", "tq_docset_word.hpp"),
     os.path.join(HERE, "csrc", "tq_device.h"),
     os.path.join(HERE, "csrc", "tq_launch.h"),
@@ -102,7 +105,9 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "agg_kernel": "tq_agg.hip", "agg_init_kernel": "tq_agg.hip",
                 "agg_sub_kernel": "tq_agg_sub.hip", "agg_sub_init_kernel": "tq_agg_sub.hip",
                 "agg_terms_count_kernel": "tq_agg_terms.hip", "agg_terms_select_kernel": "tq_agg_terms.hip",
-                "agg_terms_init_kernel": "tq_agg_terms.hip"}
+                "agg_terms_init_kernel": "tq_agg_terms.hip",
+                "agg_terms_sub_count_kernel": "tq_agg_terms_sub.hip", "agg_terms_sub_select_kernel": "tq_agg_terms_sub.hip",
+                "agg_terms_sub_init_kernel": "tq_agg_terms_sub.hip"}
 
 
 def kernel_hash(kernel_names, read=None):

@@ -13,13 +13,12 @@ static_assert(offsetof(tq_agg_terms_t, out_of_range) == offsetof(TqkAggTerms, ou
 
 namespace tqi {
 
-namespace {
-
-int terms_plan(const char *fn, const tq_column_info_t &info, const tq_agg_terms_request &req, tq_agg_terms_plan_t *out) {
+int agg_terms_plan_checked(const char *fn, const tq_column_info_t &info, const tq_agg_terms_request &req, uint32_t max_order,
+                           tq_agg_terms_plan_t *out) {
   *out = tq_agg_terms_plan_t{};
   if (req.segment_size == 0u || req.segment_size > TQ_AGG_TERMS_MAX_SIZE)
     return fail(TQ_ERR_INVALID, "%s: segment_size %u (1..%u, TQ_AGG_TERMS_MAX_SIZE)", fn, req.segment_size, TQ_AGG_TERMS_MAX_SIZE);
-  if (req.order > TQ_TERMS_KEY_DESC) return fail(TQ_ERR_INVALID, "%s: order %u", fn, req.order);
+  if (req.order > max_order) return fail(TQ_ERR_INVALID, "%s: order %u", fn, req.order);
   if (info.gcd == 0u || info.max_value < info.min_value)
     return fail(TQ_ERR_INVALID, "%s: a column with gcd %llu, min %llu, max %llu", fn, (unsigned long long)info.gcd,
                 (unsigned long long)info.min_value, (unsigned long long)info.max_value);
@@ -35,11 +34,11 @@ int terms_plan(const char *fn, const tq_column_info_t &info, const tq_agg_terms_
 }
 
 // the checks of a call, and its plan
-int check_terms_call(tq_segment *s, const char *fn, const tq_agg_terms_request *req, const void *keys, const void *counts,
-                     uint32_t out_stride, tq_agg_terms_plan_t *plan) {
+int agg_terms_check_call(tq_segment *s, const char *fn, const tq_agg_terms_request *req, uint32_t max_order, const void *keys,
+                         const void *counts, uint32_t out_stride, tq_agg_terms_plan_t *plan) {
   if (req->column >= TQ_MAX_COLUMNS || !s->columns[req->column].live)
     return fail(TQ_ERR_INVALID, "%s: column %u is not a live column of the segment", fn, req->column);
-  const int rc = terms_plan(fn, s->columns[req->column].info, *req, plan);
+  const int rc = agg_terms_plan_checked(fn, s->columns[req->column].info, *req, max_order, plan);
   if (rc != TQ_OK) return rc;
   const uint32_t need = std::min(req->segment_size, plan->n_keys);
   if (out_stride < need)
@@ -47,6 +46,8 @@ int check_terms_call(tq_segment *s, const char *fn, const tq_agg_terms_request *
   if (need && (!keys || !counts)) return fail(TQ_ERR_INVALID, "%s: null output rows for %u keys", fn, plan->n_keys);
   return TQ_OK;
 }
+
+namespace {
 
 AggSpec terms_spec(const tq_agg_terms_request *req, const tq_agg_terms_plan_t &plan, tq_agg_terms_t *d_terms, uint64_t *d_keys,
                    uint32_t *d_counts, uint32_t stride) {
@@ -64,6 +65,7 @@ AggSpec terms_spec(const tq_agg_terms_request *req, const tq_agg_terms_plan_t &p
 
 // what the count launches add to: the totals, every query's match count, the records and the scratch rows
 int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st) {
+  if (spec.terms_sub) return agg_terms_sub_prepare(s, spec, n_queries, st);
   const uint32_t n_keys = spec.terms_plan.n_keys;
   const int rc = s->d_agg_term_rows.ensure((size_t)n_queries * n_keys * sizeof(uint32_t) + 64u);
   if (rc != TQ_OK) return rc;
@@ -76,6 +78,7 @@ int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStrea
 
 // the count launch in place of a sub-batch's count / scan / write passes: records and rows under the caller's query index
 int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st) {
+  if (spec.terms_sub) return agg_terms_sub_launch(s, spec, p, q0, st);
   const tq_segment::ColumnHost &col = s->columns[spec.column];
   uint32_t caps[2];
   tqk_agg_terms_lds_capacities(caps);
@@ -97,6 +100,7 @@ int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &
 
 // the selection, once, behind the last sub-batch's count launch on the same stream
 int agg_terms_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st) {
+  if (spec.terms_sub) return agg_terms_sub_finish(s, spec, n_queries, st);
   TqkAggTermsSelectParams sp{};
   sp.records = (TqkAggTerms *)spec.d_terms;
   sp.rows = (const uint32_t *)s->d_agg_term_rows.p;
@@ -120,7 +124,7 @@ extern "C" {
 int tq_agg_terms_plan(const tq_column_info_t *info, const tq_agg_terms_request *req, tq_agg_terms_plan_t *out) {
   const char *fn = "tq_agg_terms_plan";
   if (!info || !req || !out) return fail(TQ_ERR_INVALID, "%s: null argument", fn);
-  return terms_plan(fn, *info, *req, out);
+  return agg_terms_plan_checked(fn, *info, *req, TQ_TERMS_KEY_DESC, out);
 }
 
 int tq_agg_terms_batch_device(tq_segment *s, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_request *req,
@@ -131,7 +135,7 @@ int tq_agg_terms_batch_device(tq_segment *s, const tq_query *queries, uint32_t n
   try {
     TQ_SEGMENT_LOCK(s);
     tq_agg_terms_plan_t plan;
-    const int rc = check_terms_call(s, fn, req, d_out_keys, d_out_counts, out_stride, &plan);
+    const int rc = agg_terms_check_call(s, fn, req, TQ_TERMS_KEY_DESC, d_out_keys, d_out_counts, out_stride, &plan);
     if (rc != TQ_OK || n_queries == 0) return rc;
     AggSpec spec = terms_spec(req, plan, d_out_terms, d_out_keys, d_out_counts, out_stride);
     DocsetCall call(fn, DocsetConsumer::kAgg);
@@ -150,7 +154,7 @@ int tq_agg_terms_batch(tq_segment *s, const tq_query *queries, uint32_t n_querie
   try {
     TQ_SEGMENT_LOCK(s);
     tq_agg_terms_plan_t plan;
-    int rc = check_terms_call(s, fn, req, out_keys, out_counts, out_stride, &plan);
+    int rc = agg_terms_check_call(s, fn, req, TQ_TERMS_KEY_DESC, out_keys, out_counts, out_stride, &plan);
     if (rc != TQ_OK || n_queries == 0) return rc;
     HIP_TRY(hipSetDevice(s->device));
     rc = wait_segment_idle(s);  // (the buffer below may be a batch in flight's)

@@ -117,8 +117,9 @@ static int segment_upload_common(tq_ctx *ctx, int device, uint32_t max_doc, cons
     }
     // (word 0: the batch's matches; words 1 and 2: a sorted batch's valued matches and row entries, tq_sort.hip; words 3
     // and 4: a sub-aggregation's bucketed docs with a metric value and bucketed docs, tq_agg_sub.hip; word 3 of a terms
-    // aggregation: the entries returned, tq_agg_terms.hip)
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 5u * sizeof(unsigned long long));
+    // aggregation: the entries returned, tq_agg_terms.hip; words 4 and 5 of one with a metric: counted docs with a metric
+    // value and counted docs, tq_agg_terms_sub.hip)
+    if (e == hipSuccess) e = hipMalloc((void **)&s->d_match_counter, 6u * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_tp_info, 2 * sizeof(TqpInfo));
     if (e != hipSuccess) rc = fail(TQ_ERR_HIP, "segment setup: %s", hipGetErrorString(e));
   }
@@ -481,6 +482,11 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
         unsigned long long e = 0;
         HIP_TRY(hipMemcpy(&e, s->d_match_counter + 3, sizeof e, hipMemcpyDeviceToHost));
         s->stats.algorithmic_bytes += 12u * e;
+        if (s->stats_agg_terms_sub) {  // 40 more per entry returned (its record); the metric column's reads
+          unsigned long long b[2] = {0, 0};
+          HIP_TRY(hipMemcpy(b, s->d_match_counter + 4, sizeof b, hipMemcpyDeviceToHost));
+          s->stats.algorithmic_bytes += 40u * e + 8u * b[0] + (s->stats_agg_metric_optional ? 8u * b[1] : 0u);
+        }
       }
       s->stats_sorted = false;
     } else {

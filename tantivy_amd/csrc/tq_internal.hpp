@@ -466,6 +466,9 @@ struct tq_segment {
   bool stats_agg_metric = false, stats_agg_metric_optional = false;
   // ... a terms aggregation (tq_agg_terms_batch*): d_match_counter[3] = entries returned (12 bytes each); the same
   bool stats_agg_terms = false;
+  // ... with a metric (tq_agg_terms_sub_batch*): d_match_counter[4] = counted docs with a value in the metric column,
+  // [5] = counted docs; 40 more bytes per entry returned
+  bool stats_agg_terms_sub = false;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -1087,6 +1090,12 @@ struct AggSpec {
   uint64_t *d_term_keys = nullptr;
   uint32_t *d_term_counts = nullptr;
   uint32_t terms_stride = 0;
+  // tq_agg_terms_sub_batch* (tq_agg_terms_sub.cpp): `terms` (a copy of the request's terms part) with a record of a metric
+  // column per key and, maybe, an order by one metric of it; the survivors' records at q * terms_stride like the rows; the
+  // count and record rows are the segment's scratch.  metric_optional as above
+  const tq_agg_terms_sub_request *terms_sub = nullptr;
+  tq_agg_bucket_stats_t *d_term_stats = nullptr;
+  uint32_t terms_n_queries = 0;  // agg_terms_sub_prepare: the batch's queries
 };
 // One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
 // kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass
@@ -1151,6 +1160,15 @@ int agg_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream
 int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
 int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
 int agg_terms_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
+// the plan and the checks of a terms call under `fn`; max_order: the last order the call serves
+int agg_terms_plan_checked(const char *fn, const tq_column_info_t &info, const tq_agg_terms_request &req, uint32_t max_order,
+                           tq_agg_terms_plan_t *out);
+int agg_terms_check_call(tq_segment *s, const char *fn, const tq_agg_terms_request *req, uint32_t max_order, const void *keys,
+                         const void *counts, uint32_t out_stride, tq_agg_terms_plan_t *plan);
+// tq_agg_terms_sub.cpp: what the three do for a spec with `terms_sub`
+int agg_terms_sub_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
+int agg_terms_sub_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
+int agg_terms_sub_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
 // Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the

@@ -544,6 +544,30 @@ hipError_t tqk_launch_agg_terms_count(const TqkAggTermsParams &p, hipStream_t st
 hipError_t tqk_launch_agg_terms_select(const TqkAggTermsSelectParams &p, hipStream_t st);
 void tqk_agg_terms_lds_capacities(uint32_t out[2]);  // the count kernel's two LDS tables, in keys: small, large
 uint32_t tqk_agg_terms_max_size();                   // the largest segment_size
+// ---- terms aggregation with a metric (tq_agg_terms_sub.hip): the launches above with a record of a METRIC column B per key
+// and a selection that may order by one metric of it (tq_agg_terms_sub_batch*).  The scratch is per query a count row and a
+// record row of n_keys entries each; the select launch also writes the survivors' records.
+struct TqkAggTermsSubParams {
+  TqkAggTermsParams t;         // the key column A and everything the count launch takes; t.totals is [6]: += matches, matches
+                               // with a value in A, -, entries returned (the select launch), counted docs with a value in B,
+                               // counted docs
+  TqkColumn col_b;             // the metric column
+  uint64_t min_value_b, gcd_b;
+  TqkAggBucketStats *stats;    // scratch records of the sub-batch's first query on: [n_queries][t.n_keys]
+  uint32_t value_type_b;       // TQ_VALUE_F64: no sum
+};
+struct TqkAggTermsSubSelectParams {
+  TqkAggTermsSelectParams s;       // s.order: TQ_TERMS_* up to TQ_TERMS_METRIC_ASC
+  const TqkAggBucketStats *stats;  // [n_queries][s.n_keys]
+  TqkAggBucketStats *out_stats;    // [n_queries][s.out_stride]: entries [0, n_returned) of a row are written
+  uint32_t value_type_b;           // TQ_VALUE_* of B
+  uint32_t metric;                 // tq_terms_metric, read under the two metric orders
+};
+hipError_t tqk_launch_agg_terms_sub_init(TqkAggTerms *records, uint32_t *rows, TqkAggBucketStats *stats, uint32_t n_queries,
+                                         uint32_t n_keys, hipStream_t st);
+hipError_t tqk_launch_agg_terms_sub_count(const TqkAggTermsSubParams &p, hipStream_t st);
+hipError_t tqk_launch_agg_terms_sub_select(const TqkAggTermsSubSelectParams &p, hipStream_t st);
+void tqk_agg_terms_sub_lds_capacities(uint32_t out[2]);  // the count kernel's two LDS tables, in keys: small, large
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
