@@ -609,7 +609,7 @@ int tq_decode_position_deltas(tq_segment *seg, tq_term_handle term, uint32_t *ou
  * an unknown `which`, a handle that is out of range or a released term set: TQ_ERR_INVALID.  Per-segment tables ignore
  * `term`.  Layouts: tantivy_amd/csrc/tq_device.h (TqdTermHead / TqdTerm / TqdSegment); TQ_TABLE_RMAX = every level as
  * laid out by tqd_rm_level_off; TQ_TABLE_RDIR = the directory words (padded to four), then one entry per posting;
- * TQ_TABLE_FLAT = the doc ids (padded to 16 bytes), then min(tf, 255) per posting; TQ_TABLE_LNORM = 128 bytes per block. */
+ * TQ_TABLE_FLAT = the doc ids (padded to 16 bytes), then min(tf, 255) per posting; TQ_TABLE_LNORM = 128 bytes per block; TQ_TABLE_LMAT = 128 u64 per block, empty while the table is older than the doc matrix. */
 enum {
   TQ_TABLE_REC = 0,        /* (n_blocks + 1) x 4 u32 */
   TQ_TABLE_COARSE = 1,
@@ -628,6 +628,7 @@ enum {
   TQ_TABLE_PROBE_DENSE = 14,   /* the probe pool's, while the list holds a slot */
   TQ_TABLE_PROBE_TF8 = 15,
   TQ_TABLE_PROBE_POS_DIR = 16,
+  TQ_TABLE_LMAT = 17,          /* n_blocks x 128 u64: the doc-matrix words of the list's docs in posting order (empty while stale) */
   TQ_TABLE_DOCMAT = 32,        /* per segment: max_doc u64 */
   TQ_TABLE_DOCCLS = 33,        /* max_doc u64 */
   TQ_TABLE_LOCAL_CACHE = 34,   /* 256 floats: Bm25Weight.cache under the segment's own average fieldnorm */
@@ -1232,6 +1233,9 @@ typedef struct tq_segment_stats {
   uint32_t probe_evictions;     /* lists whose probe tables ("probe_budget_x") gave their slot to another list */
   uint64_t device_scratch_bytes; /* partial / result lists + staging lists of the term-major launches: ONE set
                                     per device, shared by all its segments (count it once per device) */
+  uint64_t lead_mat_bytes;      /* leaders' doc-matrix words in posting order ("lead_mat_budget_x"): derived, a budget of their own */
+  uint32_t lead_mat_stale;      /* leaders of the last planned batch whose such table was older than the doc matrix: not used */
+  uint32_t pad_;
 } tq_segment_stats;
 int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
 /* knobs: "exhaustive" (0/1, default 0: block-max pruning as block_wand / block_wand_intersection
@@ -1281,6 +1285,12 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        leader blocks in whose doc span the directory counts no posting; before, such a list needed a
  *        max_doc / 4-byte slot of the probe pool (19 x the segment's bytes resident after a 65 536-term stream,
  *        5 x with directories),
+ *        "lead_mat_budget_x" (default 4, 0 = none built, none used) / "lead_mat_cut" (default 16): a list that leads
+ *        queries of the shared intersection launch and holds at most max_doc / cut postings gets the doc-matrix words
+ *        of its docs in posting order (8 bytes per posting, tq_segment_stats.lead_mat_bytes), while such tables stay
+ *        below this multiple of the segment's bytes: the launch reads them as one 16-byte load per lane instead of
+ *        two gathers.  A table is a copy: it is used only while no term was prepared since it was filled, and
+ *        refilled once a batch finds the doc matrix unchanged since the batch before it,
  *        "count_bitmap_ratio" (default 128, 0 = never): tq_count_batch evaluates a query as a bitwise
  *        expression over bitmap words (4-8 bytes per list per 32 docs, no postings decoded; a list
  *        without a bitmap is scattered into a scratch bitmap once per batch) when the clause a scan

@@ -98,7 +98,8 @@ class TqSegmentStats(C.Structure):
         "index_bytes", "positions_bytes", "fieldnorm_bytes", "alive_bytes", "term_table_bytes",
         "bitmap_bytes", "docmat_bytes", "posdir_bytes", "scratch_bytes", "dense_budget_bytes")] + [
         (n, C.c_uint32) for n in ("n_terms", "n_dense_lists", "n_docmat_columns", "probe_evictions")] + [
-        ("device_scratch_bytes", C.c_uint64)]
+        ("device_scratch_bytes", C.c_uint64), ("lead_mat_bytes", C.c_uint64), ("lead_mat_stale", C.c_uint32),
+        ("pad_", C.c_uint32)]
 
 
 class TqTermInfo(C.Structure):  # tq_term_info: the fields of a TermInfo as tq_term_prepare_batch takes them
@@ -183,7 +184,7 @@ TERM_TABLES = {
     "pos_blk": (4, np.uint64), "pos_tail": (5, np.uint32), "dense": (6, np.uint32), "bits": (7, np.uint32),
     "pos_dir": (8, np.uint32), "tf8": (9, np.uint8), "rmax": (10, np.uint8), "rdir": (11, np.uint32),
     "lnorm": (12, np.uint8), "flat": (13, np.uint8), "probe_dense": (14, np.uint32), "probe_tf8": (15, np.uint8),
-    "probe_pos_dir": (16, np.uint32),
+    "probe_pos_dir": (16, np.uint32), "lmat": (17, np.uint64),
     "docmat": (32, np.uint64), "doccls": (33, np.uint64), "local_cache": (34, np.float32), "min_fieldnorm_id": (35, np.uint32),
 }
 
@@ -1486,7 +1487,7 @@ class DeviceIndex:
         _check(lib().tq_segment_get_stats(self.segment_raw(segment_ord), C.byref(st)))
         out = {n: int(getattr(st, n)) for n, _ in TqSegmentStats._fields_}
         out["derived_bytes"] = (out["term_table_bytes"] + out["bitmap_bytes"] + out["docmat_bytes"]
-                                + out["posdir_bytes"])
+                                + out["posdir_bytes"] + out["lead_mat_bytes"])
         out["tantivy_bytes"] = (out["index_bytes"] + out["positions_bytes"] + out["fieldnorm_bytes"]
                                 + out["alive_bytes"])
         return out

@@ -562,6 +562,8 @@ int tq_segment_get_stats(tq_segment *s, tq_segment_stats *out) {
   r.n_docmat_columns = s->n_mat_slots;
   r.probe_evictions = (uint32_t)std::min<uint64_t>(s->probe_evictions, 0xFFFFFFFFull);
   r.dense_budget_bytes = s->dense_budget();
+  r.lead_mat_bytes = s->lmat_bytes_total;
+  r.lead_mat_stale = s->lmat_stale_skips;
   *out = r;
   return TQ_OK;
 }
@@ -583,6 +585,10 @@ int tq_set_option(tq_segment *s, const char *name, int64_t value) {
     s->opt.dense_ratio = (int)value;
   else if (!strcmp(name, "rdir_budget_x") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.rdir_budget_x = (int)value;
+  else if (!strcmp(name, "lead_mat_budget_x") && value >= 0 && value <= 0x7FFFFFFF)  // (0: the tables that exist are not used)
+    s->opt.lead_mat_budget_x = (int)value;
+  else if (!strcmp(name, "lead_mat_cut") && value >= 1 && value <= 0x7FFFFFFF)  // affects tables built afterwards
+    s->opt.lead_mat_cut = (int)value;
   else if (!strcmp(name, "probe_budget_x") && value >= 0 && value <= 0x7FFFFFFF)
     s->opt.probe_budget_x = (int)value, s->probe_full = false;
   else if (!strcmp(name, "dense_budget_x") && value >= 0)
@@ -717,6 +723,7 @@ bool table_span(tq_segment *s, uint32_t term, uint32_t which, TableSpan &sp) {
     case TQ_TABLE_RMAX: span(list ? t.rmax_blob : nullptr, tqd_rm_level_off(s->max_doc, TQD_RM_LEVELS)); return true;
     case TQ_TABLE_RDIR: span(list ? t.rdir_blob : nullptr, t.rdir_shift ? rdir_bytes(s, t.doc_freq, t.rdir_shift) : 0); return true;
     case TQ_TABLE_LNORM: span(list ? t.lnorm_blob : nullptr, (size_t)t.n_blocks * 128u); return true;
+    case TQ_TABLE_LMAT: span(list && lmat_valid(s, t) ? t.lmat_blob : nullptr, (size_t)t.n_blocks * 1024u); return true;
     case TQ_TABLE_FLAT:
       span(list ? t.flat_blob : nullptr, (((size_t)t.doc_freq * sizeof(uint32_t) + 15) & ~(size_t)15) + t.doc_freq);
       return true;

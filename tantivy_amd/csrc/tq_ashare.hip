@@ -75,11 +75,13 @@ constexpr uint32_t AS_GROUP = TQD_AS_GROUP;
 // compactions / flush selects / flushes; bytes the lanes consume (bench.py's useful_bytes): 0x100000 payload +
 // record bytes of the decoded blocks, 0x200000 fieldnorm bytes, 0x400000 doc-matrix words gathered, 0x800000
 // range-maxima bytes; 0x40000000 the fieldnorm bytes among those that were gathered doc by doc out of the fieldnorm file
-// (a leader without norm bytes in posting order, TermHost::lnorm_blob).  None of them changes a result.
-constexpr uint32_t AS_COUNTER_BITS = 0x7FE0u | 0xF00000u | 0x40000000u;
+// (a leader without norm bytes in posting order, TermHost::lnorm_blob); 0x20000000 the doc-matrix words among those of
+// 0x400000 that were gathered doc by doc out of the matrix (a leader without its words in posting order,
+// TermHost::lmat_blob).  None of them changes a result.
+constexpr uint32_t AS_COUNTER_BITS = 0x7FE0u | 0xF00000u | 0x40000000u | 0x20000000u;
 
 template <bool BOOLQ>
-struct AShareLds {  // per wavefront: 4.8 KB either way — 3.8 KB + `bw` (boolean leads) or + `pay` (intersections); 20 wavefronts per CU
+struct AShareLds {  // per wavefront: 3.8 KB + `bw` (boolean leads: 4.8 KB) or + `pay` + `mat` (intersections: 5 904 B); 20 wavefronts per CU
   float cache[256];                            // Bm25Weight.cache of the task's queries
   uint32_t q_doc[127], q_tf[127], q_tag[127];  // survivors: doc, leader tf, lead slot | fieldnorm id << 8
   TqdALeadLds lead[AS_GROUP];                  // the leads of the task (what the scoring stage needs)
@@ -89,6 +91,8 @@ struct AShareLds {  // per wavefront: 4.8 KB either way — 3.8 KB + `bw` (boole
   uint32_t flen[AS_GROUP];                     // per family head: leads in the family (itself + its twins)
   float bw[BOOLQ ? AS_GROUP * TQD_AS_MAX_TERMS : 1];  // boolean leads: what every list of the query can add to the lead's docs
   uint32_t pay[(TQ_AS_PREFETCH && !BOOLQ) ? 260 : 1];  // the NEXT wanted block's bitpacked payload (<= 1008 B), landed by LDS-DMA
+  // ... and, for a leader with TermHost::lmat_blob, the doc-matrix words of its 128 docs (1 KB, 16 bytes per lane), landed the same way
+  alignas((TQ_AS_PREFETCH && !BOOLQ) ? 16 : 4) uint32_t mat[(TQ_AS_PREFETCH && !BOOLQ) ? 256 : 1];
 };
 
 // k-th largest of the n (<= 64 R) keys held R per lane (0 = empty); n >= k
@@ -468,6 +472,13 @@ ashare_kernel(TqkAShareParams p) {
     auto norm_pair = [&](uint32_t j) __attribute__((always_inline)) -> uint32_t {  // lane l: the bytes of docs 2 l, 2 l + 1 of block j
       return reinterpret_cast<const uint16_t *>(tbase + ((uint64_t)lnorm << 3))[(size_t)j * 64u + (uint32_t)lane];
     };
+    // ... and the doc-matrix words of its docs in posting order, 1 KB per block (TermHost::lmat_blob, in any2_hi; 0 = none,
+    // or older than the matrix): lane l's two words are one aligned 16-byte load whose address does not depend on the docs
+    uint32_t lmat = 0;
+    if constexpr (!BOOLQ) lmat = sload(&p.leads[lead0].any2_hi);
+    auto mat_pair = [&](uint32_t j) __attribute__((always_inline)) -> uint4 {
+      return reinterpret_cast<const uint4 *>(tbase + ((uint64_t)lmat << 3))[(size_t)j * 64u + (uint32_t)lane];
+    };
     if (ci != cache_loaded) {
       const float *cg = p.caches + (size_t)ci * 256u;
       wave_mem_fence();
@@ -658,10 +669,15 @@ ashare_kernel(TqkAShareParams p) {
       // no registers) while the current block's doc-matrix gathers, tests and scoring run: a block's
       // chain of dependent round trips loses its first link.
       uint32_t npair_next = 0;  // ... and, in a register, the norm bytes of this lane's two docs of that block
+      // ... and their doc-matrix words (a leader with TermHost::lmat_blob) travel to L.mat like the payload: in registers
+      // they would be four more live across stages F and C (scratch 68 -> 108 bytes per lane by the compiler's report)
       auto prefetch = [&](uint64_t rest) __attribute__((always_inline)) {
         if (!PF || !rest) return;
         const uint32_t nb2 = (uint32_t)__builtin_ctzll(rest);
         if (lnorm) npair_next = norm_pair(i_base + nb2);
+        if (lmat)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(tbase + ((uint64_t)lmat << 3) + (size_t)(i_base + nb2) * 1024u + 16u * (uint32_t)lane),
+                                           (__attribute__((address_space(3))) void *)L.mat, 16, 0, 0);
         const uint32_t meta = (uint32_t)__builtin_amdgcn_readlane((int)rec_mine.y, (int)nb2);
         const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)rec_mine.z, (int)nb2);
         if (meta == META_TAIL) return;
@@ -707,10 +723,13 @@ ashare_kernel(TqkAShareParams p) {
         uint32_t c0, c1, t0, t1;
         // (the block's line of norm bytes is asked for WITH its payload: its address does not depend on the docs)
         uint32_t npair = 0;
+        uint4 mpair = make_uint4(0u, 0u, 0u, 0u);
         if constexpr (PF) {
         npair = npair_next;  // (asked for under the block before; the waits below cover it)
         if (mo_l.x == META_TAIL) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          wave_mem_fence();
+          if (lmat) mpair = *reinterpret_cast<const uint4 *>(&L.mat[4u * (uint32_t)lane]);
           decode_docs<USE_DPP>(idx, lead, mo_l, prev_l, lane, c0, c1);
           decode_tfs(idx, lead, mo_l, lane, t0, t1);
         } else {
@@ -719,6 +738,7 @@ ashare_kernel(TqkAShareParams p) {
           const uint32_t tf_bits = lead.has_freq ? (mo_l.x >> 8) & 0xFFu : 0u;
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the prefetched payload has landed
           wave_mem_fence();
+          if (lmat) mpair = *reinterpret_cast<const uint4 *>(&L.mat[4u * (uint32_t)lane]);  // (first: LDS answers in order)
           if (lead.has_freq) {
             unpack2_lds(L.pay + 4u * doc_bits, tf_bits, lane, t0, t1);
             t0 += strict;  // minus-one encoding is tied to the strict flag
@@ -731,10 +751,16 @@ ashare_kernel(TqkAShareParams p) {
           unpack2_lds(L.pay, doc_bits, lane, x0, x1);
           finish_docs<USE_DPP>(x0, x1, strict, prev_l, lane, c0, c1);
         }
-        wave_mem_fence();  // (every lane has read its payload words: the next block's may land)
+        // Write after read: the next block's LDS-DMA lands in L.pay and L.mat, and a fence of wavefront scope waits for
+        // nothing.  Every LDS read of this block has to have RETURNED before the DMA is issued — the payload words were
+        // consumed by finish_docs, the doc-matrix words are consumed only in stage F, after the prefetch: without this
+        // wait a read served late gets the next block's words.  (The operands keep the read in front of the wait.)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mpair.x), "+v"(mpair.y), "+v"(mpair.z), "+v"(mpair.w) : : "memory");
+        wave_mem_fence();  // (every lane has read its payload and matrix words: the next block's may land)
         prefetch(todo);
         } else {
         if (lnorm) npair = norm_pair(i_base + b);
+        if (lmat) mpair = mat_pair(i_base + b);
         decode_docs<USE_DPP>(idx, lead, mo_l, prev_l, lane, c0, c1);
         decode_tfs(idx, lead, mo_l, lane, t0, t1);
         }
@@ -772,11 +798,19 @@ ashare_kernel(TqkAShareParams p) {
         const float tfn1 = f1 * __builtin_amdgcn_rcpf(f1 + L.cache[nid1]);
         const bool g0 = v0 && tfn0 >= block_need, g1 = v1 && tfn1 >= block_need;
         // ONE gather per doc that may matter: membership in every column list + signature bits
-        const uint64_t mw0 = g0 ? seg.docmat[c0] : 0ull;
-        const uint64_t mw1 = g1 ? seg.docmat[c1] : 0ull;
+        // (a leader with its words in posting order: they came with the block, g0 / g1 gate them as they gate the gather)
+        uint64_t mw0, mw1;
+        if (lmat) {
+          mw0 = g0 ? (uint64_t)mpair.x | ((uint64_t)mpair.y << 32) : 0ull;
+          mw1 = g1 ? (uint64_t)mpair.z | ((uint64_t)mpair.w << 32) : 0ull;
+        } else {
+          mw0 = g0 ? seg.docmat[c0] : 0ull;
+          mw1 = g1 ? seg.docmat[c1] : 0ull;
+        }
         const uint64_t valid0 = __ballot(g0), valid1 = __ballot(g1);
         if (p.debug & 0x200000u) n_scored += (uint32_t)(__popcll(__ballot(v0)) + __popcll(__ballot(v1)));  // COUNTERS
         if (p.debug & 0x400000u) n_scored += (uint32_t)(__popcll(valid0) + __popcll(valid1));
+        if ((p.debug & 0x20000000u) && !lmat) n_scored += (uint32_t)(__popcll(valid0) + __popcll(valid1));
         if (TQ_AS_TIMERS && tphase == 5u && (uint32_t)mw0 == 0xFFFFFFFEu) ++n_scored;  // (the gathers have to land inside the region)
         te(5u);
         tb(6u);

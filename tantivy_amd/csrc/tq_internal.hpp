@@ -136,6 +136,10 @@ struct TermHost {
   void *lnorm_blob = nullptr;  // the fieldnorm ids of the list's docs in posting order (byte i = fieldnorm[doc of
                                // posting i], 128 bytes per block), built the first time the list LEADS queries of a
                                // shared-intersection launch: stage A reads one line per block instead of 128 gathers
+  void *lmat_blob = nullptr;   // the doc-matrix words of the list's docs in posting order (word i = docmat[doc of posting
+                               // i], 1 KB per block, zero padding behind the last posting), built like lnorm_blob for a
+                               // leader under the "lead_mat_cut": stage A reads one 16-byte load per lane instead of two gathers
+  uint64_t lmat_epoch = 0;     // tq_segment::docmat_epoch the table was filled at: it is used only while the two are equal
   uint32_t doc_freq = 0, n_blocks = 0, n_full = 0, n_tail = 0;
   uint32_t last_doc = 0;
   bool wants_col = true;  // false: the segment's columns are reserved for other lists
@@ -201,6 +205,10 @@ struct Options {
   // max_doc / xunion_ratio postings (0 = never), if the batch has at least xunion_min_queries of them
   int xunion_ratio = 64;
   int xunion_min_queries = 64;
+  int lead_mat_budget_x = 4;  // leaders' doc-matrix words in posting order (TermHost::lmat_blob, 8 B per posting): at most this
+                              // multiple of the segment, 0 = none are built or used
+  int lead_mat_cut = 16;      // ... only for leaders whose postings are on average at least this many docs apart (a denser
+                              // list's docs share doc-matrix lines: it keeps the gather)
   int rdir_budget_x = 4;    // range directories of the lists below "dense_ratio" (6-8 B per posting): at most this multiple of the segment
   int probe_budget_x = 16;  // bitmaps + tf bytes built on demand for the lists boolean queries probe: at most this multiple of the segment
   int count_bitmap_ratio = 128;  // Count: bitmap words instead of a scan if the driving clause holds >= max_doc / ratio postings per list
@@ -377,6 +385,15 @@ struct tq_segment {
   uint64_t share_table_lo = 0;
   bool share_span_ok = true;
   bool lnorm_off = false;  // a leader-norm table came to lie outside that span (build_lnorm): no more of them are built
+  // Leaders' doc-matrix words in posting order (TermHost::lmat_blob) are copies of doc-matrix words: every writer of the
+  // matrix bumps docmat_epoch (docmat_written), a table is used only while its lmat_epoch equals it.  A stale table is
+  // refilled — in place, on the batch's stream behind order_batch, so after every batch that may read it — only when
+  // the epoch did not move since the previous batch was planned (docmat_epoch_planned): a stream that prepares terms
+  // in every batch never refills.
+  uint64_t docmat_epoch = 1, docmat_epoch_planned = 0;
+  size_t lmat_bytes_total = 0;
+  bool lmat_off = false;   // a table came to lie outside the span: no more of them are built
+  uint32_t lmat_stale_skips = 0;  // leaders of the last planned batch whose table was stale and therefore not used
   uint32_t last_batch_queries = 0;
   // sloppy phrases (tq_phrase_slop.cpp): per query of the batch, candidate docs whose carried list went over the cap
   DevBuf d_slop_over;
@@ -948,6 +965,23 @@ int add_to_doc_signatures(tq_segment *s, uint32_t handle);
 int build_dense_device(tq_segment *s, uint32_t handle);
 int build_flat(tq_segment *s, uint32_t handle, hipStream_t st, bool *ok);
 void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st);
+// the doc matrix has been (or is being) written: tables copied out of it are stale
+inline void docmat_written(tq_segment *s) { ++s->docmat_epoch; }
+// (experiments: TQ_LEAD_MAT_BUDGET_X / TQ_LEAD_MAT_CUT override the options "lead_mat_budget_x" / "lead_mat_cut")
+inline int lead_mat_budget_x(const tq_segment *s) {
+  static const uint32_t kEnv = tune_u32("TQ_LEAD_MAT_BUDGET_X", 0xFFFFFFFFu);
+  return kEnv != 0xFFFFFFFFu ? (int)std::min<uint32_t>(kEnv, 0x7FFFFFFFu) : s->opt.lead_mat_budget_x;
+}
+inline uint32_t lead_mat_cut(const tq_segment *s) {
+  static const uint32_t kEnv = tune_u32("TQ_LEAD_MAT_CUT", 0);
+  return kEnv ? kEnv : (uint32_t)std::max(1, s->opt.lead_mat_cut);
+}
+inline bool lmat_valid(const tq_segment *s, const TermHost &t) {
+  return t.lmat_blob && t.lmat_epoch == s->docmat_epoch && lead_mat_budget_x(s) > 0;
+}
+// true: the list has a table this batch may name; *fill: ... once fill_lmat has run for it on the batch's stream
+bool plan_lmat(tq_segment *s, uint32_t handle, bool *fill);
+hipError_t fill_lmat(tq_segment *s, uint32_t handle, hipStream_t st);
 void prep_apply_lmax(tq_segment *s, bool wait);    // rmax_list of lists prepared by finished tq_term_prepare_batch calls
 // ---- tq_term_probe.cpp
 // must: the caller cannot run without the tables (nested boolean queries): any segment size, the least recently used

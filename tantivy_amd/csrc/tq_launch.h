@@ -640,6 +640,9 @@ hipError_t tqk_launch_flat_list(const TqdSegment &seg, const TqdTerm *terms, uin
 // the fieldnorm ids of a list's docs in posting order, 128 bytes per block (TermHost::lnorm_blob; needs a fieldnorm file)
 hipError_t tqk_launch_lead_norms(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle, uint32_t n_blocks,
                                  uint8_t *out, hipStream_t st);
+// the doc-matrix words of a list's docs in posting order, 128 u64 per block (TermHost::lmat_blob)
+hipError_t tqk_launch_lead_mat(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle, uint32_t n_blocks,
+                               uint64_t *out, hipStream_t st);
 hipError_t tqk_launch_decode_list(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle,
                                   uint32_t n_blocks, uint32_t *docs, uint32_t *tfs, bool use_dpp,
                                   hipStream_t st);

@@ -290,6 +290,23 @@ __global__ __launch_bounds__(256) void lead_norms_kernel(TqdSegment seg, const T
   reinterpret_cast<uint16_t *>(out)[j * 64u + (uint32_t)lane] = (uint16_t)(n0 | (n1 << 8));
 }
 
+// The doc-matrix words of a list's docs in POSTING order (TermHost::lmat_blob: word i = docmat[doc of posting i]; one wave
+// per 128-doc block, lane l stores the words of postings 2 l and 2 l + 1 as one 16-byte store): what stage A of the
+// shared-intersection launch reads as one aligned 16-byte load per lane instead of two 8-byte gathers out of the
+// matrix.  Words behind the last posting of the last block are zero.
+__global__ __launch_bounds__(256) void lead_mat_kernel(TqdSegment seg, const TqdTerm *terms, uint32_t handle, uint64_t *out) {
+  const int lane = (int)__lane_id();
+  const uint32_t wave = uni(threadIdx.x >> 6);
+  const TermRef t = load_term(terms, handle);
+  const uint32_t j = blockIdx.x * 4u + wave;
+  if (j >= t.n_blocks) return;
+  uint32_t d0, d1;
+  decode_docs<true>(uni_ptr(seg.idx), t, uni_mo(t, j), block_prev_last(t, j), lane, d0, d1);
+  // (a doc id beyond the segment — the terminator of a short tail, or a malformed list — reads nothing)
+  const uint64_t w0 = d0 < seg.max_doc ? seg.docmat[d0] : 0ull, w1 = d1 < seg.max_doc ? seg.docmat[d1] : 0ull;
+  reinterpret_cast<ulonglong2 *>(out)[(size_t)j * 64u + (uint32_t)lane] = make_ulonglong2(w0, w1);
+}
+
 }  // namespace
 
 // =================================================================== launch wrappers
@@ -302,6 +319,12 @@ hipError_t tqk_launch_lead_norms(const TqdSegment &seg, const TqdTerm *terms, ui
                                  uint8_t *out, hipStream_t st) {
   if (n_blocks == 0 || !seg.fieldnorm) return hipSuccess;
   hipLaunchKernelGGL(lead_norms_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, st, seg, terms, handle, out);
+  return hipGetLastError();
+}
+hipError_t tqk_launch_lead_mat(const TqdSegment &seg, const TqdTerm *terms, uint32_t handle, uint32_t n_blocks,
+                               uint64_t *out, hipStream_t st) {
+  if (n_blocks == 0 || !seg.docmat) return hipSuccess;
+  hipLaunchKernelGGL(lead_mat_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, st, seg, terms, handle, out);
   return hipGetLastError();
 }
 hipError_t tqk_launch_docmat_init(uint64_t *mat, const uint8_t *fieldnorm, uint32_t const_id,

@@ -437,6 +437,8 @@ int build_ashare_plan(tq_segment *s, Group &g, PlanScratch &ps, bool boolean, ui
         }
         // (the leader's fieldnorm ids in posting order, TermHost::lnorm_blob: the boolean leads' any2 words are free here)
         ld.any2_lo = off_of(s->terms[dq.term[0]].lnorm_blob);
+        // (... and its doc-matrix words in posting order, TermHost::lmat_blob, while they are as fresh as the matrix)
+        ld.any2_hi = lmat_valid(s, s->terms[dq.term[0]]) ? off_of(s->terms[dq.term[0]].lmat_blob) : 0u;
         ld.k = dq.k;
         ld.thr_row = dq.thr_index;
         unsorted[lead0[q]] = ld;

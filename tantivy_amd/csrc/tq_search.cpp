@@ -64,6 +64,7 @@ struct Batch {
   DeviceScratch *sc = nullptr;
   int slot = 0;
   uint32_t grid[kNGroups] = {};  // persistent grid of a result-list group
+  std::vector<uint32_t> lmat_fill;  // leaders whose doc-matrix words in posting order this batch (re)fills (fill_leader_mats)
 };
 
 }  // namespace
@@ -74,7 +75,7 @@ void update_table_span(tq_segment *s) {
   if (s->share_span_terms == s->terms.size()) return;  // (terms are prepared rarely)
   uint64_t lo = ~0ull, hi = 0;
   for (const TermHost &th : s->terms)
-    for (const void *ptr : {th.dense_blob, th.tf8_blob, th.probe_dense_blob, th.probe_tf8_blob, th.rmax_blob, th.posdir_blob, th.probe_posdir_blob, th.lnorm_blob})
+    for (const void *ptr : {th.dense_blob, th.tf8_blob, th.probe_dense_blob, th.probe_tf8_blob, th.rmax_blob, th.posdir_blob, th.probe_posdir_blob, th.lnorm_blob, th.lmat_blob})
       if (ptr) {
         lo = std::min<uint64_t>(lo, (uint64_t)ptr);
         hi = std::max<uint64_t>(hi, (uint64_t)ptr);
@@ -364,12 +365,22 @@ void count_leaders(Batch &b) {
 
 // The leaders of this batch's shared-intersection launch get their norm bytes in posting order (build_lnorm, tq_terms.cpp)
 // the first time they lead: a launch each on the batch's stream, ahead of the batch's kernels.
+// ... and their doc-matrix words in posting order (plan_lmat: allocated and named here, filled by fill_leader_mats).
 void build_leader_norms(Batch &b) {
-  if (!b.ashare_and || !b.s->dseg.fieldnorm) return;
-  const PlanScratch &ps = *b.ps;
-  for (size_t h = 0; h < ps.and_lead_count.size(); ++h)
-    if (ps.and_lead_count[h] >= knobs().ashare_min && !b.s->terms[h].lnorm_blob) build_lnorm(b.s, (uint32_t)h, b.st);
-  update_table_span(b.s);  // (new tables moved it; share_span_ok decided the batch's route before they existed)
+  tq_segment *s = b.s;
+  s->lmat_stale_skips = 0;
+  if (b.ashare_and) {
+    const PlanScratch &ps = *b.ps;
+    const bool norms = s->dseg.fieldnorm != nullptr;
+    for (size_t h = 0; h < ps.and_lead_count.size(); ++h) {
+      if (ps.and_lead_count[h] < knobs().ashare_min) continue;
+      if (norms && !s->terms[h].lnorm_blob) build_lnorm(s, (uint32_t)h, b.st);
+      bool fill = false;
+      if (plan_lmat(s, (uint32_t)h, &fill) && fill) b.lmat_fill.push_back((uint32_t)h);
+    }
+    update_table_span(s);  // (new tables moved it; share_span_ok decided the batch's route before they existed)
+  }
+  s->docmat_epoch_planned = s->docmat_epoch;
 }
 
 // One query's routing: its descriptor and the launch group it joins.
@@ -1104,6 +1115,25 @@ int order_batch(Batch &b) {
   return TQ_OK;
 }
 
+// The leaders' doc-matrix words in posting order this batch planned with (build_leader_norms): filled on the batch's
+// stream, behind every earlier batch of the segment (a refill rewrites a table those may read) and ahead of its kernels.
+// (a plan that is dropped before its tables were filled — a replan, an error on the way — leaves them marked stale)
+void drop_leader_mats(Batch &b) {
+  for (uint32_t h : b.lmat_fill) b.s->terms[h].lmat_epoch = 0;
+  b.lmat_fill.clear();
+}
+int fill_leader_mats(Batch &b) {
+  for (uint32_t h : b.lmat_fill) {
+    const hipError_t e = fill_lmat(b.s, h, b.st);
+    if (e != hipSuccess) {
+      drop_leader_mats(b);
+      return fail(TQ_ERR_HIP, "leader doc-matrix words: %s", hipGetErrorString(e));
+    }
+  }
+  b.lmat_fill.clear();
+  return TQ_OK;
+}
+
 // The staging blob up on the copy stream, the new term records into the table's tail on the batch's stream.
 int enqueue_copy(Batch &b) {
   // buffer bx was last read by the batch before the previous one: the copy waits for that
@@ -1672,17 +1702,22 @@ int search_batch_impl(tq_segment *s, const tq_query *queries, uint32_t n_queries
   // a shared launch's result lists over the budget even with the longest tasks: the same batch again, that family
   // through the per-query kernels
   while (rc != TQ_OK && b.replan) {
+    drop_leader_mats(b);
     b = Batch{s, queries, n_queries, out_stride, d_out_scores, d_out_docs, d_out_counts, hip_stream, b.co, d_out_segment_ords, segment_ord};
     b.n_all_queries = strip.n_all_based;
     b.set_q = strip.n_set ? strip.set_q.data() : nullptr;
     b.slop_q = strip.slop_q.empty() ? nullptr : strip.slop_q.data();
     rc = plan_batch(b);
   }
+  struct DropMats {  // (whatever ends the call before fill_leader_mats has run)
+    Batch &b;
+    ~DropMats() { drop_leader_mats(b); }
+  } drop_mats{b};
   if (rc != TQ_OK) return rc;
   // From here to the event behind the batch's last kernel the device's shared scratch is this batch's.
   b.sc = s->dscratch;
   std::unique_lock<std::mutex> scratch_lock(b.sc->m);
-  if ((rc = lay_out_stage(b)) != TQ_OK || (rc = fill_stage(b)) != TQ_OK || (rc = order_batch(b)) != TQ_OK) return rc;
+  if ((rc = lay_out_stage(b)) != TQ_OK || (rc = fill_stage(b)) != TQ_OK || (rc = order_batch(b)) != TQ_OK || (rc = fill_leader_mats(b)) != TQ_OK) return rc;
   DrainOnError drain_on_error{s, b.st};
   if ((rc = enqueue_copy(b)) != TQ_OK || (rc = zero_batch_buffers(b)) != TQ_OK || (rc = launch_groups(b)) != TQ_OK ||
       (rc = launch_merges(b)) != TQ_OK || (rc = finish_batch(b)) != TQ_OK)

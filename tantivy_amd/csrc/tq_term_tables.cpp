@@ -212,6 +212,60 @@ void build_lnorm(tq_segment *s, uint32_t handle, hipStream_t st) {
   s->share_span_terms = ~(size_t)0;  // (the tables' address span is taken again: tq_search.cpp)
 }
 
+// A leader's doc-matrix words in posting order (TermHost::lmat_blob) — 1 KB per block, the tail block included, so that
+// lane l of block j reads its two docs' words as one 16-byte load at 1024 j + 16 l.  Planned here, filled by fill_lmat
+// on the batch's stream BEHIND order_batch: a first fill needs no ordering (no earlier batch names the blob), a refill
+// of a stale table rewrites it in place and must follow every batch that may read it — order_batch puts this batch's
+// stream behind the segment's previous batch, which followed the one before it.  Field-0 lists only (like lnorm; it
+// needs no fieldnorm file), under "lead_mat_cut", inside "lead_mat_budget_x" — a budget of its own — and inside the
+// address span the launch's 32-bit offsets reach.  A stale table is refilled only when the doc matrix did not change
+// since the previous batch was planned; until then the lead carries offset 0 and stage A gathers.
+bool plan_lmat(tq_segment *s, uint32_t handle, bool *fill) {
+  TermHost &t = s->terms[handle];
+  *fill = false;
+  if (lead_mat_budget_x(s) <= 0 || !s->d_docmat) return false;
+  if (t.lmat_blob) {
+    if (t.lmat_epoch == s->docmat_epoch) return true;
+    if (s->docmat_epoch != s->docmat_epoch_planned) {  // (still moving: not this batch)
+      ++s->lmat_stale_skips;
+      return false;
+    }
+    t.lmat_epoch = s->docmat_epoch;
+    *fill = true;
+    return true;
+  }
+  if (s->lmat_off || !t.n_blocks || !t.d_self || t.field || t.set_kind != TermHost::kNoSet) return false;
+  if ((uint64_t)t.doc_freq * lead_mat_cut(s) > s->max_doc) return false;  // (several of its docs share a 128-byte line of the matrix)
+  const size_t bytes = (size_t)t.n_blocks * 1024u;
+  if (s->lmat_bytes_total + bytes > (size_t)lead_mat_budget_x(s) * (s->idx_len + s->pos_len + s->max_doc)) return false;
+  void *blob = nullptr;
+  if (dense_alloc(s, bytes + PAD, &blob) != TQ_OK) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if ((uint64_t)blob & 15u) {  // (the lanes' 16-byte loads; dense_alloc hands out 256-byte multiples: this list only, not the segment)
+    dense_release(s, blob);
+    return false;
+  }
+  if ((uint64_t)blob < s->share_table_lo + 8u || (uint64_t)blob + bytes - s->share_table_lo >= (8ull << 32)) {  // outside the span
+    dense_release(s, blob);
+    s->lmat_off = true;
+    return false;
+  }
+  t.lmat_blob = blob;
+  t.lmat_epoch = s->docmat_epoch;
+  s->lmat_bytes_total += bytes;
+  s->share_span_terms = ~(size_t)0;  // (the tables' address span is taken again: tq_search.cpp)
+  *fill = true;
+  return true;
+}
+hipError_t fill_lmat(tq_segment *s, uint32_t handle, hipStream_t st) {
+  TermHost &t = s->terms[handle];
+  const hipError_t e = tqk_launch_lead_mat(s->dseg, t.d_self, 0u, t.n_blocks, (uint64_t *)t.lmat_blob, st);
+  if (e != hipSuccess) t.lmat_epoch = 0;  // (never a live epoch: the table is refilled before it is used again)
+  return e;
+}
+
 // The doc matrix (TqdSegment::docmat): allocated with the first list that needs it.
 int ensure_docmat(tq_segment *s) {
   if (s->d_docmat) return TQ_OK;
@@ -219,6 +273,7 @@ int ensure_docmat(tq_segment *s) {
   if (s->dense_bytes_total + mat_bytes > s->dense_budget()) return TQ_OK;  // (stays null: over budget)
   HIP_TRY(hipMalloc((void **)&s->d_docmat, mat_bytes + PAD));
   HIP_TRY(hipMemsetAsync((uint8_t *)s->d_docmat + mat_bytes, 0, PAD, s->stream));
+  docmat_written(s);
   const hipError_t e = tqk_launch_docmat_init(s->d_docmat, s->d_fn, s->dseg.const_fieldnorm_id, s->max_doc, s->stream);
   if (e != hipSuccess) return fail(TQ_ERR_HIP, "docmat init: %s", hipGetErrorString(e));
   s->dense_bytes_total += mat_bytes;
@@ -254,6 +309,7 @@ int add_to_doc_signatures(tq_segment *s, uint32_t handle) {
   hipError_t e = hipSuccess;
   if (want_sig) {
     const uint32_t bit = sig_bit(handle);
+    docmat_written(s);
     e = tqk_launch_docmat_set(s->d_docmat, dl.dd, t.doc_freq, (TQD_SIG_SHIFT - 8u) + bit, s->max_doc, s->stream);
     if (e != hipSuccess) return fail(TQ_ERR_HIP, "docmat signature: %s", hipGetErrorString(e));
     s->h_dterms[handle].has_freq |= (bit + 1u) << 16;
@@ -325,6 +381,7 @@ int build_dense_device(tq_segment *s, uint32_t handle) {
     }
     if (s->d_docmat) {
       const uint32_t slot = s->n_mat_slots++;
+      docmat_written(s);
       e = tqk_launch_docmat_set(s->d_docmat, dd, t.doc_freq, slot, s->max_doc, s->stream);
       if (e != hipSuccess) return fail(TQ_ERR_HIP, "docmat set: %s", hipGetErrorString(e));
       // the list's tf classes (the first TQD_CLS_SLOTS columns; 8 B per doc once, inside the dense budget)

@@ -474,6 +474,7 @@ int enqueue_upload(PrepareBatch &b) {
     uint32_t *const *d_tabs = (uint32_t *const *)(d_selfs + n_sig);
     const uint32_t *d_bits = (const uint32_t *)(d_tabs + n_sig);
     uint32_t *d_lmax = (uint32_t *)(d_bits + 3 * n_sig);
+    if (s->d_docmat) docmat_written(s);  // (signature bits; with a null matrix the launch only fills range directories)
     e = tqk_launch_docsig_batch(s->dseg, d_selfs, d_bits, n_sig, s->d_docmat, b.any_tab ? d_tabs : nullptr, d_bits + n_sig,
                                 d_bits + 2 * n_sig, s->d_local_cache, d_lmax, s->opt.use_dpp != 0, cs);
     if (e == hipSuccess && b.any_tab && s->d_local_cache) {

@@ -600,6 +600,29 @@ struct SegmentBatch {
     for (auto &w : weights) total_terms += w.terms.size();
     handles.clear();
     handles.reserve(total_terms);
+    // A warm batch — every term a plain one whose handle the lock-free table knows — takes ONE pass: the handle is a
+    // load, no per-term call, no look for fresh terms first.  The first term the table does not know (a set, an
+    // AllQuery clause, a large id, a term nobody prepared) ends the pass and the general road below starts over.
+    if (const std::atomic<tq_term_handle> *fast = seg.fast_handle_table()) {
+      size_t i = 0;
+      for (; i < n; ++i) {
+        const Weight &w = weights[i];
+        const size_t at = handles.size();
+        bool known = true;
+        for (uint32_t t : w.terms) {
+          const tq_term_handle h = t < SegmentReader::kFastHandles ? fast[t].load(std::memory_order_acquire) : SegmentReader::kHandleUnknown;
+          if (h == SegmentReader::kHandleUnknown) {
+            known = false;
+            break;
+          }
+          handles.push_back(h);
+        }
+        if (!known) break;
+        fill_record(qs[i], w, handles.data() + at, k);
+      }
+      if (i == n) return;
+      handles.clear();
+    }
     if (n > 1) {  // the batch's new terms are prepared together before any handle is asked for
       std::vector<uint32_t> fresh;  // (a replayed or a warm batch has none: no list of 20 000 terms is built to find that out)
       for (auto &w : weights)
@@ -611,22 +634,24 @@ struct SegmentBatch {
       const Weight &w = weights[i];
       const size_t at = handles.size();
       for (uint32_t t : w.terms) handles.push_back(resolve_handle(seg_p, w, t));
-      tq_query &q = qs[i];
-      q.n_terms = (uint32_t)w.terms.size();
-      q.terms = handles.data() + at;  // stable: reserved up front
-      q.weights = w.weights.data();
-      q.tf_cache = w.bm25->tf_cache();
-      q.mode = w.mode;
-      q.phrase_offsets = w.phrase_offsets.empty() ? nullptr : w.phrase_offsets.data();
-      q.k = k;
-      q.occurs = w.occurs.empty() ? nullptr : w.occurs.data();
-      q.clause_of = w.clause_of.empty() ? nullptr : w.clause_of.data();
-      q.min_should_match = w.min_should_match;
-      q.slop = w.slop;
-      q.nested_occurs = w.nested_occurs.empty() ? nullptr : w.nested_occurs.data();
-      q.clause_min_should = w.clause_min_should.empty() ? nullptr : w.clause_min_should.data();
-      q.atom_of = w.atom_of.empty() ? nullptr : w.atom_of.data();
+      fill_record(qs[i], w, handles.data() + at, k);  // (the handles are stable: reserved up front)
     }
+  }
+  static void fill_record(tq_query &q, const Weight &w, const tq_term_handle *terms, uint32_t k) {
+    q.n_terms = (uint32_t)w.terms.size();
+    q.terms = terms;
+    q.weights = w.weights.data();
+    q.tf_cache = w.bm25->tf_cache();
+    q.mode = w.mode;
+    q.phrase_offsets = w.phrase_offsets.empty() ? nullptr : w.phrase_offsets.data();
+    q.k = k;
+    q.occurs = w.occurs.empty() ? nullptr : w.occurs.data();
+    q.clause_of = w.clause_of.empty() ? nullptr : w.clause_of.data();
+    q.min_should_match = w.min_should_match;
+    q.slop = w.slop;
+    q.nested_occurs = w.nested_occurs.empty() ? nullptr : w.nested_occurs.data();
+    q.clause_min_should = w.clause_min_should.empty() ? nullptr : w.clause_min_should.data();
+    q.atom_of = w.atom_of.empty() ? nullptr : w.atom_of.data();
   }
 };
 }  // namespace

@@ -80,6 +80,12 @@ class SegmentReader {
   void prepare_terms(const uint32_t *term_ids, size_t n);
   // term_handle(term_id) would answer from the lock-free table: the term was prepared, or found absent, before
   bool handle_known(uint32_t term_id) const;
+  // The lock-free table behind the two (null before the first prepared term): entry t < kFastHandles is term t's handle,
+  // TQ_TERM_ABSENT for a term the segment does not hold, kHandleUnknown while nobody has asked.  An entry that is known
+  // never changes again: a batch all of whose terms are known reads its handles here, one load each.
+  static constexpr uint32_t kFastHandles = 1u << 20;
+  static constexpr tq_term_handle kHandleUnknown = 0xFFFFFFFEu;
+  const std::atomic<tq_term_handle> *fast_handle_table() const { return fast_handles_.load(std::memory_order_acquire); }
   uint32_t max_doc() const { return max_doc_; }
   uint32_t segment_ord() const { return segment_ord_; }
   // inverted_index_reader.rs:72-73, of one field (a field the segment does not have: 0)
@@ -99,8 +105,6 @@ class SegmentReader {
   std::unordered_map<uint32_t, tq_term_handle> handles_;
   // handles of small term ids, read without the lock (0xFFFFFFFE = not prepared yet): a 10 000-query batch names
   // 20 000 terms per collect_segment — a mutex and a hash lookup each were a third of a millisecond per step
-  static constexpr uint32_t kFastHandles = 1u << 20;
-  static constexpr tq_term_handle kHandleUnknown = 0xFFFFFFFEu;
   std::atomic<std::atomic<tq_term_handle> *> fast_handles_{nullptr};  // (allocated with the first prepared term, 4 MB)
   std::shared_ptr<const class TermInfoStore> store_;
 };
