@@ -65,7 +65,11 @@ HEADERS = [
     os.path.join(HERE, "csrc", "tq_common.hpp"),
     os.path.join(HERE, "csrc", "tq_column_read.hpp"),
     os.path.join(HERE, "csrc", "tq_agg_metric_image.hpp"),
+    os.path.join(HERE, "csrc", "tq_agg_value.hpp"),
+    os.path.join(HERE, "csrc", "tq_agg_device.hpp"),
+    os.path.join(HERE, "csrc", "tq_agg_terms_select.hpp"),
     os.path.join(HERE, "csrc", "tq_docset_word.hpp"),
+    os.path.join(HERE, "csrc", "tq_docset_walk.hpp"),
     os.path.join(HERE, "csrc", "tq_device.h"),
     os.path.join(HERE, "csrc", "tq_launch.h"),
     os.path.join(HERE, "csrc", "tq_fields.h"),
@@ -108,6 +112,10 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "agg_terms_init_kernel": "tq_agg_terms.hip",
                 "agg_terms_sub_count_kernel": "tq_agg_terms_sub.hip", "agg_terms_sub_select_kernel": "tq_agg_terms_sub.hip",
                 "agg_terms_sub_init_kernel": "tq_agg_terms_sub.hip"}
+# the headers the five doc-set consumers (sort, the four aggregations) are assembled from: hashed with any of them
+WALK_FILES = {"tq_sort.hip", "tq_agg.hip", "tq_agg_sub.hip", "tq_agg_terms.hip", "tq_agg_terms_sub.hip"}
+WALK_HEADERS = {"tq_docset_word.hpp", "tq_docset_walk.hpp", "tq_column_read.hpp", "tq_agg_value.hpp", "tq_agg_device.hpp",
+                "tq_agg_terms_select.hpp", "tq_agg_metric_image.hpp"}
 
 
 def kernel_hash(kernel_names, read=None):
@@ -124,6 +132,8 @@ def kernel_hash(kernel_names, read=None):
         base = m.group(1) if m else k
         if base in KERNEL_FILES:
             files.add(KERNEL_FILES[base])
+    if files & WALK_FILES:
+        files |= WALK_HEADERS
     if read is None:
         def read(name):
             with open(os.path.join(HERE, "csrc", name), "rb") as f:

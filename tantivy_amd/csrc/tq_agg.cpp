@@ -7,12 +7,14 @@
 // validation of the queries, the doc-set expression, tree and slop planning, sub-batches, scatter — come from
 // docset_batch (tq_docset.cpp), which calls agg_prepare once and agg_launch per sub-batch.
 // Part of the C ABI library of include/tantivy_amd.h (internal declarations: tq_internal.hpp).
+#include "tq_agg_value.hpp"
 #include "tq_internal.hpp"
 
 #include <cfloat>
 #include <cmath>
 
 static_assert(sizeof(tq_agg_stats_t) == 64 && sizeof(TqkAggStats) == sizeof(tq_agg_stats_t), "the 64-byte record");
+static_assert(TQ_AGGV_U64 == TQ_VALUE_U64 && TQ_AGGV_I64 == TQ_VALUE_I64 && TQ_AGGV_F64 == TQ_VALUE_F64, "tq_agg_value.hpp's value types");
 static_assert(sizeof(tq_agg_request) == 40 && sizeof(tq_agg_hist_plan_t) == 32, "the ABI of the aggregation calls");
 static_assert(sizeof(tq_agg_metric_request) == 8 && sizeof(tq_agg_bucket_stats_t) == 40 && sizeof(TqkAggBucketStats) == sizeof(tq_agg_bucket_stats_t),
               "the ABI of the sub-aggregation calls");
@@ -21,28 +23,7 @@ namespace tqi {
 
 namespace {
 
-// f64_from_fastfield_u64 (src/aggregation/mod.rs:351-383): the same three conversions as agg_f64 of tq_agg.hip
-double agg_f64(uint64_t v, uint32_t value_type) {
-  const uint64_t high = 1ull << 63;
-  if (value_type == TQ_VALUE_I64) return (double)(int64_t)(v ^ high);
-  if (value_type == TQ_VALUE_F64) {
-    const uint64_t bits = (v & high) ? v ^ high : ~v;
-    double d;
-    memcpy(&d, &bits, sizeof d);
-    return d;
-  }
-  return (double)v;
-}
-
-// Rust's `f64 as i64`: saturating, NaN is 0 (a plain C++ cast is undefined out of range)
-int64_t sat_i64(double x) {
-  if (x != x) return 0;
-  if (x >= 9223372036854775808.0) return INT64_MAX;
-  if (x <= -9223372036854775808.0) return INT64_MIN;
-  return (int64_t)x;
-}
-
-int64_t bucket_pos(double val, double interval, double offset) { return sat_i64(std::floor((val - offset) / interval)); }
+int64_t bucket_pos(double val, double interval, double offset) { return tq_agg_sat_i64(std::floor((val - offset) / interval)); }
 
 int histogram_plan(const char *fn, const tq_column_info_t &info, const tq_agg_request &req, tq_agg_hist_plan_t *out) {
   *out = tq_agg_hist_plan_t{};
@@ -51,7 +32,7 @@ int histogram_plan(const char *fn, const tq_column_info_t &info, const tq_agg_re
   if (!std::isfinite(req.interval) || req.interval <= 0.0) return fail(TQ_ERR_INVALID, "%s: interval %g (finite, > 0)", fn, req.interval);
   if (!std::isfinite(req.offset)) return fail(TQ_ERR_INVALID, "%s: offset %g is not finite", fn, req.offset);
   double bmin = -DBL_MAX, bmax = DBL_MAX;
-  const double col_min = agg_f64(info.min_value, req.value_type), col_max = agg_f64(info.max_value, req.value_type);
+  const double col_min = tq_agg_f64(info.min_value, req.value_type), col_max = tq_agg_f64(info.max_value, req.value_type);
   if (req.has_hard_bounds) {
     if (!std::isfinite(req.hard_min) || !std::isfinite(req.hard_max))
       return fail(TQ_ERR_INVALID, "%s: hard bounds [%g, %g] are not finite", fn, req.hard_min, req.hard_max);

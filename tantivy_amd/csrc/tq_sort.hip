@@ -12,14 +12,11 @@
 //   ~doc    32 bits  ties: ascending doc id whatever the order
 // = 98 bits in two words: hi = class << 34 | value' >> 30, lo = (value' & (2^30 - 1)) << 32 | ~doc.
 //
-// select   workgroup = (query, slice of the bitmap words), query fastest in the grid; four wavefronts, each walking every
-//          fourth 64-word chunk of the slice on its own (no workgroup barrier inside the walk):
-//            1. a lane evaluates one word (docset_word), the popcounts are prefix-summed over the wavefront
-//            2. every lane expands its word's bits into the wavefront's LDS slab (13 bits per doc: word of the chunk, bit)
-//            3. the slab is read back 64 docs at a time — a lane per matching doc, whatever the words' densities —
-//               rg_row + rg_value per doc (a doc without a value loads nothing), the key
-//            4. offered to the wavefront's TopKW: once the heap is full a losing doc costs its decode and one compare
-//          then wavefronts 1..3 hand their lists to wavefront 0 through LDS (the slab's bytes), which writes the row
+// select   workgroup = (query, slice of the bitmap words), query fastest in the grid.  Assembled from the shared walk
+//          (docset_walk, tq_docset_walk.hpp: a lane per matching doc) and col_value (tq_agg_device.hpp); per doc
+//          rg_row + the value (a doc without a value loads nothing), the key, offered to the wavefront's TopKW: once the
+//          heap is full a losing doc costs its decode and one compare.
+//          Then wavefronts 1..3 hand their lists to wavefront 0 through LDS (the slab's bytes), which writes the row
 //          (one slice) or the slice's sorted list and {matches, valued matches}.
 // merge    one wavefront per query over its slices' lists; writes the row.
 // Match counts are sums of popcounts.  Plain vector stores only; nothing is written at or past a row's out_stride.
@@ -27,26 +24,16 @@
 // (its presence word) + 13 per row entry written (doc, value, flag).
 #include <algorithm>
 
+#include "tq_agg_device.hpp"
 #include "tq_column_read.hpp"
 #include "tq_common.hpp"
-#include "tq_docset_word.hpp"
+#include "tq_docset_walk.hpp"
 #include "tq_launch.h"
 
 namespace {
 
-constexpr uint32_t SO_THREADS = 256;
-constexpr uint32_t SO_WAVES = SO_THREADS / 64;
-constexpr uint32_t SO_CHUNK_WORDS = 64;                      // one word per lane
-constexpr uint32_t SO_CHUNK_DOCS = SO_CHUNK_WORDS * 32;      // slab entries per wavefront
-constexpr uint32_t SO_LDS_WORDS = SO_WAVES * SO_CHUNK_DOCS * 2u / 8u;  // 16 KB as 64-bit words
+constexpr uint32_t SO_LDS_WORDS = WALK_SLAB_ENTRIES * 2u / 8u;  // the slabs' 16 KB as 64-bit words
 static_assert(SO_LDS_WORDS >= 16u * 64u * 2u, "a wavefront's list of 1024 two-word keys fits the slab's bytes");
-
-__device__ __forceinline__ uint64_t sort_value(const TqkSortParams &p, uint32_t row) {
-  const uint32_t codec = p.col.codec;  // (uniform)
-  if (codec == TQK_COL_LINEAR) return rg_value<TQK_COL_LINEAR>(p.col, row);
-  const uint64_t n = codec == TQK_COL_BITPACKED ? rg_value<TQK_COL_BITPACKED>(p.col, row) : rg_value<TQK_COL_BLOCKWISE>(p.col, row);
-  return p.min_value + p.gcd * n;
-}
 
 // the row of one query from its sorted list: entries, padding (TQD_TERMINATED, 0, 0) up to out_stride, the count
 template <int KPL>
@@ -82,53 +69,29 @@ __device__ __forceinline__ void sort_write_row(const TqkSortParams &p, const Top
 }
 
 template <int KPL, bool OPTIONAL>
-__global__ __launch_bounds__(SO_THREADS) void sort_select_kernel(TqkSortParams p) {
+__global__ __launch_bounds__(WALK_THREADS) void sort_select_kernel(TqkSortParams p) {
   __shared__ uint64_t lds[SO_LDS_WORDS];
-  __shared__ uint32_t wave_cnt[SO_WAVES][2];
+  __shared__ uint32_t wave_cnt[WALK_WAVES][2];
   const int lane = (int)__lane_id();
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t q = blockIdx.x % p.ds.n_queries, slice = blockIdx.x / p.ds.n_queries;
-  const TqkDocsetQuery *Q = p.ds.queries + q;
-  const DocsetHead h = docset_head(Q);
   const uint32_t k = sload(p.ks + q);
   TopKW<KPL> tk;
   tk.reset(k);
-  uint16_t *const slab = reinterpret_cast<uint16_t *>(lds) + wave * SO_CHUNK_DOCS;
-  const uint64_t w0_64 = (uint64_t)slice * p.words_per_slice;
-  const uint64_t w1_64 = w0_64 + p.words_per_slice;
-  const uint32_t w0 = w0_64 < p.ds.n_words ? (uint32_t)w0_64 : p.ds.n_words;  // (a slice past the end: empty)
-  const uint32_t w1 = w1_64 < p.ds.n_words ? (uint32_t)w1_64 : p.ds.n_words;
-  uint32_t cnt = 0, valued = 0;  // cnt: per lane; valued: per wavefront
-  for (uint32_t base = w0 + wave * SO_CHUNK_WORDS; base < w1; base += SO_WAVES * SO_CHUNK_WORDS) {
-    const uint32_t w = base + (uint32_t)lane;
-    uint32_t res = w < w1 ? docset_word(Q, h, p.ds, w) : 0u;
-    const uint32_t pc = (uint32_t)__popc(res);
-    cnt += pc;
-    const uint32_t incl = wave_incl_sum(pc, lane);
-    const uint32_t total = (uint32_t)__shfl(incl, 63, 64);  // <= SO_CHUNK_DOCS
-    uint32_t at = incl - pc;
-    while (res) {
-      slab[at++] = (uint16_t)(((uint32_t)lane << 5) | (uint32_t)__builtin_ctz(res));
-      res &= res - 1u;
+  uint32_t valued = 0;  // per wavefront
+  uint32_t cnt = docset_walk(p.ds, p.ds.queries + q, slice, p.words_per_slice, reinterpret_cast<uint16_t *>(lds), wave, lane,
+                             [&](bool has, uint32_t doc) {
+    uint32_t row = 0;
+    const bool hv = has && rg_row<OPTIONAL>(p.col, doc, row);
+    uint64_t vp = 0;
+    if (hv) {
+      const uint64_t v = col_value(p.col, p.min_value, p.gcd, row);
+      vp = p.ascending ? ~v : v;
     }
-    wave_mem_fence();
-    for (uint32_t j = 0; j < total; j += 64u) {
-      const bool has = j + (uint32_t)lane < total;
-      const uint32_t e = has ? slab[j + (uint32_t)lane] : 0u;
-      const uint32_t doc = ((base + (e >> 5)) << 5) | (e & 31u);
-      uint32_t row = 0;
-      const bool hv = has && rg_row<OPTIONAL>(p.col, doc, row);
-      uint64_t vp = 0;
-      if (hv) {
-        const uint64_t v = sort_value(p, row);
-        vp = p.ascending ? ~v : v;
-      }
-      valued += (uint32_t)__popcll(__ballot(hv));
-      const uint64_t cls = hv ? 2ull : (p.nulls_first ? 3ull : 1ull);
-      tk.offer(has, (cls << 34) | (vp >> 30), ((vp & ((1ull << 30) - 1ull)) << 32) | (uint64_t)(~doc), lane);
-    }
-    wave_mem_fence();  // (the next chunk's expansion writes the slab again)
-  }
+    valued += (uint32_t)__popcll(__ballot(hv));
+    const uint64_t cls = hv ? 2ull : (p.nulls_first ? 3ull : 1ull);
+    tk.offer(has, (cls << 34) | (vp >> 30), ((vp & ((1ull << 30) - 1ull)) << 32) | (uint64_t)(~doc), lane);
+  });
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
   if (lane == 0) {
     wave_cnt[wave][0] = cnt;
@@ -136,7 +99,7 @@ __global__ __launch_bounds__(SO_THREADS) void sort_select_kernel(TqkSortParams p
   }
   // wavefronts 1..3 hand their lists to wavefront 0, one after the other, through the slab's bytes
   uint64_t *const mh = lds, *const ml = lds + KPL * 64;
-  for (uint32_t wv = 1; wv < SO_WAVES; ++wv) {
+  for (uint32_t wv = 1; wv < WALK_WAVES; ++wv) {
     __syncthreads();
     if (wave == wv) {
 #pragma unroll
@@ -158,7 +121,7 @@ __global__ __launch_bounds__(SO_THREADS) void sort_select_kernel(TqkSortParams p
   }
   if (wave != 0u) return;
   uint32_t matches = 0, with_value = 0;
-  for (uint32_t v = 0; v < SO_WAVES; ++v) {
+  for (uint32_t v = 0; v < WALK_WAVES; ++v) {
     matches += wave_cnt[v][0];
     with_value += wave_cnt[v][1];
   }
@@ -204,7 +167,7 @@ __global__ __launch_bounds__(64) void sort_merge_kernel(TqkSortParams p) {
 
 template <int KPL>
 void select_launch(const TqkSortParams &p, hipStream_t st) {
-  const dim3 grid(p.ds.n_queries * p.n_slices), block(SO_THREADS);
+  const dim3 grid(p.ds.n_queries * p.n_slices), block(WALK_THREADS);
   if (p.col.present)
     sort_select_kernel<KPL, true><<<grid, block, 0, st>>>(p);
   else
@@ -213,7 +176,7 @@ void select_launch(const TqkSortParams &p, hipStream_t st) {
 
 }  // namespace
 
-uint32_t tqk_sort_step_words() { return SO_WAVES * SO_CHUNK_WORDS; }
+uint32_t tqk_sort_step_words() { return WALK_STEP_WORDS; }
 
 hipError_t tqk_launch_sort_select(const TqkSortParams &p, int kpl, hipStream_t st) {
   if (!p.ds.n_queries || !p.n_slices) return hipSuccess;
