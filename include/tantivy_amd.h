@@ -1172,6 +1172,99 @@ void tq_agg_terms_sub_lds_capacities(uint32_t out[2]);
  * count of 2^32 or more or a sum of 2^96 or more; TQ_ERR_UNSUPPORTED: SUM or AVG of TQ_VALUE_F64. */
 int tq_agg_terms_metric_image(const tq_agg_bucket_stats_t *rec, uint32_t value_type, uint32_t metric, uint64_t out[2]);
 
+/* ---- range aggregation: doc counts and a metric column's stats per range of a fast field ----
+ * replaces a `range` bucket aggregation over a resident u64 column, alone or with ONE stats / avg / min / max / sum /
+ * value_count sub-aggregation ("how many of +body:error per latency band <10 / 10-100 / 100-1000 / >=1000 ms, and the avg of
+ * bytes in each"; src/aggregation/bucket/range.rs:276-305 collect, :431-437 get_bucket_pos, :451-473 to_u64_range, :477-519
+ * extend_validate_ranges; src/aggregation/mod.rs:394-402 f64_to_fastfield_u64).  One pass over every query's match bits,
+ * no doc set written, no f64 on the device: the request's bounds are converted into the column's u64 space once, on the
+ * host, and u64 values are compared.
+ *
+ * tq_agg_range_plan is the host-only part (no device): the request's ranges as BUCKETS [start, end) of the u64 space, in
+ * bucket order.  A bound converts as the reference's `as` casts do, saturating: TQ_VALUE_U64 (also Bool) negatives -> 0,
+ * >= 2^64 -> UINT64_MAX, else truncated; TQ_VALUE_I64 (also DateTime, nanoseconds) saturated to i64, then ^ 1 << 63;
+ * TQ_VALUE_F64 the monotone image of its bits; no `from`: 0, no `to`: UINT64_MAX.  Then extend_validate_ranges: a stable
+ * sort by start, a bucket [0, first start) in front unless the first start is 0, a bucket [last end, UINT64_MAX) behind
+ * unless the last end is UINT64_MAX, every hole between neighbours filled.  `source` of a bucket is the index of the
+ * caller's range it came from (custom keys stay the caller's, found through it), UINT32_MAX for an inserted bucket.
+ * out_buckets holds `cap` entries; *out_n_buckets is written whenever the plan exists, also when cap is too small.
+ * TQ_ERR_INVALID, in this order: a null argument, n_ranges == 0 (the reference indexes [0] and panics), value_type above
+ * TQ_VALUE_F64, non-zero reserved bytes, a NaN bound, a range whose converted start is above its converted end (named; the
+ * reference takes it and then searches a list that is no longer sorted), neighbours that overlap — end > next start — (both
+ * named), cap below the plan's buckets.  TQ_ERR_UNSUPPORTED naming the count: more than TQ_AGG_RANGE_MAX_BUCKETS buckets.
+ *
+ * A value falls into THE LAST BUCKET WHOSE START IS <= THE VALUE (tq_agg_range_bucket_of: the code the kernel runs, a
+ * branch-free search whose trip count depends on n alone).  For strictly increasing starts that is the reference's
+ * binary_search_by_key(..).unwrap_or_else(|p| p - 1); UINT64_MAX falls into the last bucket, as in the reference's release
+ * build.  An EMPTY range (start == end after conversion: 0.1 .. 0.2 on an integer column) shares its start with its
+ * successor and counts nothing — what [s, s) contains; the reference's count there depends on which of the equal elements
+ * its binary search happens to meet.
+ *
+ * tq_agg_range_batch: host outputs, blocking.  metric == NULL: doc counts alone.
+ *   out_stats         one tq_agg_stats_t per query, tq_agg_batch's record of column A bit for bit; in_bounds == count (every
+ *                     doc with a value has a bucket), out_of_range always 0
+ *   out_counts        row q = out_counts + q * bucket_stride: entry i = the alive matching docs with a value in A in bucket i
+ *   out_bucket_stats  with a metric alone; row q = out_bucket_stats + q * bucket_stride: entry i = the record of the metric
+ *                     column B over exactly the docs counted in bucket i, by tq_agg_sub_batch's rule (count = those with a
+ *                     value in B, min / max in B's u64 space, the exact 128-bit sum; TQ_VALUE_F64: both sum words 0).  B may
+ *                     be A
+ * Entries [0, n_buckets) of a row are written and NOTHING else.  Integer atomics only: the same call gives the same bytes.
+ * Refused before any launch, the segment stays usable: what the plan refuses; TQ_ERR_INVALID for a column that is not live,
+ * a metric column that is not live, a metric value_type above TQ_VALUE_F64 or non-zero reserved bytes of it, bucket_stride
+ * < n_buckets, a null out_counts, a null out_bucket_stats with a metric.  Query shapes, options ("docset_trees",
+ * "docset_temp_lists", "agg_slices", "agg_lds_buckets"), sub-batches, the sloppy-phrase verdict and the "query N" texts are
+ * tq_agg_batch's under this function's name.
+ * Launches: tq_agg_batch's (tq_agg_sub_batch's with a metric) with agg_range_kernel (tq_agg_range.hip) as the aggregation
+ * launch; in front of them the starts go up through a pinned staging buffer, once per call, and every workgroup copies
+ * them into LDS.  Counts alone: a uint32_t LDS table when n_buckets <= "agg_lds_buckets", else atomics on the query's row.
+ * With a metric: the 40-byte LDS table when n_buckets <= min("agg_lds_buckets", tq_agg_range_lds_capacities' large
+ * capacity), else the query's row and records.
+ * Afterwards tq_last_batch_match_counts gives `matches`, kernel_mask = TQ_KERNEL_AGG_RANGE (| TQ_KERNEL_DOCSET_TREE |
+ * TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = tq_agg_batch's for column A with this n_buckets
+ *                     + 8 x n_buckets per call (the starts)
+ *                     + with a metric: 8 per bucketed doc with a value in B
+ *                                    + 8 per bucketed doc of a TQ_CARD_OPTIONAL B (its presence word)
+ *                                    + 40 x n_buckets per query.
+ * Not served: several metric columns, sibling or nested bucket aggregations, `keyed`, DateTime key formatting (keys are the
+ * caller's), `missing`, F64 sums, multivalued columns, more than TQ_AGG_RANGE_MAX_BUCKETS buckets. */
+#define TQ_AGG_RANGE_MAX_BUCKETS 1024u
+typedef struct tq_agg_range_t {
+  double from, to;         /* read when has_from / has_to; the column's typed space (DateTime: nanoseconds) */
+  uint8_t has_from, has_to; /* 0 / 1 */
+  uint8_t reserved[6];     /* zero */
+} tq_agg_range_t; /* 24 bytes */
+typedef struct tq_agg_range_request {
+  uint32_t column;     /* bucket column A: a handle of tq_column_upload (tq_agg_range_plan does not read it) */
+  uint8_t value_type;  /* tq_value_type of A */
+  uint8_t reserved[3]; /* zero */
+  uint32_t n_ranges;
+  uint32_t reserved2;  /* zero */
+  const tq_agg_range_t *ranges;
+} tq_agg_range_request; /* 24 bytes */
+typedef struct tq_agg_range_bucket_t {
+  uint64_t start, end; /* [start, end) in the column's u64 space */
+  uint32_t source;     /* index into the request's ranges; UINT32_MAX: inserted by the plan */
+  uint32_t reserved;
+} tq_agg_range_bucket_t; /* 24 bytes */
+int tq_agg_range_plan(const tq_agg_range_request *req, tq_agg_range_bucket_t *out_buckets, uint32_t cap, uint32_t *out_n_buckets);
+/* The bucket of `value` among n buckets with these starts (non-decreasing, starts[0] == 0): the last start <= value.  Host
+ * only; starts == NULL or n == 0: 0. */
+uint32_t tq_agg_range_bucket_of(const uint64_t *starts, uint32_t n, uint64_t value);
+int tq_agg_range_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_range_request *req,
+                       const tq_agg_metric_request *metric, tq_agg_stats_t *out_stats, uint32_t *out_counts,
+                       tq_agg_bucket_stats_t *out_bucket_stats, uint32_t bucket_stride);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream), no host synchronisation.  The call itself
+ * zeroes what it accumulates into: the same buffers may be used again. */
+int tq_agg_range_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_range_request *req,
+                              const tq_agg_metric_request *metric, tq_agg_stats_t *d_out_stats, uint32_t *d_out_counts,
+                              tq_agg_bucket_stats_t *d_out_bucket_stats, uint32_t bucket_stride, void *hip_stream);
+/* The 40-byte LDS tables' capacities in buckets of the two metric instantiations of agg_range_kernel: out[0] the small one,
+ * out[1] the large one (1 024 records, 1 024 starts and the walk's slabs are exactly the static 64 KB); with a metric, more
+ * than min("agg_lds_buckets", out[1]) buckets are accumulated in global memory.  Counts alone fit LDS up to
+ * TQ_AGG_RANGE_MAX_BUCKETS. */
+void tq_agg_range_lds_capacities(uint32_t out[2]);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -1214,6 +1307,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_AGG_SUB 0x200000u    /* agg_sub_kernel (tq_agg_sub_batch*: the histogram with a metric column's stats per bucket) */
 #define TQ_KERNEL_AGG_TERMS 0x400000u  /* agg_terms_count_kernel / agg_terms_select_kernel (tq_agg_terms_batch*: the top values of a column by doc count) */
 #define TQ_KERNEL_AGG_TERMS_SUB 0x800000u /* agg_terms_sub_count_kernel / agg_terms_sub_select_kernel (tq_agg_terms_sub_batch*: a metric column's stats per key, order by it) */
+#define TQ_KERNEL_AGG_RANGE 0x1000000u /* agg_range_kernel (tq_agg_range_batch*: doc counts and a metric column's stats per range of a column) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py
@@ -1312,7 +1406,7 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        machine, no slice below 1024 words), 1 = every query's row is written by its one workgroup and no merge is
  *        launched, 2..256 = forced (a slice past the last word is empty).  Results do not depend on it,
  *        "agg_slices" (0..256, default 0; any other value: TQ_ERR_INVALID): tq_agg_batch*, tq_agg_sub_batch*,
- *        tq_agg_terms_batch*, tq_agg_terms_sub_batch* — slices of the segment's
+ *        tq_agg_terms_batch*, tq_agg_terms_sub_batch*, tq_agg_range_batch* — slices of the segment's
  *        bitmap words per query, one aggregation workgroup each; 0 = the host chooses as for "sort_slices", 1..256 =
  *        forced (a slice past the last word is empty).  Results do not depend on it,
  *        "agg_lds_buckets" (0..8192 = the kernel's LDS capacity, default 8192; any other value: TQ_ERR_INVALID):
@@ -1321,7 +1415,8 @@ int tq_segment_get_stats(tq_segment *seg, tq_segment_stats *out);
  *        an atomic add on the query's row, several times slower on dense queries.  tq_agg_sub_batch*: min(the option,
  *        tq_agg_sub_lds_capacities' large capacity); tq_agg_terms_batch*: min(the option, tq_agg_terms_lds_capacities'
  *        large capacity) keys; tq_agg_terms_sub_batch*: min(the option, tq_agg_terms_sub_lds_capacities' large capacity)
- *        keys.  Results do not depend on it,
+ *        keys; tq_agg_range_batch*: the option for counts alone, min(the option, tq_agg_range_lds_capacities' large
+ *        capacity) with a metric.  Results do not depend on it,
  *        "ashare_min_batch" (default 16; 512 until round 6): intersections take the shared leader-major launch
  *        (TQ_KERNEL_ASHARE) when at least this many queries of the batch qualify for it — below, its
  *        two launches and per-task set-up cost more than sharing the leader blocks saves (round 6, synchronous

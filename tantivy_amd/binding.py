@@ -67,8 +67,10 @@ KERNEL_AGG = 0x100000
 KERNEL_AGG_SUB = 0x200000
 KERNEL_AGG_TERMS = 0x400000
 KERNEL_AGG_TERMS_SUB = 0x800000
+KERNEL_AGG_RANGE = 0x1000000
 VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
 AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
+AGG_RANGE_MAX_BUCKETS = 1024  # TQ_AGG_RANGE_MAX_BUCKETS
 SORT_DESC, SORT_ASC = 0, 1      # tq_sort_order (Order::Desc = Natural, Order::Asc = ReverseNoneLower with NULLS_LAST)
 NULLS_LAST, NULLS_FIRST = 0, 1  # tq_sort_nulls (NULLS_FIRST: Reverse / NaturalNoneHigher)
 MAX_K = 1024  # TQ_MAX_K
@@ -78,7 +80,7 @@ KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
                 0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub",
-                0x400000: "agg_terms", 0x800000: "agg_terms_sub"}
+                0x400000: "agg_terms", 0x800000: "agg_terms_sub", 0x1000000: "agg_range"}
 
 
 def kernel_names(mask):
@@ -176,6 +178,8 @@ EXPORTS = [
     "tq_agg_terms_plan", "tq_agg_terms_batch", "tq_agg_terms_batch_device", "tq_agg_terms_lds_capacities",
     "tq_agg_terms_max_size",
     "tq_agg_terms_sub_batch", "tq_agg_terms_sub_batch_device", "tq_agg_terms_sub_lds_capacities", "tq_agg_terms_metric_image",
+    "tq_agg_range_plan", "tq_agg_range_bucket_of", "tq_agg_range_batch", "tq_agg_range_batch_device",
+    "tq_agg_range_lds_capacities",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -332,6 +336,135 @@ def merge_bucket_stats(parts):
     for o in out:
         o["sum_lo"], o["sum_hi"] = o["sum"] & ((1 << 64) - 1), o["sum"] >> 64
     return [float(pos) * interval + offset for pos in range(lo, hi)], out
+
+
+class TqAggRange(C.Structure):  # tq_agg_range_t
+    _fields_ = [("from_", C.c_double), ("to", C.c_double), ("has_from", C.c_uint8), ("has_to", C.c_uint8),
+                ("reserved", C.c_uint8 * 6)]
+
+
+class TqAggRangeRequest(C.Structure):  # tq_agg_range_request
+    _fields_ = [("column", C.c_uint32), ("value_type", C.c_uint8), ("reserved", C.c_uint8 * 3), ("n_ranges", C.c_uint32),
+                ("reserved2", C.c_uint32), ("ranges", C.POINTER(TqAggRange))]
+
+
+class TqAggRangeBucket(C.Structure):  # tq_agg_range_bucket_t
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("source", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+U64_MAX = (1 << 64) - 1
+RANGE_INSERTED = 0xFFFFFFFF  # tq_agg_range_bucket_t.source of a bucket the plan inserted
+
+
+def _agg_range_request(column, value_type, ranges):
+    """ranges: (from, to) pairs or dicts with "from" / "to"; None (or a missing key) = that end is open.  -> (request, the
+    array it points to: keep it alive)."""
+    arr = (TqAggRange * max(1, len(ranges)))()
+    for i, r in enumerate(ranges):
+        lo, hi = (r.get("from"), r.get("to")) if isinstance(r, dict) else r
+        if lo is not None:
+            arr[i].from_, arr[i].has_from = float(lo), 1
+        if hi is not None:
+            arr[i].to, arr[i].has_to = float(hi), 1
+    req = TqAggRangeRequest(column=int(column), value_type=int(value_type), n_ranges=len(ranges))
+    req.ranges = C.cast(arr, C.POINTER(TqAggRange))
+    return req, arr
+
+
+def _agg_range_plan(req):
+    out = (TqAggRangeBucket * AGG_RANGE_MAX_BUCKETS)()
+    n = C.c_uint32(0)
+    rc = lib().tq_agg_range_plan(C.byref(req), out, AGG_RANGE_MAX_BUCKETS, C.byref(n))
+    return rc, [{"start": int(b.start), "end": int(b.end), "source": None if b.source == RANGE_INSERTED else int(b.source)}
+                for b in out[:n.value]]
+
+
+def agg_range_plan(value_type, ranges):
+    """tq_agg_range_plan: the ranges of a request as buckets [start, end) of the column's u64 space, in bucket order, the
+    whole space covered (extend_validate_ranges).  ranges as for DeviceIndex.raw_agg_range.  -> a list of {"start", "end",
+    "source"}: source = the index of the caller's range, None for a bucket the plan inserted.  Needs no device."""
+    req, keep = _agg_range_request(0, value_type, ranges)
+    rc, plan = _agg_range_plan(req)
+    _check(rc)
+    return plan
+
+
+def agg_range_bucket_of(starts, value):
+    """tq_agg_range_bucket_of: the bucket of a u64-space value among buckets with these starts — the last start <= value;
+    the code the kernel runs.  Needs no device."""
+    a = np.ascontiguousarray(starts, dtype=np.uint64)
+    return int(lib().tq_agg_range_bucket_of(a.ctypes.data, a.size, int(value)))
+
+
+def agg_range_lds_capacities():
+    """tq_agg_range_lds_capacities: the record tables' capacities in buckets of agg_range_kernel's (small, large) metric
+    instantiation.  Needs no device."""
+    out = (C.c_uint32 * 2)()
+    lib().tq_agg_range_lds_capacities(out)
+    return int(out[0]), int(out[1])
+
+
+def merge_ranges(parts):
+    """The segments' range rows of ONE query and ONE request: parts = [(plan, counts, records or None)] as raw_agg_range
+    returns them (the query's rows).  The plans must be equal (the plan depends on the request alone).  Counts add; records
+    merge by merge_bucket_stats' rule.  -> (plan, counts: list of ints, records: list of dicts agg_stats_finalize takes, or
+    None without a metric).  Host only."""
+    plan = parts[0][0]
+    assert all(p == plan for p, _, _ in parts), "the segments' plans differ"
+    counts = [0] * len(plan)
+    with_recs = parts[0][2] is not None
+    recs = [{"count": 0, "min_value": U64_MAX, "max_value": 0, "sum": 0} for _ in plan] if with_recs else None
+    for _, c, r in parts:
+        for i in range(len(plan)):
+            counts[i] += int(c[i])
+            if with_recs:
+                o = recs[i]
+                o["count"] += int(r[i]["count"])
+                o["sum"] += int(r[i]["sum_lo"]) + (int(r[i]["sum_hi"]) << 64)
+                o["min_value"] = min(o["min_value"], int(r[i]["min_value"]))
+                o["max_value"] = max(o["max_value"], int(r[i]["max_value"]))
+    for o in recs or []:
+        o["sum_lo"], o["sum_hi"] = o["sum"] & U64_MAX, o["sum"] >> 64
+    return plan, counts, recs
+
+
+def f64_display(x):
+    """Rust's Display of an f64: the shortest digits that round-trip, never an exponent, no trailing ".0" ("10", "0.1",
+    "-0", "1000000000000000000000", "inf", "NaN").  Python's repr has the same digits but an exponent from 1e16 on."""
+    import decimal
+
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "inf" if x > 0 else "-inf"
+    t = format(decimal.Decimal(repr(x)), "f")
+    return t.rstrip("0").rstrip(".") if "." in t else t
+
+
+def range_key(bucket, value_type):
+    """range_to_string (bucket/range.rs:521-543) of a plan's bucket for U64 / I64 / F64 columns: "*" at an open end, else
+    f64_from_fastfield_u64 of the bound in Rust's Display.  DateTime keys are the caller's."""
+    lo = "*" if bucket["start"] == 0 else f64_display(float(agg_value_from_u64(bucket["start"], value_type)))
+    hi = "*" if bucket["end"] == U64_MAX else f64_display(float(agg_value_from_u64(bucket["end"], value_type)))
+    return "%s-%s" % (lo, hi)
+
+
+def range_finalize(plan, counts, records, value_type, metric_value_type=None, keys=None):
+    """The final entries of one query's (merged) range rows, in bucket order: {"key", "doc_count", "from", "to"[, "stats"]}.
+    from / to = f64_from_fastfield_u64(start / end), None at 0 / UINT64_MAX; key = keys[source] where the caller named the
+    range (keys: a list parallel to the request's ranges, None entries allowed), else range_key; stats =
+    agg_stats_finalize(record, metric_value_type) when records is given."""
+    out = []
+    for i, b in enumerate(plan):
+        named = keys[b["source"]] if keys is not None and b["source"] is not None else None
+        e = {"key": named if named is not None else range_key(b, value_type), "doc_count": int(counts[i]),
+             "from": None if b["start"] == 0 else float(agg_value_from_u64(b["start"], value_type)),
+             "to": None if b["end"] == U64_MAX else float(agg_value_from_u64(b["end"], value_type))}
+        if records is not None:
+            e["stats"] = agg_stats_finalize(records[i], metric_value_type)
+        out.append(e)
+    return out
 
 
 class TqAggTermsRequest(C.Structure):  # tq_agg_terms_request
@@ -654,6 +787,15 @@ def lib():
     L.tq_agg_terms_sub_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
     L.tq_agg_terms_sub_lds_capacities.restype = None
     L.tq_agg_terms_metric_image.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.tq_agg_range_plan.argtypes = [C.POINTER(TqAggRangeRequest), C.POINTER(TqAggRangeBucket), C.c_uint32, u32p]
+    L.tq_agg_range_bucket_of.argtypes = [vp, C.c_uint32, C.c_uint64]
+    L.tq_agg_range_bucket_of.restype = C.c_uint32
+    L.tq_agg_range_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRangeRequest),
+                                     C.POINTER(TqAggMetricRequest), vp, u32p, vp, C.c_uint32]
+    L.tq_agg_range_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggRangeRequest),
+                                            C.POINTER(TqAggMetricRequest), vp, vp, vp, C.c_uint32, vp]
+    L.tq_agg_range_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
+    L.tq_agg_range_lds_capacities.restype = None
     L.tq_agg_terms_max_size.argtypes = []
     L.tq_agg_terms_max_size.restype = C.c_uint32
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
@@ -1714,6 +1856,62 @@ class DeviceIndex:
                                              d_stats.data_ptr(), d_buckets.data_ptr() if d_buckets is not None else None,
                                              d_bucket_stats.data_ptr() if d_bucket_stats is not None else None, int(stride),
                                              C.c_void_p(stream) if stream else None)
+
+    # ---- range aggregation (tq_agg_range.cpp, tq_agg_range.hip)
+    def raw_agg_range(self, queries, column, value_type, ranges, metric_column=None, metric_value_type=None, segment_ord=0,
+                      device=False, stride=None):
+        """Direct tq_agg_range_batch on one segment: the query tuples of raw_docset; ranges = (from, to) pairs or dicts with
+        "from" / "to", None = open; metric_column = None: doc counts alone.  -> (stats: structured array [n] of
+        AGG_STATS_DTYPE, counts [n, n_buckets] uint32, bucket_stats [n, n_buckets] of AGG_BUCKET_STATS_DTYPE or None, plan of
+        agg_range_plan).  stride: the stride of both kinds of rows in the call (default n_buckets); device=True: through
+        tq_agg_range_batch_device into torch tensors on the segment's GPU."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req, keep_ranges = _agg_range_request(column, value_type, ranges)
+        with_metric = metric_column is not None
+        metric = TqAggMetricRequest(column=int(metric_column), value_type=int(metric_value_type or 0)) if with_metric else None
+        mref = C.byref(metric) if with_metric else None
+        _, plan = _agg_range_plan(req)  # (the call makes the same plan; a refusal comes from the call, under its name)
+        nb = len(plan)
+        stride = nb if stride is None else int(stride)
+        stats = np.zeros(max(1, n), AGG_STATS_DTYPE)
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_stats = torch.full((max(1, n), 8), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_rows = torch.full((max(1, n), max(1, stride)), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            d_recs = torch.full((max(1, n), max(1, stride) * 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_range_batch_device(self.segment_raw(segment_ord), qs, n, C.byref(req), mref, d_stats.data_ptr(),
+                                                   d_rows.data_ptr(), d_recs.data_ptr(), stride, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            stats = d_stats.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_STATS_DTYPE)
+            rows = d_rows.cpu().numpy().view(np.uint32)
+            recs = d_recs.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_BUCKET_STATS_DTYPE).reshape(max(1, n), max(1, stride))
+        else:
+            rows = np.full((max(1, n), max(1, stride)), 0xDEADBEEF, np.uint32)
+            recs = np.full((max(1, n), max(1, stride) * 5), 0xDEADBEEF, np.uint64)
+            _check(lib().tq_agg_range_batch(self.segment_raw(segment_ord), qs, n, C.byref(req), mref, stats.ctypes.data,
+                                            _u32(rows), recs.ctypes.data, stride))
+            recs = recs.reshape(-1).view(AGG_BUCKET_STATS_DTYPE).reshape(max(1, n), max(1, stride))
+        return stats[:n], rows[:n, :nb], recs[:n, :nb] if with_metric else None, plan
+
+    def raw_agg_range_device(self, queries, column, value_type, ranges, metric_column, metric_value_type, stride, d_stats, d_counts,
+                             d_bucket_stats, segment_ord=0, stream=None):
+        """Direct tq_agg_range_batch_device: raw_agg_sub_device's tensors (d_bucket_stats None without a metric) on the
+        segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req, keep_ranges = _agg_range_request(column, value_type, ranges)
+        metric = None
+        if metric_column is not None:
+            metric = TqAggMetricRequest(column=int(metric_column), value_type=int(metric_value_type or 0))
+        return lib().tq_agg_range_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req),
+                                               C.byref(metric) if metric is not None else None, d_stats.data_ptr(),
+                                               d_counts.data_ptr() if d_counts is not None else None,
+                                               d_bucket_stats.data_ptr() if d_bucket_stats is not None else None, int(stride),
+                                               C.c_void_p(stream) if stream else None)
 
     # ---- terms aggregation (tq_agg_terms.cpp, tq_agg_terms.hip)
     def agg_terms_plan(self, column, order=TERMS_COUNT_DESC, segment_size=10, segment_ord=0):

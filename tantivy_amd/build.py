@@ -37,6 +37,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_agg_terms.cpp"),
     os.path.join(HERE, "csrc", "tq_agg_terms_sub.hip"),
     os.path.join(HERE, "csrc", "tq_agg_terms_sub.cpp"),
+    os.path.join(HERE, "csrc", "tq_agg_range.hip"),
+    os.path.join(HERE, "csrc", "tq_agg_range.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -68,6 +70,7 @@ HEADERS = [
     os.path.join(HERE, "csrc", "tq_agg_value.hpp"),
     os.path.join(HERE, "csrc", "tq_agg_device.hpp"),
     os.path.join(HERE, "csrc", "tq_agg_terms_select.hpp"),
+    os.path.join(HERE, "csrc", "tq_agg_range_search.hpp"),
     os.path.join(HERE, "csrc", "tq_docset_word.hpp"),
     os.path.join(HERE, "csrc", "tq_docset_walk.hpp"),
     os.path.join(HERE, "csrc", "tq_device.h"),
@@ -111,11 +114,12 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "agg_terms_count_kernel": "tq_agg_terms.hip", "agg_terms_select_kernel": "tq_agg_terms.hip",
                 "agg_terms_init_kernel": "tq_agg_terms.hip",
                 "agg_terms_sub_count_kernel": "tq_agg_terms_sub.hip", "agg_terms_sub_select_kernel": "tq_agg_terms_sub.hip",
-                "agg_terms_sub_init_kernel": "tq_agg_terms_sub.hip"}
-# the headers the five doc-set consumers (sort, the four aggregations) are assembled from: hashed with any of them
-WALK_FILES = {"tq_sort.hip", "tq_agg.hip", "tq_agg_sub.hip", "tq_agg_terms.hip", "tq_agg_terms_sub.hip"}
+                "agg_terms_sub_init_kernel": "tq_agg_terms_sub.hip",
+                "agg_range_kernel": "tq_agg_range.hip"}
+# the headers the six doc-set consumers (sort, the five aggregations) are assembled from: hashed with any of them
+WALK_FILES = {"tq_sort.hip", "tq_agg.hip", "tq_agg_sub.hip", "tq_agg_terms.hip", "tq_agg_terms_sub.hip", "tq_agg_range.hip"}
 WALK_HEADERS = {"tq_docset_word.hpp", "tq_docset_walk.hpp", "tq_column_read.hpp", "tq_agg_value.hpp", "tq_agg_device.hpp",
-                "tq_agg_terms_select.hpp", "tq_agg_metric_image.hpp"}
+                "tq_agg_terms_select.hpp", "tq_agg_metric_image.hpp", "tq_agg_range_search.hpp"}
 
 
 def kernel_hash(kernel_names, read=None):

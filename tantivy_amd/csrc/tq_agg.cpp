@@ -117,45 +117,56 @@ int agg_host_call(tq_segment *s, const char *fn, const tq_query *queries, uint32
     int rc = check_agg_call(s, fn, req, out_buckets, bucket_stride, &plan);
     if (rc == TQ_OK && metric) rc = check_metric(s, fn, req, metric, out_bucket_stats, plan);
     if (rc != TQ_OK || n_queries == 0) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    rc = wait_segment_idle(s);  // (the buffer below may be a batch in flight's)
-    if (rc != TQ_OK) return rc;
-    // on the device: [records | rows of n_buckets entries | with a metric: bucket records, n_buckets per query], copied
-    // back row by row into the caller's stride
-    const size_t stats_bytes = (size_t)n_queries * sizeof(tq_agg_stats_t);
-    const size_t row_bytes = (size_t)plan.n_buckets * sizeof(uint32_t);
-    const size_t rec_at = (stats_bytes + (size_t)n_queries * row_bytes + 7u) & ~(size_t)7u;
-    const size_t rec_row_bytes = metric ? (size_t)plan.n_buckets * sizeof(tq_agg_bucket_stats_t) : 0u;
-    rc = s->d_agg_rows.ensure(rec_at + (size_t)n_queries * rec_row_bytes + 64u);
-    if (rc != TQ_OK) return rc;
-    uint8_t *const base = (uint8_t *)s->d_agg_rows.p;
-    AggSpec spec{req->column, req->value_type, plan, req->interval, req->offset, plan.n_buckets, (tq_agg_stats_t *)base,
-                 plan.n_buckets ? (uint32_t *)(base + stats_bytes) : nullptr};
+    AggSpec spec{req->column, req->value_type, plan, req->interval, req->offset, 0u, nullptr, nullptr};
     spec.metric = metric;
-    spec.d_bucket_stats = rec_row_bytes ? (tq_agg_bucket_stats_t *)(base + rec_at) : nullptr;
-    DocsetCall call(fn, DocsetConsumer::kAgg);
-    call.agg = &spec;
-    rc = docset_batch(s, queries, n_queries, call);
-    if (rc != TQ_OK) return rc;
-    hipStream_t st = s->stream;
-    HIP_TRY(hipMemcpyAsync(out_stats, base, stats_bytes, hipMemcpyDeviceToHost, st));
-    if (plan.n_buckets && bucket_stride == plan.n_buckets)
-      HIP_TRY(hipMemcpyAsync(out_buckets, base + stats_bytes, (size_t)n_queries * row_bytes, hipMemcpyDeviceToHost, st));
-    else if (plan.n_buckets)
-      HIP_TRY(hipMemcpy2DAsync(out_buckets, (size_t)bucket_stride * sizeof(uint32_t), base + stats_bytes, row_bytes, row_bytes, n_queries,
-                               hipMemcpyDeviceToHost, st));
-    if (rec_row_bytes)
-      HIP_TRY(hipMemcpy2DAsync(out_bucket_stats, (size_t)bucket_stride * sizeof(tq_agg_bucket_stats_t), base + rec_at, rec_row_bytes,
-                               rec_row_bytes, n_queries, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (s->d_agg_rows.cap > ((size_t)256 << 20)) s->d_agg_rows.release();  // (a large result is not kept as scratch)
-    return slop_overflow_readback(s, fn);  // a sloppy phrase whose carried list went over the cap is reported; the other rows are valid
+    return agg_host_run(s, fn, queries, n_queries, spec, out_stats, out_buckets, out_bucket_stats, bucket_stride);
   } catch (const std::exception &e) {
     return fail(TQ_ERR_HIP, "%s: %s", fn, e.what());
   }
 }
 
 }  // namespace
+
+// The host-output variant of a checked call whose rows are plan.n_buckets entries per query (the histogram's, the range
+// aggregation's): the segment is locked, spec holds everything but the outputs.
+int agg_host_run(tq_segment *s, const char *fn, const tq_query *queries, uint32_t n_queries, AggSpec &spec, tq_agg_stats_t *out_stats,
+                 uint32_t *out_buckets, tq_agg_bucket_stats_t *out_bucket_stats, uint32_t bucket_stride) {
+  const tq_agg_hist_plan_t &plan = spec.plan;
+  const tq_agg_metric_request *const metric = spec.metric;
+  HIP_TRY(hipSetDevice(s->device));
+  int rc = wait_segment_idle(s);  // (the buffer below may be a batch in flight's)
+  if (rc != TQ_OK) return rc;
+  // on the device: [records | rows of n_buckets entries | with a metric: bucket records, n_buckets per query], copied
+  // back row by row into the caller's stride
+  const size_t stats_bytes = (size_t)n_queries * sizeof(tq_agg_stats_t);
+  const size_t row_bytes = (size_t)plan.n_buckets * sizeof(uint32_t);
+  const size_t rec_at = (stats_bytes + (size_t)n_queries * row_bytes + 7u) & ~(size_t)7u;
+  const size_t rec_row_bytes = metric ? (size_t)plan.n_buckets * sizeof(tq_agg_bucket_stats_t) : 0u;
+  rc = s->d_agg_rows.ensure(rec_at + (size_t)n_queries * rec_row_bytes + 64u);
+  if (rc != TQ_OK) return rc;
+  uint8_t *const base = (uint8_t *)s->d_agg_rows.p;
+  spec.bucket_stride = plan.n_buckets;
+  spec.d_stats = (tq_agg_stats_t *)base;
+  spec.d_buckets = plan.n_buckets ? (uint32_t *)(base + stats_bytes) : nullptr;
+  spec.d_bucket_stats = rec_row_bytes ? (tq_agg_bucket_stats_t *)(base + rec_at) : nullptr;
+  DocsetCall call(fn, DocsetConsumer::kAgg);
+  call.agg = &spec;
+  rc = docset_batch(s, queries, n_queries, call);
+  if (rc != TQ_OK) return rc;
+  hipStream_t st = s->stream;
+  HIP_TRY(hipMemcpyAsync(out_stats, base, stats_bytes, hipMemcpyDeviceToHost, st));
+  if (plan.n_buckets && bucket_stride == plan.n_buckets)
+    HIP_TRY(hipMemcpyAsync(out_buckets, base + stats_bytes, (size_t)n_queries * row_bytes, hipMemcpyDeviceToHost, st));
+  else if (plan.n_buckets)
+    HIP_TRY(hipMemcpy2DAsync(out_buckets, (size_t)bucket_stride * sizeof(uint32_t), base + stats_bytes, row_bytes, row_bytes, n_queries,
+                             hipMemcpyDeviceToHost, st));
+  if (rec_row_bytes)
+    HIP_TRY(hipMemcpy2DAsync(out_bucket_stats, (size_t)bucket_stride * sizeof(tq_agg_bucket_stats_t), base + rec_at, rec_row_bytes,
+                             rec_row_bytes, n_queries, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (s->d_agg_rows.cap > ((size_t)256 << 20)) s->d_agg_rows.release();  // (a large result is not kept as scratch)
+  return slop_overflow_readback(s, fn);  // a sloppy phrase whose carried list went over the cap is reported; the other rows are valid
+}
 
 // what the aggregation launches add to: the totals, every query's match count, the records and bucket rows (and, with a
 // metric, the bucket records)
@@ -164,6 +175,10 @@ int agg_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, uint32_t max_s
   spec.words_per_slice = (n_words + spec.n_slices - 1u) / spec.n_slices;
   spec.optional = s->columns[spec.column].dev.present != nullptr;
   if (spec.terms) return agg_terms_prepare(s, spec, n_queries, st);
+  if (spec.range) {  // (its starts; the records and rows below are a histogram's of plan.n_buckets buckets)
+    const int rc = agg_range_prepare(s, spec, st);
+    if (rc != TQ_OK) return rc;
+  }
   s->stats.algorithmic_bytes += (uint64_t)n_queries * (sizeof(tq_agg_stats_t) + 4u * (uint64_t)spec.plan.n_buckets);
   HIP_TRY(hipMemsetAsync(s->d_match_counter, 0, (spec.metric ? 5u : 3u) * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(s->d_qmatches.p, 0, (size_t)n_queries * sizeof(uint32_t), st));
@@ -199,6 +214,7 @@ int agg_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uin
   ap.value_type = spec.value_type;
   ap.n_slices = spec.n_slices;
   ap.words_per_slice = spec.words_per_slice;
+  if (spec.range) return agg_range_launch(s, spec, ap, q0, st);  // (ap's histogram fields are not read)
   if (!spec.metric || !spec.plan.n_buckets)  // (no bucket: no bucket record either; the record alone)
     return launched(tqk_launch_agg(ap, st), "aggregation kernel");
   const tq_segment::ColumnHost &mcol = s->columns[spec.metric->column];

@@ -303,6 +303,8 @@ void tq_segment_free(tq_segment *s) {
   s->h_sort_ks.release();
   s->d_agg_rows.release();
   s->d_agg_term_rows.release();
+  s->d_agg_range_starts.release();
+  s->h_agg_range_starts.release();
   s->h_docset.release();
   s->h_stage.release();
   s->h_out.release();

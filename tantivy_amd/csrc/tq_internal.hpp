@@ -371,11 +371,14 @@ struct tq_segment {
   PinnedBuf h_sort_ks;  // ... the queries' k on their way up
   DevBuf d_agg_rows;  // aggregations (tq_agg.hip): the host variant's records and bucket rows
   DevBuf d_agg_term_rows;  // terms aggregation (tq_agg_terms.hip): the batch's count rows, n_queries x n_keys
+  DevBuf d_agg_range_starts;     // range aggregation (tq_agg_range.hip): the plan's starts, uploaded per call
+  PinnedBuf h_agg_range_starts;  // ... on their way up
   PinnedBuf h_docset;  // descriptors + scatter work list on their way up
   size_t docset_scratch_bytes() const {
     return d_docset_queries.cap + d_docset_counts.cap + d_docset_offs.cap + d_docset_partials.cap + d_docset_starts.cap +
            d_docset_docs.cap + d_docset_squeries.cap + d_docset_caches.cap + d_docset_scores.cap +
-           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap + d_agg_rows.cap + d_agg_term_rows.cap;
+           d_docset_trees.cap + d_sort_ks.cap + d_sort_partials.cap + d_sort_slice_counts.cap + d_sort_rows.cap + d_agg_rows.cap + d_agg_term_rows.cap +
+           d_agg_range_starts.cap;
   }
   DevBuf d_ashare_words, d_bshare_words;  // shared-intersection launches (run next to the shared-union one)
   DeviceScratch *dscratch = nullptr;  // partial / result lists and staging lists: the device's (tq_ctx)
@@ -1130,6 +1133,12 @@ struct AggSpec {
   const tq_agg_terms_sub_request *terms_sub = nullptr;
   tq_agg_bucket_stats_t *d_term_stats = nullptr;
   uint32_t terms_n_queries = 0;  // agg_terms_sub_prepare: the batch's queries
+  // tq_agg_range_batch* (tq_agg_range.cpp): in place of the histogram, the range request (null: none) with its plan's buckets
+  // (plan.n_buckets of them; nothing else of `plan`, interval and offset is read); counts at d_buckets, with `metric` the
+  // records at d_bucket_stats, as for a histogram.  d_range_starts: agg_range_prepare's upload of the buckets' starts
+  const tq_agg_range_request *range = nullptr;
+  std::vector<tq_agg_range_bucket_t> range_plan;
+  const uint64_t *d_range_starts = nullptr;
 };
 // One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
 // kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass
@@ -1199,6 +1208,13 @@ int agg_terms_plan_checked(const char *fn, const tq_column_info_t &info, const t
                            tq_agg_terms_plan_t *out);
 int agg_terms_check_call(tq_segment *s, const char *fn, const tq_agg_terms_request *req, uint32_t max_order, const void *keys,
                          const void *counts, uint32_t out_stride, tq_agg_terms_plan_t *plan);
+// tq_agg_range.cpp: for a spec with `range` — the starts' upload in front of agg_prepare's own work (the records and rows
+// are a histogram's), and the launch; nothing follows the last sub-batch
+int agg_range_prepare(tq_segment *s, AggSpec &spec, hipStream_t st);
+int agg_range_launch(tq_segment *s, const AggSpec &spec, const TqkAggParams &a, uint32_t q0, hipStream_t st);  // a: agg_launch's
+// tq_agg.cpp: the host-output variant of a checked call with rows of spec.plan.n_buckets entries (locked; spec without outputs)
+int agg_host_run(tq_segment *s, const char *fn, const tq_query *queries, uint32_t n_queries, AggSpec &spec, tq_agg_stats_t *out_stats,
+                 uint32_t *out_buckets, tq_agg_bucket_stats_t *out_bucket_stats, uint32_t bucket_stride);
 // tq_agg_terms_sub.cpp: what the three do for a spec with `terms_sub`
 int agg_terms_sub_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
 int agg_terms_sub_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);

@@ -508,6 +508,18 @@ hipError_t tqk_launch_agg_sub_init(TqkAggBucketStats *bucket_stats, uint32_t n_q
 hipError_t tqk_launch_agg_sub(const TqkAggSubParams &p, hipStream_t st);
 // the LDS tables' compile-time capacities in buckets: out[0] the small instantiation's, out[1] the large one's
 void tqk_agg_sub_lds_capacities(uint32_t out[2]);
+// ---- range aggregation (tq_agg_range.hip): doc counts per range of column A over a doc set and, with a metric, a record of
+// column B per range (tq_agg_range_batch*).  The ranges are the host plan's buckets; the launch takes their STARTS in the
+// column's u64 space.  tqk_launch_agg_init (and, with a metric, tqk_launch_agg_sub_init) in front, as for the histogram.
+struct TqkAggRangeParams {
+  TqkAggSubParams s;       // everything tqk_launch_agg_sub takes; of s.a the histogram's interval / offset / bounds / base_pos
+                           // are not read, 1 <= s.a.n_buckets <= 1 024; without a metric col_b and bucket_stats are not read
+                           // and s.a.totals is [3]
+  const uint64_t *starts;  // [s.a.n_buckets] non-decreasing, starts[0] == 0: a value's bucket is the last start <= it
+};
+hipError_t tqk_launch_agg_range(const TqkAggRangeParams &p, bool metric, hipStream_t st);
+// the record table's compile-time capacities in buckets (with a metric): out[0] the small instantiation's, out[1] the large one's
+void tqk_agg_range_lds_capacities(uint32_t out[2]);
 // ---- terms aggregation (tq_agg_terms.hip): doc counts per key of a column over a doc set, then the top segment_size
 // entries per query (tq_agg_terms_batch*).  tqk_launch_agg_terms_init in front; one count launch per sub-batch adds to the
 // records and to the per-query scratch rows with vector atomics; one select launch behind the last of them writes the output
