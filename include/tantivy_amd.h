@@ -1265,6 +1265,87 @@ int tq_agg_range_batch_device(tq_segment *seg, const tq_query *queries, uint32_t
  * TQ_AGG_RANGE_MAX_BUCKETS. */
 void tq_agg_range_lds_capacities(uint32_t out[2]);
 
+/* ---- terms x histogram: a (date_)histogram per key of a terms aggregation ----
+ * replaces a `terms` aggregation over a low-cardinality column T with ONE `histogram` / `date_histogram` leaf over a column
+ * H below it ("requests per hour for each status among +body:error +timestamp:[a TO b]";
+ * src/aggregation/bucket/term_agg/term_histogram.rs, the fused collector: a flat grid counts[term * num_time_buckets +
+ * bucket] and per term the docs outside hard_bounds; the general buffered path gives the same result and defines the
+ * Optional cases).  Per query of a batch, one pass over the query's match bits; no doc set is written and only the
+ * surviving keys' rows leave the device.
+ *
+ * Per query, over its alive matching docs: a doc without a value in T enters nothing (it counts in `matches` alone).  A doc
+ * with key index i = (value - min) / gcd of T counts once under key i — tq_agg_terms_batch's exact integer index, its plan
+ * (tq_agg_terms_plan on T), its four orders with ties at the cut to the ascending key, its tq_agg_terms_t record with the
+ * same meaning of every field, its out_keys / out_counts: record, keys and counts are that call's, bit for bit.  The doc is
+ * counted in cell (i, b) when it has a value in H, that value as tq_agg_batch's f64 passes the plan's effective bounds, and
+ * b = floor((val - offset) / interval) - base_pos: tq_agg_batch's arithmetic and tq_agg_histogram_plan's plan on H, hard
+ * bounds that cannot exclude a value of H dropped.  Otherwise — no value in H, or out of bounds — it is counted in the
+ * key's OUTSIDE entry.  A key's doc count is the sum of its cells plus its outside entry (the reference's in_bounds +
+ * out_of_bounds).  H may be T.
+ * For query q and returned entry j, in the order used: out_keys[q * out_stride + j], out_counts[q * out_stride + j], and the
+ * key's dense histogram row out_hist[(q * out_stride + j) * hist_stride + b], b in [0, n_buckets); bucket b has the key
+ * (base_pos + b) * interval + offset, as for tq_agg_batch.  The outside entry does not leave the device: it is the doc
+ * count minus the row's sum.
+ *
+ * tq_agg_terms_hist_plan is the host-only part (no device): the terms plan of info_t, the histogram plan of info_h, and
+ * n_cells = n_keys x (n_buckets + 1), the grid of one query — the + 1 is the outside entry, the last of each key's row, so
+ * that one index serves every doc and a key's doc count is one row sum.  n_buckets == 0 (no value of H within bounds, or H
+ * without a row) is served: every doc of a key goes to its outside entry, the keys come back with empty rows.  n_keys == 0
+ * returns records of zeros with `matches`.  TQ_ERR_INVALID: a null argument, non-zero reserved fields (the request's, the
+ * histogram half's), a histogram half with histogram != 1, what tq_agg_terms_plan and tq_agg_histogram_plan refuse;
+ * TQ_ERR_UNSUPPORTED: what those two refuse so, and n_cells > TQ_AGG_MAX_BUCKETS, naming n_keys and n_buckets (four times
+ * the reference's MAX_FUSED_GRID_BUCKETS: the dense scratch row tq_agg_terms_batch allows per query) — all under this
+ * function's name.
+ *
+ * tq_agg_terms_hist_batch: host outputs, blocking.  Of the row set q entries [0, n_returned) hold the result; the host
+ * variant writes entries [n_returned, min(segment_size, n_keys)) — keys, counts and their histogram rows' [0, n_buckets) —
+ * as zeros and nothing past them.  Refused before any launch, the segment stays usable: what the plan refuses, a column
+ * that is not live, out_stride < min(segment_size, n_keys), hist_stride < n_buckets, null outputs (TQ_ERR_INVALID).  Query
+ * shapes, options ("agg_slices", "agg_lds_buckets", "docset_trees", "docset_temp_lists"), the sloppy-phrase verdict and the
+ * message texts are tq_agg_batch's under this function's name.
+ * Launches: after the doc-set path's scatter / tree / sloppy-phrase launches, one that initialises the records and the
+ * scratch — per query a grid row of n_cells and a totals row of n_keys entries, n_queries x (n_cells + n_keys) x 4 bytes of
+ * segment scratch, never an output —, one agg_terms_hist_count_kernel launch per sub-batch (tq_agg_terms_hist.hip: the
+ * shared walk; per doc a read of T, a read of H, the f64 bucket arithmetic and one add on its cell — of a workgroup-private
+ * LDS table when n_cells <= min("agg_lds_buckets", tq_agg_terms_hist_lds_capacities' large capacity), else of the query's
+ * grid row) and, behind the last sub-batch, three: the row sums into the totals rows, agg_terms_select_kernel over them
+ * (tq_agg_terms_batch's own selection), and a gather of the survivors' rows, a wavefront per returned entry.  Integer
+ * arithmetic and integer vector atomics only: deterministic.
+ * Afterwards tq_last_batch_match_counts gives `matches`, kernel_mask = TQ_KERNEL_AGG_TERMS_HIST (| TQ_KERNEL_DOCSET_TREE |
+ * TQ_KERNEL_PHRASE_SLOP), and
+ *   algorithmic_bytes = tq_agg_terms_batch's for column T
+ *                     + 8 per counted doc with a value in H
+ *                     + 8 per counted doc of a TQ_CARD_OPTIONAL H (its presence word)
+ *                     + 4 x n_cells per query + 4 x n_buckets per entry returned.
+ * Not served: a metric under the histogram, several leaves, `min_doc_count` / `extended_bounds` (the caller's
+ * post-processing of dense rows), `missing`, multivalued columns, grids above TQ_AGG_MAX_BUCKETS cells. */
+typedef struct tq_agg_terms_hist_request {
+  tq_agg_terms_request terms; /* the key column T, the order, segment_size */
+  uint32_t reserved;          /* zero */
+  tq_agg_request hist;        /* the histogram column H: tq_agg_batch's request with histogram == 1 */
+} tq_agg_terms_hist_request; /* 56 bytes */
+typedef struct tq_agg_terms_hist_plan_t {
+  tq_agg_terms_plan_t terms; /* tq_agg_terms_plan of T */
+  tq_agg_hist_plan_t hist;   /* tq_agg_histogram_plan of H */
+  uint32_t n_cells;          /* n_keys x (n_buckets + 1) <= TQ_AGG_MAX_BUCKETS */
+  uint32_t reserved;
+} tq_agg_terms_hist_plan_t; /* 64 bytes */
+int tq_agg_terms_hist_plan(const tq_column_info_t *info_t, const tq_column_info_t *info_h, const tq_agg_terms_hist_request *req,
+                           tq_agg_terms_hist_plan_t *out);
+int tq_agg_terms_hist_batch(tq_segment *seg, const tq_query *queries, uint32_t n_queries, const tq_agg_terms_hist_request *req,
+                            tq_agg_terms_t *out_terms, uint64_t *out_keys, uint32_t *out_counts, uint32_t *out_hist,
+                            uint32_t out_stride, uint32_t hist_stride);
+/* Same with DEVICE outputs, enqueued on hip_stream (NULL = the segment's stream), no host synchronisation.  Nothing at or
+ * past n_returned of a row set — keys, counts, histogram rows — and nothing at or past n_buckets of a histogram row is
+ * touched.  The call itself zeroes what it accumulates into: the same buffers may be used again. */
+int tq_agg_terms_hist_batch_device(tq_segment *seg, const tq_query *queries, uint32_t n_queries,
+                                   const tq_agg_terms_hist_request *req, tq_agg_terms_t *d_out_terms, uint64_t *d_out_keys,
+                                   uint32_t *d_out_counts, uint32_t *d_out_hist, uint32_t out_stride, uint32_t hist_stride,
+                                   void *hip_stream);
+/* The LDS tables' capacities in cells of the two instantiations of agg_terms_hist_count_kernel: out[0] the small one, out[1]
+ * the large one; a grid of more than min("agg_lds_buckets", out[1]) cells is counted in global memory. */
+void tq_agg_terms_hist_lds_capacities(uint32_t out[2]);
+
 /* ---- introspection ---- */
 typedef struct tq_batch_stats {
   uint64_t algorithmic_bytes; /* sum len(postings_range) [+positions] + matches + 8k */
@@ -1308,6 +1389,7 @@ typedef struct tq_batch_stats {
 #define TQ_KERNEL_AGG_TERMS 0x400000u  /* agg_terms_count_kernel / agg_terms_select_kernel (tq_agg_terms_batch*: the top values of a column by doc count) */
 #define TQ_KERNEL_AGG_TERMS_SUB 0x800000u /* agg_terms_sub_count_kernel / agg_terms_sub_select_kernel (tq_agg_terms_sub_batch*: a metric column's stats per key, order by it) */
 #define TQ_KERNEL_AGG_RANGE 0x1000000u /* agg_range_kernel (tq_agg_range_batch*: doc counts and a metric column's stats per range of a column) */
+#define TQ_KERNEL_AGG_TERMS_HIST 0x2000000u /* agg_terms_hist_count_kernel / _rowsum_ / _gather_ (tq_agg_terms_hist_batch*: a histogram of a second column per key) */
 int tq_last_batch_stats(tq_segment *seg, tq_batch_stats *out);
 /* Which scan-kernel family (one TQ_KERNEL_* bit) evaluated every query of the last tq_search_batch* call on this
  * segment; needs the option "record_query_kernels" set before that call (diagnosis / parity tooling: bench.py

@@ -68,6 +68,7 @@ KERNEL_AGG_SUB = 0x200000
 KERNEL_AGG_TERMS = 0x400000
 KERNEL_AGG_TERMS_SUB = 0x800000
 KERNEL_AGG_RANGE = 0x1000000
+KERNEL_AGG_TERMS_HIST = 0x2000000
 VALUE_U64, VALUE_I64, VALUE_F64 = 0, 1, 2  # tq_value_type (Bool as U64, DateTime as I64 of nanoseconds)
 AGG_MAX_BUCKETS = 65536  # TQ_AGG_MAX_BUCKETS
 AGG_RANGE_MAX_BUCKETS = 1024  # TQ_AGG_RANGE_MAX_BUCKETS
@@ -80,7 +81,8 @@ KERNEL_NAMES = {0x1: "and_dense", 0x2: "and", 0x4: "union", 0x8: "or_windows", 0
                 0x40: "bool", 0x80: "ushare", 0x100: "xunion", 0x200: "ashare", 0x400: "bshare", 0x800: "count_bitmaps",
                 0x1000: "tree", 0x2000: "docset", 0x4000: "docset_score", 0x8000: "all", 0x10000: "docset_tree",
                 0x20000: "docset_tree_score", 0x40000: "phrase_slop", 0x80000: "sort", 0x100000: "agg", 0x200000: "agg_sub",
-                0x400000: "agg_terms", 0x800000: "agg_terms_sub", 0x1000000: "agg_range"}
+                0x400000: "agg_terms", 0x800000: "agg_terms_sub", 0x1000000: "agg_range",
+                0x2000000: "agg_terms_hist"}
 
 
 def kernel_names(mask):
@@ -180,6 +182,7 @@ EXPORTS = [
     "tq_agg_terms_sub_batch", "tq_agg_terms_sub_batch_device", "tq_agg_terms_sub_lds_capacities", "tq_agg_terms_metric_image",
     "tq_agg_range_plan", "tq_agg_range_bucket_of", "tq_agg_range_batch", "tq_agg_range_batch_device",
     "tq_agg_range_lds_capacities",
+    "tq_agg_terms_hist_plan", "tq_agg_terms_hist_batch", "tq_agg_terms_hist_batch_device", "tq_agg_terms_hist_lds_capacities",
 ]
 
 # tq_term_table_read's tables (TQ_TABLE_*): name -> (which, dtype of the array DeviceIndex.term_table returns)
@@ -658,6 +661,105 @@ def terms_sub_finalize(merged, value_type, size=10, min_doc_count=1, order=TERMS
             "doc_count_error_upper_bound": merged["doc_count_error_upper_bound"]}
 
 
+class TqAggTermsHistRequest(C.Structure):  # tq_agg_terms_hist_request
+    _fields_ = [("terms", TqAggTermsRequest), ("reserved", C.c_uint32), ("hist", TqAggRequest)]
+
+
+class TqAggTermsHistPlan(C.Structure):  # tq_agg_terms_hist_plan_t
+    _fields_ = [("terms", TqAggTermsPlan), ("hist", TqAggHistPlan), ("n_cells", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _agg_terms_hist_request(column, hist_column, value_type, histogram, order, segment_size, reserved=(0, 0), histogram_flag=1):
+    """histogram: the dict of raw_agg ("interval", optionally "offset", "hard_bounds"); reserved: the request's and the
+    histogram half's reserved fields; histogram_flag: the histogram half's `histogram` byte (1 in every served request)."""
+    req = TqAggTermsHistRequest()
+    req.terms = TqAggTermsRequest(column=int(column), order=int(order), segment_size=int(segment_size))
+    req.hist = _agg_request(hist_column, value_type, histogram)
+    req.hist.histogram = int(histogram_flag)
+    req.reserved, req.hist.reserved = int(reserved[0]), int(reserved[1])
+    return req
+
+
+def _agg_terms_hist_plan_dict(plan, req):
+    return {"terms": _agg_terms_plan_dict(plan.terms), "hist": _agg_plan_dict(plan.hist, req.hist), "n_cells": int(plan.n_cells)}
+
+
+def agg_terms_hist_plan(info_t, info_h, value_type, histogram, order=TERMS_COUNT_DESC, segment_size=10, reserved=(0, 0),
+                        histogram_flag=1):
+    """tq_agg_terms_hist_plan: the terms plan of the key column, the histogram plan of the histogram column and the grid of
+    one query, from the columns' info dicts.  -> {"terms": agg_terms_plan's dict, "hist": agg_histogram_plan's dict,
+    "n_cells": n_keys * (n_buckets + 1)}.  Needs no device."""
+    ct = TqColumnInfo(**{n: int(info_t[n]) for n, _ in TqColumnInfo._fields_ if n in info_t})
+    ch = TqColumnInfo(**{n: int(info_h[n]) for n, _ in TqColumnInfo._fields_ if n in info_h})
+    req = _agg_terms_hist_request(0, 0, value_type, histogram, order, segment_size, reserved, histogram_flag)
+    plan = TqAggTermsHistPlan()
+    _check(lib().tq_agg_terms_hist_plan(C.byref(ct), C.byref(ch), C.byref(req), C.byref(plan)))
+    return _agg_terms_hist_plan_dict(plan, req)
+
+
+def agg_terms_hist_lds_capacities():
+    """tq_agg_terms_hist_lds_capacities: the LDS tables' capacities in cells of agg_terms_hist_count_kernel's (small, large)
+    instantiation.  Needs no device."""
+    out = (C.c_uint32 * 2)()
+    lib().tq_agg_terms_hist_lds_capacities(out)
+    return int(out[0]), int(out[1])
+
+
+def merge_terms_hist(per_segment_results):
+    """merge_terms with a histogram row per key: an item is (keys, counts, rows, terms record, hist plan dict) — the query's
+    rows as raw_agg_terms_hist returns them, of which the first n_returned entries are taken, and plan["hist"] of that
+    segment — or a dict this function returned.  Counts add per key as in merge_terms; a key's rows are aligned by base_pos
+    and added as in merge_histograms, over the dense range from the lowest to the highest bucket of ANY segment, so every
+    entry carries a row of the same length.  -> {"entries": {key: (doc_count, [counts])}, "bucket_keys": [pos * interval +
+    offset], "base_pos", "interval", "offset", "sum_other_doc_count", "doc_count_error_upper_bound"}.  Host only."""
+    parts = []
+    for part in per_segment_results:
+        if isinstance(part, dict):
+            if part["interval"] is None:  # (the merge of nothing)
+                continue
+            items = [(k, c, r) for k, (c, r) in part["entries"].items()]
+            parts.append((items, part["sum_other_doc_count"], part["doc_count_error_upper_bound"], part["base_pos"],
+                          len(part["bucket_keys"]), part["interval"], part["offset"]))
+        else:
+            keys, counts, rows, rec, hp = part
+            n = int(rec["n_returned"])
+            items = [(keys[j], counts[j], rows[j][:hp["n_buckets"]] if hp["n_buckets"] else []) for j in range(n)]
+            parts.append((items, rec["sum_other_doc_count"], rec["doc_count_error_upper_bound"], hp["base_pos"], hp["n_buckets"],
+                          hp["interval"], hp["offset"]))
+    out = {"entries": {}, "bucket_keys": [], "base_pos": 0, "interval": None, "offset": None, "sum_other_doc_count": 0,
+           "doc_count_error_upper_bound": 0}
+    if parts:
+        out["interval"], out["offset"] = parts[0][5], parts[0][6]
+        assert all(p[5] == out["interval"] and p[6] == out["offset"] for p in parts)
+    ranged = [p for p in parts if p[4]]
+    lo = min((p[3] for p in ranged), default=0)
+    hi = max((p[3] + p[4] for p in ranged), default=0)
+    out["base_pos"] = lo
+    out["bucket_keys"] = [float(pos) * out["interval"] + out["offset"] for pos in range(lo, hi)]
+    for items, other, err, base_pos, n_buckets, _, _ in parts:
+        for k, c, r in items:
+            c0, row = out["entries"].get(int(k), (0, None))
+            row = [0] * (hi - lo) if row is None else row
+            for i in range(n_buckets):
+                row[base_pos - lo + i] += int(r[i])
+            out["entries"][int(k)] = (c0 + int(c), row)
+        out["sum_other_doc_count"] += int(other)
+        out["doc_count_error_upper_bound"] += int(err)
+    return out
+
+
+def terms_hist_finalize(merged, size=10, min_doc_count=1, order=TERMS_COUNT_DESC):
+    """terms_finalize of merge_terms_hist's result, each bucket carrying its row: entries below min_doc_count are dropped, the
+    rest ordered (ties by ascending key) and cut at `size`.  -> {"buckets": [(key, doc_count, [counts])], "bucket_keys",
+    "sum_other_doc_count", "doc_count_error_upper_bound"}; a bucket's row is dense over bucket_keys (the histogram's own
+    min_doc_count and extended_bounds stay the caller's).  Host only."""
+    flat = terms_finalize({"entries": {k: c for k, (c, _) in merged["entries"].items()},
+                           "sum_other_doc_count": merged["sum_other_doc_count"],
+                           "doc_count_error_upper_bound": merged["doc_count_error_upper_bound"]}, size, min_doc_count, order)
+    return {"buckets": [(k, c, list(merged["entries"][k][1])) for k, c in flat["buckets"]], "bucket_keys": list(merged["bucket_keys"]),
+            "sum_other_doc_count": flat["sum_other_doc_count"], "doc_count_error_upper_bound": flat["doc_count_error_upper_bound"]}
+
+
 def merge_histograms(parts):
     """The segments' histogram rows of ONE query and ONE request: parts = [(plan, counts)] as raw_agg returns them (plan
     dict, counts = the query's row).  The rows are aligned by base_pos and added.  -> (keys, counts): keys[i] = pos *
@@ -796,6 +898,14 @@ def lib():
                                             C.POINTER(TqAggMetricRequest), vp, vp, vp, C.c_uint32, vp]
     L.tq_agg_range_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
     L.tq_agg_range_lds_capacities.restype = None
+    L.tq_agg_terms_hist_plan.argtypes = [C.POINTER(TqColumnInfo), C.POINTER(TqColumnInfo), C.POINTER(TqAggTermsHistRequest),
+                                         C.POINTER(TqAggTermsHistPlan)]
+    L.tq_agg_terms_hist_batch.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsHistRequest), vp, vp, u32p, u32p,
+                                          C.c_uint32, C.c_uint32]
+    L.tq_agg_terms_hist_batch_device.argtypes = [vp, C.POINTER(TqQuery), C.c_uint32, C.POINTER(TqAggTermsHistRequest), vp, vp, vp, vp,
+                                                 C.c_uint32, C.c_uint32, vp]
+    L.tq_agg_terms_hist_lds_capacities.argtypes = [C.POINTER(C.c_uint32)]
+    L.tq_agg_terms_hist_lds_capacities.restype = None
     L.tq_agg_terms_max_size.argtypes = []
     L.tq_agg_terms_max_size.restype = C.c_uint32
     L.tqh_searcher_add_segment_fields.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint8, C.c_uint32, C.POINTER(TqFieldFiles),
@@ -2032,6 +2142,71 @@ class DeviceIndex:
                                                    d_counts.data_ptr() if d_counts is not None else None,
                                                    d_records.data_ptr() if d_records is not None else None, int(stride),
                                                    C.c_void_p(stream) if stream else None)
+
+    # ---- terms x histogram (tq_agg_terms_hist.cpp, tq_agg_terms_hist.hip)
+    def agg_terms_hist_plan(self, column, hist_column, value_type, histogram, order=TERMS_COUNT_DESC, segment_size=10, segment_ord=0):
+        """tq_agg_terms_hist_plan of two resident columns: {"terms", "hist", "n_cells"}."""
+        return agg_terms_hist_plan(self.column_info(column, segment_ord), self.column_info(hist_column, segment_ord), value_type,
+                                   histogram, order, segment_size)
+
+    def raw_agg_terms_hist(self, queries, column, hist_column, value_type, histogram, order=TERMS_COUNT_DESC, segment_size=10,
+                           segment_ord=0, device=False, stride=None, hist_stride=None, reserved=(0, 0), histogram_flag=1):
+        """Direct tq_agg_terms_hist_batch on one segment: raw_agg_terms' arguments, the histogram column with its value type
+        and raw_agg's histogram dict.  -> (terms, keys [n, width] uint64, counts [n, width] uint32, rows [n, width, n_buckets]
+        uint32, plan dict of agg_terms_hist_plan), width = min(segment_size, n_keys); of row set q the first
+        terms[q]["n_returned"] entries are the result, in the request's order.  stride / hist_stride: the strides in the call
+        (default width / n_buckets; the arrays come back that wide when given); device=True: through
+        tq_agg_terms_hist_batch_device into torch tensors on the segment's GPU (what the call leaves alone keeps the fill)."""
+        n = len(queries)
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_terms_hist_request(column, hist_column, value_type, histogram, order, segment_size, reserved, histogram_flag)
+        plan = TqAggTermsHistPlan()
+        it, ih = TqColumnInfo(), TqColumnInfo()  # (the call makes the same plan; a refusal comes from the call, under its name)
+        seg = self.segment_raw(segment_ord)
+        if lib().tq_column_info(seg, int(column), C.byref(it)) == 0 and lib().tq_column_info(seg, int(hist_column), C.byref(ih)) == 0:
+            lib().tq_agg_terms_hist_plan(C.byref(it), C.byref(ih), C.byref(req), C.byref(plan))
+        width, n_buckets = min(int(segment_size), int(plan.terms.n_keys)), int(plan.hist.n_buckets)
+        out_w = width if stride is None else int(stride)
+        out_b = n_buckets if hist_stride is None else int(hist_stride)
+        shape = (max(1, n), max(1, out_w))
+        if device:
+            import torch
+
+            dv = torch.device("cuda", self._devs[segment_ord % len(self._devs)])  # (where __init__ put the segment)
+            d_terms = torch.full((max(1, n), 5), 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_keys = torch.full(shape, 0x5A5A5A5A, dtype=torch.int64, device=dv)
+            d_counts = torch.full(shape, 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            d_rows = torch.full(shape + (max(1, out_b),), 0x5A5A5A5A, dtype=torch.int32, device=dv)
+            torch.cuda.synchronize(dv)
+            _check(lib().tq_agg_terms_hist_batch_device(seg, qs, n, C.byref(req), d_terms.data_ptr(), d_keys.data_ptr(),
+                                                        d_counts.data_ptr(), d_rows.data_ptr(), out_w, out_b, None))
+            self.last_batch_stats(segment_ord)  # (waits for the segment's stream)
+            torch.cuda.synchronize(dv)
+            terms = d_terms.cpu().numpy().view(np.uint64).reshape(-1).view(AGG_TERMS_DTYPE)
+            keys = d_keys.cpu().numpy().view(np.uint64)
+            counts = d_counts.cpu().numpy().view(np.uint32)
+            rows = d_rows.cpu().numpy().view(np.uint32)
+        else:
+            terms = np.zeros(max(1, n), AGG_TERMS_DTYPE)
+            keys = np.full(shape, 0xDEADBEEF, np.uint64)
+            counts = np.full(shape, 0xDEADBEEF, np.uint32)
+            rows = np.full(shape + (max(1, out_b),), 0xDEADBEEF, np.uint32)
+            _check(lib().tq_agg_terms_hist_batch(seg, qs, n, C.byref(req), terms.ctypes.data, keys.ctypes.data, _u32(counts), _u32(rows),
+                                                 out_w, out_b))
+        return terms[:n], keys[:n, :out_w], counts[:n, :out_w], rows[:n, :out_w, :out_b], _agg_terms_hist_plan_dict(plan, req)
+
+    def raw_agg_terms_hist_device(self, queries, column, hist_column, value_type, histogram, order, segment_size, stride, hist_stride,
+                                  d_terms, d_keys, d_counts, d_rows, segment_ord=0, stream=None, reserved=(0, 0), histogram_flag=1):
+        """Direct tq_agg_terms_hist_batch_device: raw_agg_terms_device's tensors and d_rows (int32 / uint32, len(queries) *
+        stride * hist_stride entries, or None), torch tensors on the segment's GPU; only enqueues.  -> rc"""
+        qs, keep = self._raw_flat_queries(queries, segment_ord)
+        req = _agg_terms_hist_request(column, hist_column, value_type, histogram, order, segment_size, reserved, histogram_flag)
+        return lib().tq_agg_terms_hist_batch_device(self.segment_raw(segment_ord), qs, len(queries), C.byref(req),
+                                                    d_terms.data_ptr() if d_terms is not None else None,
+                                                    d_keys.data_ptr() if d_keys is not None else None,
+                                                    d_counts.data_ptr() if d_counts is not None else None,
+                                                    d_rows.data_ptr() if d_rows is not None else None, int(stride), int(hist_stride),
+                                                    C.c_void_p(stream) if stream else None)
 
     def _raw_scored_queries(self, queries, weights, cache, segment_ord):
         """_raw_flat_queries with the scoring fields: weights = per-query lists of floats (or None: left NULL), cache =

@@ -39,6 +39,8 @@ SOURCES = [
     os.path.join(HERE, "csrc", "tq_agg_terms_sub.cpp"),
     os.path.join(HERE, "csrc", "tq_agg_range.hip"),
     os.path.join(HERE, "csrc", "tq_agg_range.cpp"),
+    os.path.join(HERE, "csrc", "tq_agg_terms_hist.hip"),
+    os.path.join(HERE, "csrc", "tq_agg_terms_hist.cpp"),
     os.path.join(HERE, "csrc", "tq_xunion.hip"),
     os.path.join(HERE, "csrc", "tq_phrase.hip"),
     os.path.join(HERE, "csrc", "tq_phrase_slop.hip"),
@@ -115,9 +117,12 @@ KERNEL_FILES = {"and_kernel": "tq_and.hip", "union_kernel_small": "tq_union.hip"
                 "agg_terms_init_kernel": "tq_agg_terms.hip",
                 "agg_terms_sub_count_kernel": "tq_agg_terms_sub.hip", "agg_terms_sub_select_kernel": "tq_agg_terms_sub.hip",
                 "agg_terms_sub_init_kernel": "tq_agg_terms_sub.hip",
-                "agg_range_kernel": "tq_agg_range.hip"}
-# the headers the six doc-set consumers (sort, the five aggregations) are assembled from: hashed with any of them
-WALK_FILES = {"tq_sort.hip", "tq_agg.hip", "tq_agg_sub.hip", "tq_agg_terms.hip", "tq_agg_terms_sub.hip", "tq_agg_range.hip"}
+                "agg_range_kernel": "tq_agg_range.hip",
+                "agg_terms_hist_count_kernel": "tq_agg_terms_hist.hip", "agg_terms_hist_rowsum_kernel": "tq_agg_terms_hist.hip",
+                "agg_terms_hist_gather_kernel": "tq_agg_terms_hist.hip", "agg_terms_hist_init_kernel": "tq_agg_terms_hist.hip"}
+# the headers the seven doc-set consumers (sort, the six aggregations) are assembled from: hashed with any of them
+WALK_FILES = {"tq_sort.hip", "tq_agg.hip", "tq_agg_sub.hip", "tq_agg_terms.hip", "tq_agg_terms_sub.hip", "tq_agg_range.hip",
+              "tq_agg_terms_hist.hip"}
 WALK_HEADERS = {"tq_docset_word.hpp", "tq_docset_walk.hpp", "tq_column_read.hpp", "tq_agg_value.hpp", "tq_agg_device.hpp",
                 "tq_agg_terms_select.hpp", "tq_agg_metric_image.hpp", "tq_agg_range_search.hpp"}
 

@@ -127,6 +127,10 @@ int agg_host_call(tq_segment *s, const char *fn, const tq_query *queries, uint32
 
 }  // namespace
 
+int agg_histogram_plan_checked(const char *fn, const tq_column_info_t &info, const tq_agg_request &req, tq_agg_hist_plan_t *out) {
+  return histogram_plan(fn, info, req, out);
+}
+
 // The host-output variant of a checked call whose rows are plan.n_buckets entries per query (the histogram's, the range
 // aggregation's): the segment is locked, spec holds everything but the outputs.
 int agg_host_run(tq_segment *s, const char *fn, const tq_query *queries, uint32_t n_queries, AggSpec &spec, tq_agg_stats_t *out_stats,

@@ -1,5 +1,5 @@
 // tq_agg_device.hpp — the device helpers the kernels over a doc set and a fast-field column share (tq_sort.hip, tq_agg.hip,
-// tq_agg_sub.hip, tq_agg_terms.hip, tq_agg_terms_sub.hip, tq_agg_range.hip), all in this one header:
+// tq_agg_sub.hip, tq_agg_terms.hip, tq_agg_terms_sub.hip, tq_agg_range.hip, tq_agg_terms_hist.hip), all in this one header:
 //   col_value / col_key_index   a row's value, and its key index (value - min) / gcd, by the column's codec
 //   wave_sum64 / add128         a wavefront's sum; the 128-bit atomic add
 //   AggStatsLane, agg_stats_*   the top-level 64-byte stats record: per lane, per wavefront, per workgroup, published

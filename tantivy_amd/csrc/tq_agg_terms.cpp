@@ -65,6 +65,7 @@ AggSpec terms_spec(const tq_agg_terms_request *req, const tq_agg_terms_plan_t &p
 
 // what the count launches add to: the totals, every query's match count, the records and the scratch rows
 int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st) {
+  if (spec.terms_hist) return agg_terms_hist_prepare(s, spec, n_queries, st);
   if (spec.terms_sub) return agg_terms_sub_prepare(s, spec, n_queries, st);
   const uint32_t n_keys = spec.terms_plan.n_keys;
   const int rc = s->d_agg_term_rows.ensure((size_t)n_queries * n_keys * sizeof(uint32_t) + 64u);
@@ -78,6 +79,7 @@ int agg_terms_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStrea
 
 // the count launch in place of a sub-batch's count / scan / write passes: records and rows under the caller's query index
 int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st) {
+  if (spec.terms_hist) return agg_terms_hist_launch(s, spec, p, q0, st);
   if (spec.terms_sub) return agg_terms_sub_launch(s, spec, p, q0, st);
   const tq_segment::ColumnHost &col = s->columns[spec.column];
   uint32_t caps[2];
@@ -100,6 +102,7 @@ int agg_terms_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &
 
 // the selection, once, behind the last sub-batch's count launch on the same stream
 int agg_terms_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st) {
+  if (spec.terms_hist) return agg_terms_hist_finish(s, spec, n_queries, st);
   if (spec.terms_sub) return agg_terms_sub_finish(s, spec, n_queries, st);
   TqkAggTermsSelectParams sp{};
   sp.records = (TqkAggTerms *)spec.d_terms;

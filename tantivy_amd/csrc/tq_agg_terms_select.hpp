@@ -1,5 +1,6 @@
 // tq_agg_terms_select.hpp — the exact top-N selection of a terms aggregation: the body of agg_terms_select_kernel
-// (tq_agg_terms.hip, a 64-bit key) and agg_terms_sub_select_kernel (tq_agg_terms_sub.hip, a 128-bit key).  One workgroup
+// (tq_agg_terms.hip, a 64-bit key; tq_agg_terms_hist.cpp launches it over its totals rows) and agg_terms_sub_select_kernel
+// (tq_agg_terms_sub.hip, a 128-bit key).  One workgroup
 // per query over the query's count row: a composite key per non-empty entry — never 0, unique per entry, so nothing ties,
 // the order's first entry the largest — of which the segment_size LARGEST survive.  The segment_size-th largest key is
 // found exactly by an MSB-first radix select, 8 bits a pass with a 256-bin LDS histogram; one more pass compacts the

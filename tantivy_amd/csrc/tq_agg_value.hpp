@@ -1,5 +1,5 @@
 // tq_agg_value.hpp — how a u64-space column value becomes the f64 a histogram buckets, and how that f64's bucket
-// position becomes an integer.  One piece of code for the kernels (tq_agg.hip, tq_agg_sub.hip) and the host plan
+// position becomes an integer.  One piece of code for the kernels (tq_agg.hip, tq_agg_sub.hip, tq_agg_terms_hist.hip) and the host plan
 // (tq_agg.cpp), which must agree bit for bit with each other and with the reference's f64_from_fastfield_u64
 // (src/aggregation/mod.rs:351-383; common/src/lib.rs:108-114 u64_to_f64) and `f64 as i64`.  Built with -ffp-contract=off.
 #pragma once

@@ -489,6 +489,11 @@ int tq_last_batch_stats(tq_segment *s, tq_batch_stats *out) {
           HIP_TRY(hipMemcpy(b, s->d_match_counter + 4, sizeof b, hipMemcpyDeviceToHost));
           s->stats.algorithmic_bytes += 40u * e + 8u * b[0] + (s->stats_agg_metric_optional ? 8u * b[1] : 0u);
         }
+        if (s->stats_agg_terms_hist_row) {  // 4 x n_buckets more per entry returned (its row); the histogram column's reads
+          unsigned long long b[2] = {0, 0};
+          HIP_TRY(hipMemcpy(b, s->d_match_counter + 4, sizeof b, hipMemcpyDeviceToHost));
+          s->stats.algorithmic_bytes += 4u * (uint64_t)(s->stats_agg_terms_hist_row - 1u) * e + 8u * b[0] + (s->stats_agg_metric_optional ? 8u * b[1] : 0u);
+        }
       }
       s->stats_sorted = false;
     } else {

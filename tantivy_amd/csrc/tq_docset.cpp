@@ -13,7 +13,7 @@
 // docset_batch runs one DocsetCall as stages around one Batch record: check_and_express, plan_trees, cut_docset_subs,
 // size_and_upload, then per sub-batch launch_match_bits and launch_consumer, driven by run_device / run_host.  The consumer
 // of a sub-batch's match words is one of four: rows, the count pass alone (tq_count_batch), or the launches tq_sort.cpp
-// (tq_search_sorted_batch*) / tq_agg.cpp (tq_agg_batch*, tq_agg_sub_batch*, tq_agg_terms_batch*, tq_agg_terms_sub_batch*, tq_agg_range_batch*) put in place of the count / scan / write passes.
+// (tq_search_sorted_batch*) / tq_agg.cpp (tq_agg_batch*, tq_agg_sub_batch*, tq_agg_terms_batch*, tq_agg_terms_sub_batch*, tq_agg_range_batch*, tq_agg_terms_hist_batch*) put in place of the count / scan / write passes.
 #include "tq_internal.hpp"
 
 #include <deque>
@@ -624,6 +624,7 @@ int run_device(const Batch &b) {
   s->stats_agg_metric_optional = call.agg && call.agg->metric_optional;
   s->stats_agg_terms = call.agg && call.agg->terms;
   s->stats_agg_terms_sub = call.agg && call.agg->terms_sub;
+  s->stats_agg_terms_hist_row = call.agg && call.agg->terms_hist ? call.agg->plan.n_buckets + 1u : 0u;
   HIP_TRY(hipEventRecord(s->ev_batch_done, b.st));
   s->last_stream = b.st;
   s->batch_in_flight = true;
@@ -694,7 +695,7 @@ int docset_batch(tq_segment *s, const tq_query *queries, uint32_t n_queries, con
   if (rc != TQ_OK) return rc;
   const bool scored = call.scored;
   s->stats = tq_batch_stats{};
-  s->stats.kernel_mask = (call.consumer == Consumer::kSort ? TQ_KERNEL_SORT : call.consumer == Consumer::kAgg ? (call.agg->terms_sub ? TQ_KERNEL_AGG_TERMS_SUB : call.agg->terms ? TQ_KERNEL_AGG_TERMS : call.agg->range ? TQ_KERNEL_AGG_RANGE : call.agg->metric ? TQ_KERNEL_AGG_SUB : TQ_KERNEL_AGG) : TQ_KERNEL_DOCSET) |
+  s->stats.kernel_mask = (call.consumer == Consumer::kSort ? TQ_KERNEL_SORT : call.consumer == Consumer::kAgg ? (call.agg->terms_hist ? TQ_KERNEL_AGG_TERMS_HIST : call.agg->terms_sub ? TQ_KERNEL_AGG_TERMS_SUB : call.agg->terms ? TQ_KERNEL_AGG_TERMS : call.agg->range ? TQ_KERNEL_AGG_RANGE : call.agg->metric ? TQ_KERNEL_AGG_SUB : TQ_KERNEL_AGG) : TQ_KERNEL_DOCSET) |
                          (scored ? TQ_KERNEL_DOCSET_SCORE : 0u) | (b.tqs.empty() ? 0u : TQ_KERNEL_DOCSET_TREE) |
                          (scored && !b.tqs.empty() ? TQ_KERNEL_DOCSET_TREE_SCORE : 0u) | (b.slop_qs.empty() ? 0u : TQ_KERNEL_PHRASE_SLOP);
   s->stats.algorithmic_bytes = b.algo_bytes;

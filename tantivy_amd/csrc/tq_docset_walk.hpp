@@ -1,6 +1,6 @@
 // tq_docset_walk.hpp — the walk of one query's match bits that hands every matching doc to a lane: the loop of the
 // kernels that consume a doc set without writing it (tq_sort.hip, tq_agg.hip, tq_agg_sub.hip, tq_agg_terms.hip,
-// tq_agg_terms_sub.hip, tq_agg_range.hip).  A workgroup = (query, slice of the bitmap words) of four wavefronts, each walking every fourth
+// tq_agg_terms_sub.hip, tq_agg_range.hip, tq_agg_terms_hist.hip).  A workgroup = (query, slice of the bitmap words) of four wavefronts, each walking every fourth
 // 64-word chunk of the slice on its own (no workgroup barrier inside the walk):
 //   1. a lane evaluates one word (docset_word, tq_docset_word.hpp), the popcounts are prefix-summed over the wavefront
 //   2. every lane expands its word's bits into the wavefront's LDS slab (13 bits per doc: word of the chunk, bit)

@@ -489,6 +489,9 @@ struct tq_segment {
   // ... with a metric (tq_agg_terms_sub_batch*): d_match_counter[4] = counted docs with a value in the metric column,
   // [5] = counted docs; 40 more bytes per entry returned
   bool stats_agg_terms_sub = false;
+  // ... with a histogram per key (tq_agg_terms_hist_batch*): d_match_counter[4] / [5] likewise for the histogram column;
+  // its buckets + 1 (0: not such a call): 4 x buckets per entry returned
+  uint32_t stats_agg_terms_hist_row = 0;
   // host planner scratch (launch groups, chunk tables): kept between batches so that planning a
   // batch does not start by page-faulting tens of megabytes of fresh vectors
   struct PlanScratch *plan = nullptr;
@@ -1139,6 +1142,12 @@ struct AggSpec {
   const tq_agg_range_request *range = nullptr;
   std::vector<tq_agg_range_bucket_t> range_plan;
   const uint64_t *d_range_starts = nullptr;
+  // tq_agg_terms_hist_batch* (tq_agg_terms_hist.cpp): `terms` (the request's terms part) with a histogram of a second column
+  // H per key — the request's hist part, its plan in `plan`, value_type / interval / offset as for a histogram; the
+  // survivors' rows at d_buckets, row (q, j) at (q * terms_stride + j) * bucket_stride; the grid and totals rows are the
+  // segment's scratch (terms_n_queries as above).  metric_optional: H has a presence table
+  const tq_agg_terms_hist_request *terms_hist = nullptr;
+  uint32_t terms_hist_cells = 0;  // n_keys x (n_buckets + 1)
 };
 // One call of the doc-set route: who consumes the match words of its sub-batches, and where the results go.
 // kRows: CSR rows of ascending doc ids, `scored` with every doc's score beside it; kCount (host outputs): the count pass
@@ -1219,6 +1228,12 @@ int agg_host_run(tq_segment *s, const char *fn, const tq_query *queries, uint32_
 int agg_terms_sub_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
 int agg_terms_sub_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
 int agg_terms_sub_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
+// tq_agg_terms_hist.cpp: what the three do for a spec with `terms_hist`
+int agg_terms_hist_prepare(tq_segment *s, AggSpec &spec, uint32_t n_queries, hipStream_t st);
+int agg_terms_hist_launch(tq_segment *s, const AggSpec &spec, const TqkDocsetParams &p, uint32_t q0, hipStream_t st);
+int agg_terms_hist_finish(tq_segment *s, const AggSpec &spec, uint32_t n_queries, hipStream_t st);
+// tq_agg.cpp: tq_agg_histogram_plan under `fn`
+int agg_histogram_plan_checked(const char *fn, const tq_column_info_t &info, const tq_agg_request &req, tq_agg_hist_plan_t *out);
 // A phrase or nested boolean query as plan_tree_query takes it for a doc set (option "docset_trees"): unit weights
 // whatever the caller's are (doc sets score nothing; weights may be NULL), and a TQ_MODE_PHRASE query as the tree "one
 // Must clause holding one phrase atom" with the caller's phrase_offsets.  scored (option "docset_score_trees"): the

@@ -580,6 +580,42 @@ hipError_t tqk_launch_agg_terms_sub_init(TqkAggTerms *records, uint32_t *rows, T
 hipError_t tqk_launch_agg_terms_sub_count(const TqkAggTermsSubParams &p, hipStream_t st);
 hipError_t tqk_launch_agg_terms_sub_select(const TqkAggTermsSubSelectParams &p, hipStream_t st);
 void tqk_agg_terms_sub_lds_capacities(uint32_t out[2]);  // the count kernel's two LDS tables, in keys: small, large
+// ---- terms x histogram (tq_agg_terms_hist.hip): a histogram of a column H per key of a column T over a doc set
+// (tq_agg_terms_hist_batch*).  The scratch is per query a GRID row of n_cells = n_keys x (n_buckets + 1) entries — key i's
+// row at i x (n_buckets + 1), its last entry the docs outside the histogram — and a TOTALS row of n_keys entries.
+// tqk_launch_agg_terms_hist_init in front; one count launch per sub-batch adds to the records and the grid rows with vector
+// atomics; behind the last of them the row sums into the totals rows, tqk_launch_agg_terms_select over the totals rows, and
+// the gather of the survivors' rows.
+struct TqkAggTermsHistParams {
+  TqkAggTermsParams t;         // the key column T and everything the terms count launch takes; t.rows: the GRID rows of the
+                               // sub-batch's first query on, [n_queries][n_cells]; t.lds_buckets against n_cells; t.totals is
+                               // [6]: += matches, matches with a value in T, -, entries returned (the select launch), counted
+                               // docs with a value in H, counted docs
+  TqkColumn col_h;             // the histogram column
+  uint64_t min_value_h, gcd_h;
+  double interval, offset;     // pos = floor((val - offset) / interval)
+  double bounds_min, bounds_max;  // the effective bounds (tq_agg_hist_plan_t)
+  int64_t base_pos;            // bucket of a key row's entry 0
+  uint32_t n_buckets;          // a key's row has n_buckets + 1 entries
+  uint32_t value_type_h;       // TQ_VALUE_*
+};
+struct TqkAggTermsHistFinishParams {
+  const TqkAggTerms *records;  // [n_queries] of the whole batch (the gather reads n_returned)
+  const uint32_t *grid;        // [n_queries][n_keys x (n_buckets + 1)]
+  uint32_t *totals_rows;       // [n_queries][n_keys]: the row-sum launch writes every entry
+  const uint64_t *out_keys;    // [n_queries][out_stride]: what the select launch wrote
+  uint32_t *out_hist;          // [n_queries][out_stride][hist_stride]: entries [0, n_buckets) of rows [0, n_returned)
+  uint64_t min_value, gcd;     // index = (key - min) / gcd
+  uint32_t n_queries, n_keys, n_buckets;
+  uint32_t out_stride, hist_stride;
+  uint32_t width;              // min(segment_size, n_keys): the most entries a query returns
+};
+hipError_t tqk_launch_agg_terms_hist_init(TqkAggTerms *records, uint32_t *grid, uint32_t *totals_rows, uint32_t n_queries, uint32_t n_cells,
+                                          uint32_t n_keys, hipStream_t st);
+hipError_t tqk_launch_agg_terms_hist_count(const TqkAggTermsHistParams &p, hipStream_t st);
+hipError_t tqk_launch_agg_terms_hist_rowsum(const TqkAggTermsHistFinishParams &p, hipStream_t st);
+hipError_t tqk_launch_agg_terms_hist_gather(const TqkAggTermsHistFinishParams &p, hipStream_t st);
+void tqk_agg_terms_hist_lds_capacities(uint32_t out[2]);  // the count kernel's two LDS tables, in cells: small, large
 // ---- scores of full doc sets (tq_docset_score.hip): the pass behind the write pass of a tq_docset_scored_batch* call.
 // How a scoring list answers "is doc d in the list, with which tf" (chosen by the host per list):
 #define TQK_SCORE_BITMAP 0u  // tab = the list's bitmap + rank directory, aux = its byte-wide tfs (null: read the block)
