@@ -66,7 +66,8 @@ def _assert_hits(got, want, mode, n_terms):
 def _assert_hits_close(got, want, tol=1e-5):
     """3+ term sums: the reference's own sum order is not canonical (block_wand_union.rs sums in
     cursor order), so ranks are compared score-wise and docs up to swaps between near-ties, the
-    way the reference's tests do (block_wand_union.rs:327-349)."""
+    way the reference's tests do (block_wand_union.rs:327-349).
+    Which members of a tie class a row holds is checked exactly in tests/test_gpu_plateau_ties.py."""
     assert len(got) == len(want)
     for (gs, _), (ws, _) in zip(got, want):
         assert rel_close(gs, ws, tol), (gs, ws)
